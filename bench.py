@@ -21,7 +21,14 @@ the timed region.  Prints ONE JSON line on rank 0.
 BASELINE.json configs[3] (the second headline metric's workload): DAVIS label propagation on a synthetic
 480x854 clip with the reference's test-time settings; one "step" = one propagated frame (backbone of the frame,
 L2 normalisation, masked attention over first + 20 preceding frames, upsample / min-max / argmax).  Same JSON
-schema (`roofline` on the in-mask affinity FLOP, `cpu_baseline` = the C oracle per frame).  N > 1: replicas."""
+schema (`roofline` on the in-mask affinity FLOP, `cpu_baseline` = the C oracle per frame).  N > 1: replicas.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line.  Everything else it can measure - the
+per-kernel roofline leg, the CPU baselines, the DAVIS leg and the ResNet-18 / 512^2 legs of the train line, the DAVIS steady
+state, the all-reduce timing of N > 1 - runs only with --full (the --no-* options then drop single parts of it).
+
+  --dump-outputs DIR   after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64,
+                       64 MB at most; larger arrays as a fixed seeded sample).  Same arguments -> same inputs, run after run."""
 import argparse
 import json
 import os
@@ -45,6 +52,39 @@ WORK_PER_PAIR = {(50, 256): (64.2e9, 232e6), (50, 224): (49.2e9, 178e6), (50, 51
 
 def log(*a):
     print(f'[bench {time.strftime("%H:%M:%S")}]', *a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: every array of one run together
+DUMP_SAMPLE = 1 << 22            # elements kept of a larger array (16 MB in float32)
+
+
+_SAMPLE_IDX = {}
+
+
+def sample_flat(t, k=DUMP_SAMPLE, seed=0):
+    """t flattened: all of it up to k elements, else the k elements at fixed seeded positions (ascending; the same positions
+    for every array of the same length)"""
+    t = t.reshape(-1)
+    if t.numel() <= k:
+        return t
+    if (t.numel(), k, seed) not in _SAMPLE_IDX:
+        _SAMPLE_IDX[t.numel(), k, seed] = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    return t[_SAMPLE_IDX[t.numel(), k, seed].to(t.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor or array} -> dirname/<name>.npy, float64 kept, everything else as float32"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f'--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}')
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    log(f'outputs of the last timed step: {", ".join(arrays)} ({total / 1e6:.1f} MB) in {dirname}')
 
 
 def _free_port():
@@ -165,7 +205,7 @@ def extra_train_leg(model, size, batch, steps, warmup, timeout=300):
     a reader of the headline line needs - value, ms_per_step, the step-level roofline and the dominant kernel family"""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--model', model, '--size', str(size), '--batch', str(batch), '--steps', str(steps),
-           '--warmup', str(warmup), '--no-cpu-baseline', '--no-davis', '--no-extra-legs']
+           '--warmup', str(warmup), '--full', '--no-cpu-baseline', '--no-davis', '--no-extra-legs']
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
         line = next((ln for ln in reversed(out.stdout.splitlines()) if ln.startswith('{')), None)
@@ -244,7 +284,7 @@ def davis_cpu_baseline(depth, threads):
                        f'{t_bb:.2f} s + propagation over 21 key frames {t_lp:.2f} s + post-processing {t_pp:.2f} s')
 
 
-def bench_davis(args, depth, dev, world, rank, steps=None, warmup=None):
+def bench_davis(args, depth, dev, world, rank, steps=None, warmup=None, dump_dir=None):
     """BASELINE.json configs[3]: DAVIS-2017 label propagation, synthetic 480x854 clip, the reference's test-time config"""
     import numpy as np
     import vfs_amd
@@ -297,10 +337,13 @@ def bench_davis(args, depth, dev, world, rank, steps=None, warmup=None):
         return float(tm.item()), out
     dt, out = timed()
     log(f'{K} propagated frames: {dt / K * 1e3:.3f} ms/frame')
+    if dump_dir and rank == 0:      # the caller's result: the label map of every frame of the clip
+        labels = torch.from_numpy(np.ascontiguousarray(out[0])).float()
+        dump_outputs(dump_dir, {'labels': sample_flat(labels), 'labels_last_frame': labels[-1]})
     # steady state: every frame from the 21st on propagates from the full key window (first + 20 preceding frames); the first 20
     # have fewer key frames (and cold thresholds).  steady = (whole clip - its first 21 frames) / the frames in between
     steady = None
-    if K > 24:
+    if args.full and K > 24:
         head = imgs[:, :, :, :21].contiguous()
         run(head)
         torch.cuda.synchronize()
@@ -323,7 +366,7 @@ def bench_davis(args, depth, dev, world, rank, steps=None, warmup=None):
                       'frames_per_clip': K + 1, 'parallelism': f'replicas x{world}'},
            'steady_state_ms_per_frame': steady,
            'labels_present': sorted(int(v) for v in np.unique(out[0][-1]))}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         eng.prof = []
         run(imgs)
         torch.cuda.synchronize()
@@ -372,7 +415,7 @@ def bench_davis(args, depth, dev, world, rank, steps=None, warmup=None):
                                    + ('fp32-input MFMA (157.3 TFLOP/s)' if args.precision == 'fp32' else 'bf16 MFMA (2.5 PFLOP/s)'))
         res['roofline']['families'] = [family(k) for k in sorted(agg, key=lambda k: -agg[k][1]) if k != kind and agg[k][1] / tot >= 0.03]
         res['roofline']['in_mask_pairs_per_key_frame'] = mask_pairs(60, 107, radius)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('timing the C oracle on one frame ...')
         import subprocess
         threads = min(os.cpu_count() or 1, 64)
@@ -398,6 +441,10 @@ def main():
     ap.add_argument('--batch', type=int, default=32, help='videos per GPU (configs: videos_per_gpu=32)')
     ap.add_argument('--workload', default='train', choices=['train', 'davis'])
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='davis workload: evaluation precision')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline leg, CPU baselines, DAVIS leg, ResNet-18 / 512^2 legs, DAVIS steady state, '
+                         'all-reduce timing (N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-davis', action='store_true', help='train workload: skip the DAVIS leg appended to the JSON line (N = 1 only)')
     ap.add_argument('--davis-frames', type=int, default=49, help='propagated frames of the appended DAVIS leg (49: the T = 50 clip of BASELINE configs[3] / SURVEY 8(d) Cfg 4)')
@@ -441,7 +488,7 @@ def main():
         Tape.slowest = {}
     depth = 18 if args.model == 'r18' else 50
     if args.workload == 'davis':
-        res = bench_davis(args, depth, dev, world, rank)
+        res = bench_davis(args, depth, dev, world, rank, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(res))
         if dist.is_initialized():
@@ -527,6 +574,18 @@ def main():
         log(f'--min-seconds {args.min_seconds}: timing {args.steps} steps')
     dt, out = timed(args.steps)
     log(f'{args.steps} timed steps: {dt / args.steps * 1e3:.2f} ms/step')
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step holds after it: the loss and its log values, the updated parameters and their gradients
+        # (the same seeded positions in both), the BatchNorm running statistics
+        lv = out['log_vars']
+        params = list(model.parameters())
+        flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+        bufs = torch.cat([b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()])
+        dump_outputs(args.dump_outputs, {'loss': out['loss'].detach().double().reshape(1),
+                                         'log_vars': torch.tensor([lv[k] for k in list(lv.keys())], dtype=torch.float64),
+                                         'params': sample_flat(flat_p), 'grads': sample_flat(flat_g), 'bn_buffers': sample_flat(bufs)})
+        del flat_p, flat_g, bufs
     if phases is not None:
         log('host ms per step in train_step / zero_grad / backward / opt.step / log read (timed steps): ' +
             ' / '.join(f'{p / args.steps * 1e3:.2f}' for p in phases))
@@ -541,7 +600,7 @@ def main():
     # every conv launch (events pre-created; only hipEventRecord is added)
     prof, dt_prof, prof_mode = None, None, None
     tape_mode = os.environ.get('VFS_TAPE', '1') == '1' and not (world == 1 and os.environ.get('VFS_GRAPHS', '0') == '1')
-    if not args.no_roofline and tape_mode:
+    if args.full and not args.no_roofline and tape_mode:
         # per-kernel durations of the schedule that was TIMED: the same command-tape replay (weight gradients on the side stream,
         # overlapping the dgrad chain) with every C-ABI launch bracketed by HIP events on the stream it is launched on
         # (vfs_amd/_lib.py Tape.timing); the one eager launch of the step (SGD) through the engine's own event pair
@@ -558,7 +617,7 @@ def main():
         prof_mode = (f'{args.steps} steps of the TIMED schedule (command-tape replay, two streams) right after the timed region, HIP events '
                      f'around every launch on its own stream: {dt_prof / args.steps * 1e3:.2f} ms/step with the events')
         log(f'{args.steps} replayed steps with per-kernel events: {dt_prof / args.steps * 1e3:.2f} ms/step')
-    elif not args.no_roofline:
+    elif args.full and not args.no_roofline:
         # (hipGraph / eager launch modes) one stream for this leg: with the weight-gradient kernels running concurrently on the side
         # stream a per-kernel event pair on torch's current stream would time two overlapping kernels, not one
         side_prev = os.environ.get('VFS_SIDE_STREAM')
@@ -593,29 +652,30 @@ def main():
                         else 'eager'),
     }
     if world > 1 or force_coll:
-        # how the N ranks talk: collective backend, how the SyncBN statistics travelled, what a gradient bucket costs
+        # how the N ranks talk: collective backend, how the SyncBN statistics travelled, (--full) what a gradient bucket costs
         bucket = int(model.grad_bucket_bytes)
         g = flat['grads']
-        n = min(g.numel(), max(1, bucket // 4))
-        times = []
-        for _ in range(5):
-            torch.cuda.synchronize()
-            dist.barrier()
-            t0 = time.perf_counter()
-            dist.all_reduce(g[:n])
-            torch.cuda.synchronize()
-            times.append((time.perf_counter() - t0) * 1e3)
-        g.zero_()
         res['distributed'] = {
             'ranks': world, 'devices_visible': torch.cuda.device_count(),
             'collective_backend': 'gloo, device tensors staged through the host (shared-device mode)' if shared_dev else 'nccl (RCCL)',
             'shared_device': bool(shared_dev),
             'syncbn_statistics': 'IPC-window exchange (csrc/p2p.hip)' if eng._p2p is not None else 'collective-library all-reduce',
             'syncbn_exchanges': int(eng._p2p.state[0].item()) if eng._p2p is not None else 0,
-            'gradient_bytes': int(g.numel()) * 4, 'gradient_bucket_bytes': bucket,
-            'allreduce_ms_per_bucket': {'bytes': n * 4, 'min': min(times), 'median': sorted(times)[len(times) // 2],
-                                        'note': 'blocking all-reduce of one bucket on an idle GPU, host-timed; in the step the buckets '
-                                                'overlap the backward chain'}}
+            'gradient_bytes': int(g.numel()) * 4, 'gradient_bucket_bytes': bucket}
+        if args.full:
+            n = min(g.numel(), max(1, bucket // 4))
+            times = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                dist.barrier()
+                t0 = time.perf_counter()
+                dist.all_reduce(g[:n])
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3)
+            g.zero_()
+            res['distributed']['allreduce_ms_per_bucket'] = {
+                'bytes': n * 4, 'min': min(times), 'median': sorted(times)[len(times) // 2],
+                'note': 'blocking all-reduce of one bucket on an idle GPU, host-timed; in the step the buckets overlap the backward chain'}
         if shared_dev:
             res['config']['parallelism'] = (f'dp{world}: {world} ranks SHARING one device (functional check of the N > 1 code path, '
                                             'not a scaling measurement)')
@@ -701,16 +761,16 @@ def main():
             res['step_roofline'].update({'traffic_bytes_per_step': st['hbm_bytes_per_step'], 'ideal_bytes_per_step': ideal,
                                          'traffic_ratio': st['hbm_bytes_per_step'] / ideal,
                                          'moved_TB/s': st['hbm_bytes_per_step'] / (dt / args.steps) / 1e12})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('timing the CPU oracle (bounded sample) ...')
         res['cpu_baseline'] = cpu_baseline_subprocess(depth, args.size, min(os.cpu_count() or 1, 64))
-    if world == 1 and not args.no_davis:
+    if world == 1 and args.full and not args.no_davis:
         # the second headline metric (BASELINE.json: "DAVIS J&F-Mean"; J&F itself needs the checkpoint + dataset, neither is on
         # the box): the label-propagation workload of configs[3] on the SAME model family, same process, after the train leg
         # - its own metric / value / roofline / cpu_baseline under the key "davis" of the same JSON line
         log(f'DAVIS leg: R{depth} {args.precision}, {args.davis_frames} propagated frames ...')
         res['davis'] = bench_davis(args, depth, dev, world, rank, steps=args.davis_frames, warmup=2)
-    if world == 1 and rank == 0 and not args.no_extra_legs and not args.no_davis and args.model == 'r50' and args.size == 256:
+    if world == 1 and rank == 0 and args.full and not args.no_extra_legs and not args.no_davis and args.model == 'r50' and args.size == 256:
         # BASELINE.json configs[1] and configs[4] beside the headline: after the timed region, each in its own
         # process, a few seconds of GPU time each
         del model, opt, imgs, batch

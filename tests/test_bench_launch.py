@@ -42,7 +42,7 @@ def test_world_size_mismatch_is_refused_cleanly():
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_its_own_ranks(gpu_backend):
     import torch
-    r = subprocess.run([sys.executable, BENCH, '--gpus', '2'] + SMALL, env=_env(VFS_P2P_SPIN=str(1 << 26)), capture_output=True, text=True,
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--full'] + SMALL, env=_env(VFS_P2P_SPIN=str(1 << 26)), capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -7,7 +7,7 @@ TAG=${TAG:-r04}
 for E in "$@"; do
   if [ "$E" = "-" ]; then EE=""; else EE="$E"; fi
   echo -n "[$E]: "
-  env $EE timeout 300 python bench.py --workload davis --model ${MODEL:-r50} --steps 20 --warmup 2 --no-cpu-baseline 2>&1 | python -c "
+  env $EE timeout 300 python bench.py --workload davis --model ${MODEL:-r50} --steps 20 --warmup 2 --full --no-cpu-baseline 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

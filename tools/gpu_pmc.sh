@@ -5,7 +5,7 @@
 # Round 6: the train step is profiled on its DEFAULT schedule (command-tape replay, weight gradients on the side stream) - rounds 1-5 forced
 # VFS_GRAPHS=0 VFS_SIDE_STREAM=0.  (rocprofv3 serialises the dispatches while it collects counters, so the bytes per kernel do not depend on it.)
 MODEL=${1:-r18}; WORK=${2:-train}; SIZE=${3:-256}
-if [ "$WORK" = davis ]; then BARGS="--workload davis --precision fp32 --steps 49 --warmup 0 --no-cpu-baseline --no-roofline"; OUT=davis_$MODEL
+if [ "$WORK" = davis ]; then BARGS="--workload davis --precision fp32 --steps 49 --warmup 0 --full --no-cpu-baseline --no-roofline"; OUT=davis_$MODEL
 else BARGS="--steps 3 --warmup 1 --size $SIZE --no-cpu-baseline --no-roofline --no-davis"; OUT=$MODEL; [ "$SIZE" != 256 ] && OUT=${MODEL}_$SIZE; fi
 mkdir -p gpurun_out && cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp

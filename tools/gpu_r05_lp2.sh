@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out
 TAG=${TAG:-r05_lp2}
 timeout 900 python -m pytest tests/test_labelprop2.py -m gpu -x -q > gpurun_out/${TAG}_pytest.txt 2>&1; grep -E "passed|failed" gpurun_out/${TAG}_pytest.txt | tail -2
-B="--model ${MODEL:-r50} --workload davis --precision fp32 --steps ${STEPS:-49} --warmup 2 --no-cpu-baseline --no-roofline"
+B="--model ${MODEL:-r50} --workload davis --precision fp32 --steps ${STEPS:-49} --warmup 2 --full --no-cpu-baseline --no-roofline"
 {
 for i in 1 2; do for E in "$@"; do
   if [ "$E" = "-" ]; then EE=""; else EE="$E"; fi

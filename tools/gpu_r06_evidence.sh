@@ -24,7 +24,8 @@ done
 for f in gpurun_out/${TAG}_bench_*_kernel_stats.csv gpurun_out/${TAG}_bench_*_kernel_stats.meta.json gpurun_out/${TAG}_davis_*_kernel_stats.*; do
   [ -f "$f" ] && cp "$f" profiles/$(basename "$f" | sed "s/^${TAG}_/r06_/")
 done
-timeout 900 python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.log
-tail -6 gpurun_out/${TAG}_bench_default.log; cut -c1-400 gpurun_out/${TAG}_bench_default.json
-VFS_BENCH_SHAPES=gpurun_out/${TAG}_per_launch_shapes_r50.txt timeout 600 python bench.py --model r50 --no-davis --no-cpu-baseline > /dev/null 2>&1
-python tools/gap_table.py gpurun_out/${TAG}_per_launch_shapes_r50.txt > gpurun_out/${TAG}_gap_table_r50.txt 2>&1; tail -12 gpurun_out/${TAG}_gap_table_r50.txt
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # the bench lines and the gap table
+timeout 900 python bench.py --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_default.log"
+tail -6 "$OUT/${TAG}_bench_default.log"; cut -c1-400 "$OUT/${TAG}_bench_default.json"
+VFS_BENCH_SHAPES="$OUT/${TAG}_per_launch_shapes_r50.txt" timeout 600 python bench.py --full --model r50 --no-davis --no-cpu-baseline > /dev/null 2>&1
+python tools/gap_table.py "$OUT/${TAG}_per_launch_shapes_r50.txt" > "$OUT/${TAG}_gap_table_r50.txt" 2>&1; tail -12 "$OUT/${TAG}_gap_table_r50.txt"

@@ -65,7 +65,7 @@ def main():
         kernels[name] = {'calls': v['calls'], 'fetch_bytes_per_launch': 2.0 * v['sum'] * 1024 / v['calls'],
                          'write_bytes_per_launch': w['sum'] * 1024 / max(w['calls'], 1)}
     classes = aggregate(kernels)
-    cmd = (f'bench.py --workload davis --model {model[6:]} --precision fp32 --steps 49 --warmup 0` (tools/gpu_pmc.sh {model[6:]} davis: '
+    cmd = (f'bench.py --workload davis --model {model[6:]} --precision fp32 --steps 49 --warmup 0 --full` (tools/gpu_pmc.sh {model[6:]} davis: '
            'every launch of the warm-up, the untimed and the timed pass over the 31-frame clip)' if model.startswith('davis_') else
            f'bench.py --model {model.split("_")[0]} --steps 3 --warmup 1' + (f' --size {model.split("_")[1]}' if '_' in model else '') + '` (tools/gpu_pmc.sh; default schedule: command-tape replay, weight gradients on the side stream)')
     out = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) on `' + cmd + '; '
