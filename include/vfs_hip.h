@@ -468,6 +468,27 @@ int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_
                               double mean_g, double mean_b, double std_r, double std_g, double std_b,
                               vfs_stream_t stream);
 
+/* the same chain with the photometric steps of the object-level configs between Flip and Normalize
+ * (r18_sgd_cos_100e_r2_1xNx8_k400.py / r50_sgd_cos_100e_r5_1xNx2_k400.py train_pipeline; pipelines/augmentations.py:1224-1320
+ * ColorJitter, RandomGrayScale, RandomGaussianBlur), applied to the uint8 frame after the resize and flip, in that order.
+ * photo int32 [F][8], one row per frame (pipeline order (b, v, t)):
+ *   [0] jitter ops in application order, op k in bits 4k..4k+3 (k = 0..3): 1 brightness, 2 contrast, 3 saturation,
+ *       4 hue, 0 none.  0 = ColorJitter not applied to the frame (its shuffled order, torchvision 0.7 get_params)
+ *   [1] [2] [3] brightness / contrast / saturation factors as fp32 bits: PIL ImageEnhance = Image.blend(degenerate,
+ *       img, factor) with degenerate 0 / the frame's mean PIL luma int(mean + 0.5) when contrast runs / the pixel's luma
+ *   [4] hue shift added to PIL's uint8 H, mod 256 (= np.uint8(hue_factor * 255) of torchvision 0.7 adjust_hue)
+ *   [5] grey flag: mmcv.rgb2gray = cv2 RGB2GRAY fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14, to 3 channels
+ *   [6] [7] blur ww, fw: PIL GaussianBlur(radius=sigma) box weights for a box radius < 1 (ww = 2^24 / (2*r + 1),
+ *       fw = (2^24 - ww) / 2); three horizontal then three vertical passes, edges replicated.  ww = 0: no blur
+ * Frames whose row is all zero come out bit-identical to vfs_crop_resize_flip_norm.  workspace: at least
+ * vfs_crop_resize_flip_photo_norm_workspace_bytes(B*V*T, Ho, Wo) bytes ([F] luma sums, [F][Ho][Wo] uint8 RGBX frames),
+ * workspace_bytes = what the caller allocated: a smaller buffer is REFUSED.  Other arguments as vfs_crop_resize_flip_norm. */
+int vfs_crop_resize_flip_photo_norm_workspace_bytes(int frames, int Ho, int Wo, long long* bytes);
+int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const uint8_t* flips, const int* photo,
+                                    void* workspace, long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V,
+                                    int T, int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g,
+                                    double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream);
+
 /* ---- SiamFC probe head (projects/siamfc-pytorch/siamfc/heads.py:16-23,51-58 `_fast_xcorr`): response maps
  * out[m][i][j] = scale * sum_{u,v,c} z[m % nz][u][v][c] * x[m][i+u][j+v][c]; z bf16 [nz][Hz][Wz][C], x bf16 [nx][H][W][C] (NHWC),
  * out fp32 [nx][H-Hz+1][W-Wz+1]; nx % nz == 0, C % 8 == 0.  Forward only (inference of a trained probe). */

@@ -796,4 +796,32 @@ int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_
   return vfs_crop_resize_flip_norm_launch(a, S(stream));
 }
 
+int vfs_crop_resize_flip_photo_norm_workspace_bytes(int frames, int Ho, int Wo, long long* bytes) {
+  if (!bytes || frames <= 0 || Ho <= 0 || Wo <= 0) return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm_workspace_bytes: bad argument");
+  *bytes = vfs_photo_workspace_bytes(frames, Ho, Wo);
+  return VFS_OK;
+}
+
+int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const uint8_t* flips, const int* photo, void* workspace,
+                                    long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T, int Hs, int Ws, int Ho,
+                                    int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r, double std_g,
+                                    double std_b, vfs_stream_t stream) {
+  if (!src || !boxes || !flips || !photo || (!imgs && !x4)) return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm: null buffer");
+  if (x4 && Wp < Wo) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_photo_norm: Wp < Wo");
+  if (B <= 0 || V <= 0 || T <= 0 || Ho <= 0 || Wo <= 0) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_photo_norm: empty batch");
+  long long need = 0;
+  if (vfs_crop_resize_flip_photo_norm_workspace_bytes(B * V * T, Ho, Wo, &need) != VFS_OK || !workspace || workspace_bytes < need)
+    return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm: workspace smaller than vfs_crop_resize_flip_photo_norm_workspace_bytes");
+  PhotoArgs pa;
+  PipelineArgs& a = pa.p;
+  a.src = src; a.boxes = boxes; a.flips = flips; a.imgs = imgs; a.x4 = x4;
+  a.B = B; a.V = V; a.T = T; a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo; a.Wp = Wp;
+  a.mean[0] = mean_r; a.mean[1] = mean_g; a.mean[2] = mean_b;
+  a.stdinv[0] = 1.0 / std_r; a.stdinv[1] = 1.0 / std_g; a.stdinv[2] = 1.0 / std_b;
+  pa.photo = photo;
+  pa.sums = (unsigned long long*)workspace;
+  pa.pix = (uint32_t*)((char*)workspace + (size_t)B * V * T * 8);
+  return vfs_crop_resize_flip_photo_norm_launch(pa, S(stream));
+}
+
 }  // extern "C"

@@ -88,3 +88,280 @@ int vfs_crop_resize_flip_norm_launch(const PipelineArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(crop_resize_flip_norm_kernel, dim3((int)blocks), dim3(256), 0, s, a);
   return vfs_check_launch("crop_resize_flip_norm");
 }
+
+// ---- photometric steps: ColorJitter / RandomGrayScale / RandomGaussianBlur (augmentations.py:1224-1320) between Flip
+// and Normalize, for the object-level configs (r18_sgd_cos_100e_r2_1xNx8_k400.py, r50_sgd_cos_100e_r5_1xNx2_k400.py).
+// They act on the uint8 224x224 frame after the resize, through PIL (torchvision 0.7 ColorJitter: ImageEnhance blend,
+// HSV round trip), mmcv.rgb2gray (cv2.cvtColor) and PIL's GaussianBlur (extended box blur, three passes per axis).
+// Two launches: A = crop + resize + flip + the jitter ops that precede contrast in the frame's shuffled order, uint8
+// RGBX into the workspace, plus the frame's sum of PIL luma when contrast follows (contrast blends towards the mean of
+// the frame AS IT STANDS then); B = one 64x16 tile + 3-pixel halo in LDS: contrast, the remaining jitter ops, grey,
+// the six box-blur passes, normalise, store.  Integer sums: bit-identical whatever the order of the atomics.
+
+#define PHOTO_TW 64
+#define PHOTO_TH 16
+#define PHOTO_HALO 3
+#define PHOTO_LW (PHOTO_TW + 2 * PHOTO_HALO)
+#define PHOTO_LH (PHOTO_TH + 2 * PHOTO_HALO)
+
+enum { PH_BRIGHT = 1, PH_CONTRAST = 2, PH_SAT = 3, PH_HUE = 4 };
+
+struct PhotoFrame {
+  int ops[4];          // jitter ops in application order (0 = none)
+  int split;           // index of contrast in ops (4 if absent): ops[0, split) run in launch A, ops(split, 4) in launch B
+  float fac[4];        // blend factors by op code - 1 (brightness, contrast, saturation)
+  int hue, gray;
+  uint32_t ww, fw;     // box-blur weights, ww == 0: no blur
+};
+
+__device__ __forceinline__ PhotoFrame load_photo(const int* p) {
+  PhotoFrame r;
+  const uint32_t code = (uint32_t)p[0];
+  r.split = 4;
+  for (int k = 0; k < 4; ++k) {
+    const int op = (int)((code >> (4 * k)) & 15u);
+    r.ops[k] = op <= PH_HUE ? op : 0;        // unknown codes are no-ops
+    if (r.ops[k] == PH_CONTRAST && r.split == 4) r.split = k;
+  }
+  r.fac[0] = __builtin_bit_cast(float, p[1]); r.fac[1] = __builtin_bit_cast(float, p[2]); r.fac[2] = __builtin_bit_cast(float, p[3]); r.fac[3] = 0.f;
+  r.hue = p[4] & 255;
+  r.gray = p[5] != 0;
+  // host weights are clamped so that x*ww + 2*255*fw + 2^23 stays below 2^32 (ww + 2*fw <= 2^24)
+  r.ww = min((uint32_t)p[6], 1u << 24);
+  r.fw = min((uint32_t)p[7], ((1u << 24) - r.ww) / 2);
+  return r;
+}
+
+__device__ __forceinline__ int pil_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+
+// ImagingBlend(degenerate, image, alpha): temp = d + alpha*(x - d) in fp32 with the multiply and the add rounded apart
+__device__ __forceinline__ int pil_blend(int x, int d, float alpha) {
+#pragma clang fp contract(off)
+  const float t = (float)d + alpha * (float)(x - d);
+  if (!(t > 0.f)) return 0;
+  if (t >= 255.f) return 255;
+  return (int)t;
+}
+
+// Pillow Convert.c rgb2hsv_row + hue shift + hsv2rgb (the HSV round trip of torchvision 0.7 adjust_hue)
+__device__ __forceinline__ void pil_hue(int& r, int& g, int& b, int shift) {
+#pragma clang fp contract(off)
+  const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+  int uh = 0, us = 0;
+  if (maxc != minc) {
+    const float cr = (float)(maxc - minc);
+    const float s = cr / (float)maxc;
+    const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
+    float h;
+    if (r == maxc) h = bc - gc;
+    else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
+    else h = (float)(4.0 + (double)gc - (double)rc);
+    h = (float)fmod((double)h / 6.0 + 1.0, 1.0);
+    uh = min(max((int)((double)h * 255.0), 0), 255);
+    us = min(max((int)((double)s * 255.0), 0), 255);
+  }
+  const int hh = (uh + shift) & 255, v = maxc;
+  if (us == 0) { r = g = b = v; return; }
+  const double hf = (double)(float)hh * 6.0 / 255.0;
+  const int i = (int)floor(hf);
+  const float f = (float)(hf - (double)(float)i);
+  const float fs = (float)((double)(float)us / 255.0);
+  const float fsf = fs * f;                                   // fp32 product in Pillow's q
+  const int p = min(max((int)round((double)v * (1.0 - (double)fs)), 0), 255);
+  const int q = min(max((int)round((double)v * (1.0 - (double)fsf)), 0), 255);
+  const int t = min(max((int)round((double)v * (1.0 - (double)fs * (1.0 - (double)f))), 0), 255);
+  switch (i % 6) {
+    case 0: r = v; g = t; b = p; break;
+    case 1: r = q; g = v; b = p; break;
+    case 2: r = p; g = v; b = t; break;
+    case 3: r = p; g = q; b = v; break;
+    case 4: r = t; g = p; b = v; break;
+    default: r = v; g = p; b = q; break;
+  }
+}
+
+__device__ __forceinline__ void jitter_op(int op, const PhotoFrame& ph, int cmean, int& r, int& g, int& b) {
+  if (op == PH_BRIGHT) {
+    r = pil_blend(r, 0, ph.fac[0]); g = pil_blend(g, 0, ph.fac[0]); b = pil_blend(b, 0, ph.fac[0]);
+  } else if (op == PH_CONTRAST) {
+    r = pil_blend(r, cmean, ph.fac[1]); g = pil_blend(g, cmean, ph.fac[1]); b = pil_blend(b, cmean, ph.fac[1]);
+  } else if (op == PH_SAT) {
+    const int l = pil_luma(r, g, b);
+    r = pil_blend(r, l, ph.fac[2]); g = pil_blend(g, l, ph.fac[2]); b = pil_blend(b, l, ph.fac[2]);
+  } else if (op == PH_HUE) {
+    pil_hue(r, g, b, ph.hue);
+  }
+}
+
+__device__ __forceinline__ uint32_t pack_rgb(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
+
+// crop + resize + flip of one output pixel: the arithmetic of crop_resize_flip_norm_kernel (uint8 per channel)
+__device__ __forceinline__ void resize_pixel(const PipelineArgs& a, int f, int x, int y, int u[3]) {
+  const int left = min(max(a.boxes[4 * f], 0), a.Ws - 1), top = min(max(a.boxes[4 * f + 1], 0), a.Hs - 1);
+  const int right = min(max(a.boxes[4 * f + 2], left + 1), a.Ws), bottom = min(max(a.boxes[4 * f + 3], top + 1), a.Hs);
+  const int cw = right - left, ch = bottom - top;
+  const int xr = a.flips[f] ? a.Wo - 1 - x : x;
+  int sx, sx1, ax0, ax1, sy, sy1, by0, by1;
+  cv_linear_coef<true>(xr, cw, a.Wo, sx, sx1, ax0, ax1);
+  cv_linear_coef<false>(y, ch, a.Ho, sy, sy1, by0, by1);
+  const uint8_t* img = a.src + (size_t)f * a.Hs * a.Ws * 3;
+  const uint8_t* p00 = img + ((size_t)(top + sy) * a.Ws + left + sx) * 3;
+  const uint8_t* p01 = img + ((size_t)(top + sy) * a.Ws + left + sx1) * 3;
+  const uint8_t* p10 = img + ((size_t)(top + sy1) * a.Ws + left + sx) * 3;
+  const uint8_t* p11 = img + ((size_t)(top + sy1) * a.Ws + left + sx1) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int h0 = p00[c] * ax0 + p01[c] * ax1;
+    const int h1 = p10[c] * ax0 + p11[c] * ax1;
+    u[c] = min((((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2, 255);
+  }
+}
+
+// mmcv.imnormalize_ + FormatShape of one uint8 pixel, both outputs laid out as crop_resize_flip_norm_kernel writes them
+__device__ __forceinline__ void store_normalized(const PipelineArgs& a, int f, int x, int y, uint32_t px) {
+  const int t = f % a.T, v = (f / a.T) % a.V, b = f / (a.T * a.V);
+  float o[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int u = (int)((px >> (8 * c)) & 255u);
+    const float d = (float)((double)u - a.mean[c]);
+    o[c] = (float)((double)d * a.stdinv[c]);
+  }
+  if (a.imgs) {
+    const size_t plane = (size_t)a.T * a.Ho * a.Wo;
+    float* q = a.imgs + (((size_t)b * a.V + v) * 3) * plane + ((size_t)t * a.Ho + y) * a.Wo + x;
+    q[0] = o[0]; q[plane] = o[1]; q[2 * plane] = o[2];
+  }
+  if (a.x4) {
+    const size_t fr = ((size_t)v * a.B + b) * a.T + t;
+    u32x2 pk;
+    pk.x = pack2bf(o[0], o[1]);
+    pk.y = pack2bf(o[2], 0.f);
+    st8(a.x4 + ((fr * a.Ho + y) * a.Wp + x) * 4, pk);
+    if (a.Wp > a.Wo && x == a.Wo - 1) st8(a.x4 + ((fr * a.Ho + y) * a.Wp + a.Wo) * 4, (u32x2){0u, 0u});
+  }
+}
+
+// launch A: grid (pixel blocks, frames)
+__global__ __launch_bounds__(256) void photo_resize_kernel(PhotoArgs pa) {
+  const PipelineArgs& a = pa.p;
+  const int f = blockIdx.y;
+  const PhotoFrame ph = load_photo(pa.photo + 8 * f);
+  const long long hw = (long long)a.Ho * a.Wo;
+  uint32_t* out = pa.pix + (size_t)f * hw;
+  uint32_t lsum = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < hw; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % a.Wo), y = (int)(i / a.Wo);
+    int u[3];
+    resize_pixel(a, f, x, y, u);
+    for (int k = 0; k < ph.split; ++k) jitter_op(ph.ops[k], ph, 0, u[0], u[1], u[2]);
+    out[i] = pack_rgb(u[0], u[1], u[2]);
+    lsum += (uint32_t)pil_luma(u[0], u[1], u[2]);
+  }
+  if (ph.split < 4) {      // block-uniform: contrast follows, its mean needs the frame's luma sum
+    __shared__ uint32_t red[256];
+    red[threadIdx.x] = lsum;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(pa.sums + f, (unsigned long long)red[0]);
+  }
+}
+
+__device__ __forceinline__ uint32_t box_pass(uint32_t c, uint32_t lo, uint32_t hi, uint32_t ww, uint32_t fw) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const uint32_t x = (c >> (8 * k)) & 255u, l = (lo >> (8 * k)) & 255u, h = (hi >> (8 * k)) & 255u;
+    o |= ((x * ww + (l + h) * fw + (1u << 23)) >> 24) << (8 * k);
+  }
+  return o;
+}
+
+// the per-pixel tail of launch B: contrast and the jitter ops after it, then grey
+__device__ __forceinline__ uint32_t photo_post(uint32_t px, const PhotoFrame& ph, int cmean) {
+  int r = px & 255, g = (px >> 8) & 255, b = (px >> 16) & 255;
+  for (int k = ph.split; k < 4; ++k) jitter_op(ph.ops[k], ph, cmean, r, g, b);
+  if (ph.gray) r = g = b = (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;     // cv2 RGB2GRAY, 8-bit fixed point
+  return pack_rgb(r, g, b);
+}
+
+// launch B: grid (column tiles, row tiles, frames)
+__global__ __launch_bounds__(256) void photo_finish_kernel(PhotoArgs pa) {
+  const PipelineArgs& a = pa.p;
+  const int f = blockIdx.z, x0 = blockIdx.x * PHOTO_TW, y0 = blockIdx.y * PHOTO_TH;
+  const PhotoFrame ph = load_photo(pa.photo + 8 * f);
+  const uint32_t* in = pa.pix + (size_t)f * a.Ho * a.Wo;
+  int cmean = 0;
+  if (ph.split < 4) cmean = (int)((double)pa.sums[f] / ((double)a.Ho * (double)a.Wo) + 0.5);     // ImageStat mean, int(m + 0.5)
+  if (ph.ww == 0) {     // no blur: pixel by pixel
+    for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+      const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+      if (x < a.Wo && y < a.Ho) store_normalized(a, f, x, y, photo_post(in[(size_t)y * a.Wo + x], ph, cmean));
+    }
+    return;
+  }
+  // blur: PIL's three horizontal then three vertical box passes, uint8 after each, edge pixels of the FRAME replicated
+  __shared__ uint32_t buf[2][PHOTO_LH * PHOTO_LW];
+  const int gx0 = x0 - PHOTO_HALO, gy0 = y0 - PHOTO_HALO;
+  for (int i = threadIdx.x; i < PHOTO_LH * PHOTO_LW; i += 256) {
+    const int gx = gx0 + i % PHOTO_LW, gy = gy0 + i / PHOTO_LW;
+    if (gx >= 0 && gx < a.Wo && gy >= 0 && gy < a.Ho) buf[0][i] = photo_post(in[(size_t)gy * a.Wo + gx], ph, cmean);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int k = 1; k <= 3; ++k) {       // pass k is valid on local columns [k, LW - k): its neighbours were valid in pass k-1
+    const int w = PHOTO_LW - 2 * k;
+    for (int i = threadIdx.x; i < PHOTO_LH * w; i += 256) {
+      const int lx = k + i % w, ly = i / w;
+      const int gx = gx0 + lx, gy = gy0 + ly;
+      if (gx < 0 || gx >= a.Wo || gy < 0 || gy >= a.Ho) continue;
+      const int xl = max(gx - 1, 0) - gx0, xh = min(gx + 1, a.Wo - 1) - gx0;
+      const uint32_t* s = buf[cur] + ly * PHOTO_LW;
+      buf[cur ^ 1][ly * PHOTO_LW + lx] = box_pass(s[lx], s[xl], s[xh], ph.ww, ph.fw);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  for (int k = 1; k <= 3; ++k) {       // rows [k, LH - k) of the columns [3, LW - 3) the tile keeps
+    const int h = PHOTO_LH - 2 * k;
+    for (int i = threadIdx.x; i < h * PHOTO_TW; i += 256) {
+      const int lx = PHOTO_HALO + i % PHOTO_TW, ly = k + i / PHOTO_TW;
+      const int gx = gx0 + lx, gy = gy0 + ly;
+      if (gx >= a.Wo || gy < 0 || gy >= a.Ho) continue;
+      const int yl = max(gy - 1, 0) - gy0, yh = min(gy + 1, a.Ho - 1) - gy0;
+      const uint32_t* s = buf[cur];
+      buf[cur ^ 1][ly * PHOTO_LW + lx] = box_pass(s[ly * PHOTO_LW + lx], s[yl * PHOTO_LW + lx], s[yh * PHOTO_LW + lx], ph.ww, ph.fw);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+    const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+    if (x < a.Wo && y < a.Ho) store_normalized(a, f, x, y, buf[cur][(i / PHOTO_TW + PHOTO_HALO) * PHOTO_LW + i % PHOTO_TW + PHOTO_HALO]);
+  }
+}
+
+long long vfs_photo_workspace_bytes(int F, int Ho, int Wo) {
+  return (long long)F * 8 + (long long)F * Ho * Wo * 4;
+}
+
+int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& pa, hipStream_t s) {
+  const PipelineArgs& a = pa.p;
+  if (a.B <= 0 || a.V <= 0 || a.T <= 0 || a.Ho <= 0 || a.Wo <= 0) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: empty batch");
+  const long long F = (long long)a.B * a.V * a.T;
+  if (F > 65535) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: at most 65535 frames per launch");
+  if (hipMemsetAsync(pa.sums, 0, (size_t)F * 8, s) != hipSuccess) return vfs_set_error(VFS_ERR_LAUNCH, "photo pipeline: memset");
+  const long long hw = (long long)a.Ho * a.Wo;
+  long long bx = (hw + 255) / 256;
+  if (bx > 4096) bx = 4096;
+  hipLaunchKernelGGL(photo_resize_kernel, dim3((int)bx, (int)F), dim3(256), 0, s, pa);
+  int rc = vfs_check_launch("photo_resize");
+  if (rc != VFS_OK) return rc;
+  const int tx = (a.Wo + PHOTO_TW - 1) / PHOTO_TW, ty = (a.Ho + PHOTO_TH - 1) / PHOTO_TH;
+  if (ty > 65535) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: output too tall");
+  hipLaunchKernelGGL(photo_finish_kernel, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
+  return vfs_check_launch("photo_finish");
+}

@@ -370,4 +370,12 @@ struct PipelineArgs {
   double mean[3], stdinv[3];
 };
 int vfs_crop_resize_flip_norm_launch(const PipelineArgs& a, hipStream_t s);
+struct PhotoArgs {
+  PipelineArgs p;        // crop / resize / flip / normalise exactly as vfs_crop_resize_flip_norm
+  const int* photo;      // [F][8] photometric parameters (vfs_hip.h vfs_crop_resize_flip_photo_norm)
+  unsigned long long* sums;   // workspace: [F] luma sums of the frames whose contrast follows launch A's ops
+  uint32_t* pix;         // workspace: [F][Ho][Wo] uint8 RGB(X) after launch A
+};
+long long vfs_photo_workspace_bytes(int F, int Ho, int Wo);
+int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& a, hipStream_t s);
 

@@ -4,9 +4,15 @@ mmaction/datasets/pipelines/augmentations.py, formating.py:222-309) applied to d
 are already on the device, by ONE kernel (`vfs_crop_resize_flip_norm`, csrc/pipeline.hip).  Decoding
 (DecordInit / SampleFrames / DecordDecode) stays outside.
 
+The object-level configs (r18_sgd_cos_100e_r2_1xNx8_k400.py, r50_sgd_cos_100e_r5_1xNx2_k400.py) add ColorJitter,
+RandomGrayScale and RandomGaussianBlur between Flip and Normalize (augmentations.py:1224-1320); with any of
+them present the chain runs as two launches (`vfs_crop_resize_flip_photo_norm`) that apply them to the uint8
+resized frame, where the reference's PIL / cv2 calls act.
+
 The random decisions are drawn on the host with the reference's own rules and RNG streams
 (`np.random` for the candidates / flips, `random.randint` for the offsets): seeding both reproduces the
 reference's boxes and flips (tests/golden/pipeline_decisions.npz)."""
+import math
 import random
 
 import numpy as np
@@ -57,6 +63,74 @@ def clips_from_pipeline(pipeline_cfg):
     return num_clips, clip_len
 
 
+PHOTOMETRIC = ('ColorJitter', 'RandomGrayScale', 'RandomGaussianBlur')
+
+
+def _jitter_range(value, center=1, bound=(0, float('inf')), clip_first_on_zero=True):
+    """torchvision 0.7 ColorJitter._check_input; None = component disabled"""
+    if isinstance(value, (int, float)):
+        if value < 0:
+            raise ValueError('ColorJitter: a single value must be non-negative')
+        value = [center - value, center + value]
+        if clip_first_on_zero:
+            value[0] = max(value[0], 0.0)
+        if not bound[0] <= value[0] <= value[1] <= bound[1]:
+            raise ValueError(f'ColorJitter: {value} out of {bound}')
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        if not bound[0] <= value[0] <= value[1] <= bound[1]:
+            raise ValueError(f'ColorJitter: {value} out of {bound}')
+        value = list(value)
+    else:
+        raise TypeError('ColorJitter: a number or a (min, max) pair')
+    return None if value[0] == value[1] == center else value
+
+
+def _jitter_params(ranges):
+    """torchvision 0.7 ColorJitter.get_params: random.uniform per enabled component, then random.shuffle of the ops"""
+    factors, ops = [math.nan] * 4, []
+    for k, r in enumerate(ranges):
+        if r is not None:
+            factors[k] = random.uniform(r[0], r[1])
+            ops.append(k + 1)
+    random.shuffle(ops)
+    return factors, ops
+
+
+def blur_weights(sigma):
+    """PIL GaussianBlur(radius=sigma): _gaussian_blur_radius (3 passes, fp32 as Pillow computes it) -> the box weights
+    (ww, fw) of ImagingHorizontalBoxBlur.  The kernel runs box radii below 1 only (sigma_range (0.1, 0.2) gives ~0.1)."""
+    f32 = np.float32
+    s2 = f32(f32(f32(sigma) * f32(sigma)) / f32(3))
+    L = f32(math.sqrt(12.0 * float(s2) + 1.0))
+    l = f32(math.floor((float(L) - 1.0) / 2.0))
+    a = f32(f32(f32(2) * l + f32(1)) * f32(f32(l * f32(l + f32(1))) - f32(f32(3) * s2)))
+    a = f32(a / f32(f32(6) * f32(s2 - f32(f32(l + f32(1)) * f32(l + f32(1))))))
+    rad = f32(l + a)
+    if not 0 <= rad < 1:
+        raise NotImplementedError(f'RandomGaussianBlur: sigma {sigma} gives a box radius of {float(rad)} (only < 1 runs on the GPU)')
+    ww = int(f32(f32(1 << 24) / f32(rad * f32(2) + f32(1))))
+    return ww, ((1 << 24) - ww) // 2
+
+
+def pack_photometric(photo):
+    """per-frame photometric decisions (GpuTrainPipeline.sample) -> int32 [F][8] parameter rows of
+    vfs_crop_resize_flip_photo_norm (layout in include/vfs_hip.h)"""
+    F = len(photo['jitter'])
+    rows = np.zeros((F, 8), np.int32)
+    for i in range(F):
+        if photo['jitter'][i]:
+            rows[i, 0] = sum(int(op) << (4 * k) for k, op in enumerate(photo['order'][i]))
+            for k in range(3):
+                if not math.isnan(photo['factors'][i][k]):
+                    rows[i, 1 + k] = np.float32(photo['factors'][i][k]).view(np.int32)
+            if not math.isnan(photo['factors'][i][3]):
+                rows[i, 4] = int(math.trunc(photo['factors'][i][3] * 255)) % 256    # np.uint8(h * 255) of numpy 1.x: wraps
+        rows[i, 5] = int(photo['gray'][i])
+        if photo['blur'][i]:
+            rows[i, 6], rows[i, 7] = blur_weights(float(photo['sigma'][i]))
+    return rows
+
+
 class GpuTrainPipeline:
     """Built from the reference's `train_pipeline` list; `__call__(frames)` with frames uint8
     [B][num_clips*clip_len][Hs][Ws][3] on the GPU returns dict(imgs=fp32 [B][num_clips][3][clip_len][H][W])
@@ -68,6 +142,18 @@ class GpuTrainPipeline:
         self.num_clips, self.clip_len = int(num_clips), int(clip_len)
         self.crop = self.flip = None
         self.out_hw, self.mean, self.std = None, None, None
+        self.jitter = self.gray = self.blur = None
+        self._ws = None
+        types = [step['type'] for step in pipeline_cfg]
+        photo_at = [i for i, t in enumerate(types) if t in PHOTOMETRIC]
+        if photo_at:     # only on the uint8 resized frame: after Resize, before Normalize, each once, in this order
+            resize = types.index('Resize') if 'Resize' in types else len(types)
+            norm = types.index('Normalize') if 'Normalize' in types else -1
+            names = [types[i] for i in photo_at]
+            if (not all(resize < i < norm for i in photo_at) or len(set(names)) != len(names)
+                    or names != sorted(names, key=PHOTOMETRIC.index)):
+                raise NotImplementedError(f'{", ".join(names)}: the GPU pipeline runs ColorJitter, RandomGrayScale, '
+                                          'RandomGaussianBlur only between Resize and Normalize, each once, in that order')
         for step in pipeline_cfg:
             t = step['type']
             if t == 'RandomResizedCrop':
@@ -91,13 +177,31 @@ class GpuTrainPipeline:
             elif t == 'FormatShape':
                 if step.get('input_format') != 'NCTHW':
                     raise NotImplementedError(f"FormatShape {step.get('input_format')}")
-            elif t in ('ColorJitter', 'RandomGrayScale', 'RandomGaussianBlur'):
-                raise NotImplementedError(f'{t} is not on the GPU pipeline (commented out in the reference configs)')
+            elif t == 'ColorJitter':      # augmentations.py:1290-1320 (p default 0.5) over torchvision 0.7 ColorJitter
+                ranges = [_jitter_range(step.get('brightness', 0)), _jitter_range(step.get('contrast', 0)),
+                          _jitter_range(step.get('saturation', 0)),
+                          _jitter_range(step.get('hue', 0), center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)]
+                self.jitter = dict(ranges=ranges, p=float(step.get('p', 0.5)), same_on_clip=step.get('same_on_clip', True),
+                                   same_across_clip=step.get('same_across_clip', True))
+            elif t == 'RandomGrayScale':    # augmentations.py:1258-1281
+                self.gray = dict(p=float(step.get('p', 0.5)), same_on_clip=step.get('same_on_clip', True),
+                                 same_across_clip=step.get('same_across_clip', True))
+            elif t == 'RandomGaussianBlur':   # augmentations.py:1224-1255
+                sr = tuple(float(v) for v in step.get('sigma_range', (0.1, 0.2)))
+                for sg in sr:
+                    blur_weights(sg)      # NotImplementedError for a box radius >= 1
+                self.blur = dict(sigma_range=sr, p=float(step.get('p', 0.5)), same_on_clip=step.get('same_on_clip', True),
+                                 same_across_clip=step.get('same_across_clip', True))
         if self.out_hw is None or self.mean is None:
             raise ValueError('pipeline needs Resize(scale=..., keep_ratio=False) and Normalize')
 
+    @property
+    def photometric(self):
+        return self.jitter is not None or self.gray is not None or self.blur is not None
+
     def sample(self, num_frames, img_shape):
-        """boxes int32 [F][4], flips uint8 [F] for ONE sample, consuming the RNGs like the reference"""
+        """boxes int32 [F][4], flips uint8 [F] for ONE sample, consuming the RNGs like the reference; with photometric
+        steps in the pipeline a third item, their per-frame decisions (sample_photometric)"""
         Hs, Ws = img_shape
         if self.crop is None:
             boxes = np.tile(np.asarray([[0, 0, Ws, Hs]], np.int32), (num_frames, 1))
@@ -121,16 +225,68 @@ class GpuTrainPipeline:
                     flip = np.random.rand() < f['flip_ratio']
                 vals.append(flip)
             flips = np.asarray(vals, np.uint8)
-        return boxes, flips
+        if not self.photometric:
+            return boxes, flips
+        return boxes, flips, self.sample_photometric(num_frames)
 
-    def __call__(self, frames, boxes=None, flips=None, want_x4=False, want_imgs=True):
+    def sample_photometric(self, num_frames):
+        """ColorJitter, RandomGrayScale, RandomGaussianBlur decisions of ONE sample's frames, drawn as their __call__s
+        do (augmentations.py:1224-1320): apply flag (np.random) and parameters (random) once before the frame loop, again
+        for every frame that does not share.  -> dict jitter uint8 [F], factors float64 [F][4] (brightness, contrast,
+        saturation, hue; nan = disabled), order int8 [F][4] (op codes in application order, 0 = none), gray uint8 [F],
+        blur uint8 [F], sigma float64 [F]"""
+        F = num_frames
+        out = dict(jitter=np.zeros(F, np.uint8), factors=np.full((F, 4), np.nan), order=np.zeros((F, 4), np.int8),
+                   gray=np.zeros(F, np.uint8), blur=np.zeros(F, np.uint8), sigma=np.zeros(F))
+        if self.jitter is not None:
+            j = self.jitter
+            apply = np.random.rand() < j['p']
+            factors, ops = _jitter_params(j['ranges'])
+            for i in range(F):
+                if _new_for_frame(i, self.clip_len, j['same_on_clip'], j['same_across_clip']):
+                    apply = np.random.rand() < j['p']
+                    factors, ops = _jitter_params(j['ranges'])
+                out['jitter'][i], out['factors'][i] = apply, factors
+                out['order'][i, :len(ops)] = ops
+        if self.gray is not None:
+            g = self.gray
+            apply = np.random.rand() < g['p']
+            for i in range(F):
+                if _new_for_frame(i, self.clip_len, g['same_on_clip'], g['same_across_clip']):
+                    apply = np.random.rand() < g['p']
+                out['gray'][i] = apply
+        if self.blur is not None:
+            b = self.blur
+            apply = np.random.rand() < b['p']
+            sigma = random.uniform(*b['sigma_range'])
+            for i in range(F):
+                if _new_for_frame(i, self.clip_len, b['same_on_clip'], b['same_across_clip']):
+                    apply = np.random.rand() < b['p']
+                    sigma = random.uniform(*b['sigma_range'])
+                out['blur'][i], out['sigma'][i] = apply, sigma
+        return out
+
+    def _workspace(self, frames, H, W, dev):
+        """the photometric launches' workspace (luma sums + uint8 frames), kept and grown across calls"""
+        nbytes = torch.zeros(1, dtype=torch.int64)
+        get_lib().crop_resize_flip_photo_norm_workspace_bytes(frames, H, W, nbytes)
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < int(nbytes.item()):
+            self._ws = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
+        return self._ws
+
+    def __call__(self, frames, boxes=None, flips=None, want_x4=False, want_imgs=True, photo=None):
+        """boxes / flips / photo: decisions to use instead of sampling them (tests); photo = sample_photometric's dict
+        (concatenated over the samples) or packed int32 [B*F][8] rows; with explicit boxes and no photo, no frame gets a
+        photometric step"""
         assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3, frames.shape
         B, F, Hs, Ws, _ = frames.shape
         assert F == self.num_clips * self.clip_len
         dev = frames.device
-        if boxes is None:      # sample by sample: crop boxes of all its frames, then its flips (pipeline order)
-            bs, fs = zip(*[self.sample(F, (Hs, Ws)) for _ in range(B)])
-            boxes, flips = np.concatenate(bs), np.concatenate(fs)
+        if boxes is None:      # sample by sample: crop boxes of all its frames, then its flips, then the photometric steps (pipeline order)
+            draws = [self.sample(F, (Hs, Ws)) for _ in range(B)]
+            boxes, flips = np.concatenate([d[0] for d in draws]), np.concatenate([d[1] for d in draws])
+            if self.photometric:
+                photo = {k: np.concatenate([d[2][k] for d in draws]) for k in draws[0][2]}
         H, W = self.out_hw
         Wp = W + (W & 1)
         imgs = torch.empty(B, self.num_clips, 3, self.clip_len, H, W, device=dev) if want_imgs else None
@@ -138,9 +294,24 @@ class GpuTrainPipeline:
         bt = torch.as_tensor(np.ascontiguousarray(boxes, dtype=np.int32)).to(dev)
         ft = torch.as_tensor(np.ascontiguousarray(flips, dtype=np.uint8)).to(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else None
-        get_lib().crop_resize_flip_norm(frames.contiguous(), bt, ft, imgs, x4, B, self.num_clips, self.clip_len, Hs, Ws, H, W,
-                                        Wp, *self.mean, *self.std, stream)
         out = dict(boxes=boxes, flips=flips)
+        if self.photometric:
+            if photo is None:
+                rows = np.zeros((B * F, 8), np.int32)
+            elif isinstance(photo, dict):
+                rows = pack_photometric(photo)
+                out['photo'] = photo
+            else:
+                rows = np.ascontiguousarray(photo, dtype=np.int32)
+            assert rows.shape == (B * F, 8), rows.shape
+            out['photo_rows'] = rows
+            pt = torch.as_tensor(rows).to(dev)
+            ws = self._workspace(B * F, H, W, dev)
+            get_lib().crop_resize_flip_photo_norm(frames.contiguous(), bt, ft, pt, ws, ws.numel(), imgs, x4, B, self.num_clips,
+                                                  self.clip_len, Hs, Ws, H, W, Wp, *self.mean, *self.std, stream)
+        else:
+            get_lib().crop_resize_flip_norm(frames.contiguous(), bt, ft, imgs, x4, B, self.num_clips, self.clip_len, Hs, Ws, H,
+                                            W, Wp, *self.mean, *self.std, stream)
         if want_imgs:
             out['imgs'] = imgs
         if want_x4:
