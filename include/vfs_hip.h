@@ -457,6 +457,33 @@ int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, 
 int vfs_davis_counts(const uint8_t* pred, const uint8_t* gt, int* counts, void* scratch, int T, int H, int W,
                      int nobj, int radius, int use_void, vfs_stream_t stream);
 
+/* ---- JHMDB pose (PCK) and VIP parts (mIoU): the other two label-propagation benchmarks -------------
+ * vfs_heatmap_topk: JHMDBDataset.img2coord (datasets/jhmdb_dataset.py:118-136) without the np.argsort over every
+ * full-resolution map.  maps fp32 [N][H*W] (N = frames x key points of the tracker's [T][K][H][W]; 4-byte aligned,
+ * any H*W <= 2^28), topk 1..8 (the reference: 5), H*W >= topk (else VFS_ERR_SHAPE).  Per map: vals fp32 [N][topk]
+ * and idx int32 [N][topk] = the topk largest values and their flat indices in ASCENDING rank order (what
+ * argsort(...)[-topk:] yields); larger value ranks higher, among equal values the LOWER flat index ranks higher
+ * (argsort leaves ties open); minv fp32 [N] = the map's minimum; flags int32 [N]: bit 0 = every element is zero,
+ * bit 1 = the map holds a NaN, bit 2 = the map holds a -inf (elements equal to -inf never rank, so a map with fewer than
+ * topk elements above -inf has no defined top-k).  Both are bad data, not a bad call: VFS_OK, and vals / idx of that map
+ * mean nothing (minv is the minimum over the non-NaN elements). */
+int vfs_heatmap_topk(const float* maps, float* vals, int* idx, float* minv, int* flags, long long N, int H, int W, int topk,
+                     vfs_stream_t stream);
+/* vfs_label_counts: intersect_and_union (core/evaluation/iou.py:5-63) of one frame or of a whole video.  pred / gt uint8 [n]
+ * (n <= 2^40), num_classes 1..256, ignore_index 0..255 or -1 for none.  counts uint64 [num_classes][3] = {intersect,
+ * prediction area, label area} (union = prediction + label - intersect), ADDED onto what the buffer holds: zero it once,
+ * sum a dataset on the device, read it back once.  Pixels with gt == ignore_index are dropped first.  As
+ * np.histogram(x, bins=np.arange(num_classes + 1)), whose last bin is closed: a value equal to num_classes is counted in
+ * class num_classes - 1, larger values are dropped. */
+int vfs_label_counts(const uint8_t* pred, const uint8_t* gt, unsigned long long* counts, long long n, int num_classes,
+                     int ignore_index, vfs_stream_t stream);
+/* vfs_pose_heatmaps: the pose_coord branch of RawFrameDecode + draw_label_map (pipelines/loading.py:1055-1101).  patch fp32
+ * [P][P] (P = 6*sigma + 1 <= 1024): exp(-((x-x0)^2 + (y-y0)^2) / (2 sigma^2)) evaluated in float64 on the host and rounded
+ * to fp32 (sigma <= 0: P = 1, patch = {1}); kp int32 [K][5] per key point = {ul_x, ul_y, br_x, br_y, inside}: the reference's
+ * int()-truncated corners and the outcome of its early-return test.  out fp32 [K][H][W] (H*W <= 2^30, K <= 65535) is
+ * written whole: zero, and out[k][y][x] = patch[y - ul_y][x - ul_x] for max(0, ul) <= (x, y) < min(br, (W, H)) when inside. */
+int vfs_pose_heatmaps(const float* patch, const int* kp, float* out, int K, int H, int W, int P, vfs_stream_t stream);
+
 /* ---- training input pipeline (configs/r*_*.py:48-91: RandomResizedCrop -> Resize -> Flip -> Normalize ->
  * FormatShape NCTHW; pipelines/augmentations.py:171-334,487-596,600-707,711-794) in one pass over the decoded
  * frames.  src uint8 [B*V*T][Hs][Ws][3] RGB in pipeline order (b, v, t); boxes int32 [F][4] = left, top,

@@ -783,6 +783,35 @@ int vfs_davis_counts(const uint8_t* pred, const uint8_t* gt, int* counts, void* 
   return vfs_davis_counts_launch(a, S(stream));
 }
 
+int vfs_heatmap_topk(const float* maps, float* vals, int* idx, float* minv, int* flags, long long N, int H, int W, int topk,
+                     vfs_stream_t stream) {
+  if (N > 0 && (!maps || !vals || !idx || !minv || !flags)) return vfs_set_error(VFS_ERR_ARG, "heatmap_topk: null buffer");
+  if (((uintptr_t)maps & 3u) != 0) return vfs_set_error(VFS_ERR_ARG, "heatmap_topk: maps must be 4-byte aligned");
+  if (H < 1 || W < 1 || (long long)H * W > (1LL << 28)) return vfs_set_error(VFS_ERR_SHAPE, "heatmap_topk: 1 <= H*W <= 2^28");
+  HeatmapTopkArgs a;
+  a.maps = maps; a.vals = vals; a.idx = idx; a.minv = minv; a.flags = flags;
+  a.N = N; a.HW = H * W; a.topk = topk;
+  return vfs_heatmap_topk_launch(a, S(stream));
+}
+
+int vfs_label_counts(const uint8_t* pred, const uint8_t* gt, unsigned long long* counts, long long n, int num_classes,
+                     int ignore_index, vfs_stream_t stream) {
+  if (n > 0 && (!pred || !gt || !counts)) return vfs_set_error(VFS_ERR_ARG, "label_counts: null buffer");
+  if (((uintptr_t)counts & 7u) != 0) return vfs_set_error(VFS_ERR_ARG, "label_counts: counts must be 8-byte aligned");
+  LabelCountsArgs a;
+  a.pred = pred; a.gt = gt; a.counts = counts;
+  a.n = n; a.nvec = 0; a.num_classes = num_classes; a.ignore_index = ignore_index;
+  return vfs_label_counts_launch(a, S(stream));
+}
+
+int vfs_pose_heatmaps(const float* patch, const int* kp, float* out, int K, int H, int W, int P, vfs_stream_t stream) {
+  if (K > 0 && (!patch || !kp || !out)) return vfs_set_error(VFS_ERR_ARG, "pose_heatmaps: null buffer");
+  PoseHeatmapArgs a;
+  a.patch = patch; a.kp = kp; a.out = out;
+  a.K = K; a.H = H; a.W = W; a.P = P;
+  return vfs_pose_heatmaps_launch(a, S(stream));
+}
+
 int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_t* flips, float* imgs, vfs_bf16* x4, int B, int V, int T,
                               int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r,
                               double std_g, double std_b, vfs_stream_t stream) {

@@ -359,6 +359,36 @@ struct DavisArgs {
 };
 int vfs_davis_counts_launch(const DavisArgs& a, hipStream_t s);
 
+// JHMDB / VIP evaluation around forward_test (propeval.hip)
+#define VFS_TOPK_ALL_ZERO 1u   // flags of vfs_heatmap_topk (include/vfs_hip.h)
+#define VFS_TOPK_NAN 2u
+#define VFS_TOPK_NEG_INF 4u
+struct HeatmapTopkArgs {
+  const float* maps;     // [N][HW]
+  float* vals;           // [N][topk] ascending
+  int* idx;              // [N][topk] flat indices of vals
+  float* minv;           // [N]
+  int* flags;            // [N] VFS_TOPK_ALL_ZERO | VFS_TOPK_NAN | VFS_TOPK_NEG_INF
+  long long N;
+  int HW, topk;
+};
+int vfs_heatmap_topk_launch(const HeatmapTopkArgs& a, hipStream_t s);
+struct LabelCountsArgs {
+  const uint8_t* pred;   // [n]
+  const uint8_t* gt;     // [n]
+  unsigned long long* counts;   // [num_classes][3] = intersect, prediction area, label area (accumulated onto)
+  long long n, nvec;     // nvec: 16-byte steps of the vector body (set by the launcher)
+  int num_classes, ignore_index;
+};
+int vfs_label_counts_launch(const LabelCountsArgs& a, hipStream_t s);
+struct PoseHeatmapArgs {
+  const float* patch;    // [P][P]
+  const int* kp;         // [K][5] = ul_x, ul_y, br_x, br_y, inside
+  float* out;            // [K][H][W]
+  int K, H, W, P;
+};
+int vfs_pose_heatmaps_launch(const PoseHeatmapArgs& a, hipStream_t s);
+
 // training input pipeline (pipeline.hip)
 struct PipelineArgs {
   const uint8_t* src;    // [F][Hs][Ws][3] decoded RGB frames, F = B*V*T in pipeline order (b, v, t)
