@@ -10,19 +10,18 @@ Backward of a unit: bn_bwd_reduce -> (all-reduce) -> bn_bwd_apply -> wgrad (+dgr
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
 
 from ._lib import Tape, TapeLib, get_lib
-from .packing import (igemm_ksplit, bn_fold_eligible, build_pack_table, build_reduce_table, conv_halo_eligible, conv_stats_rows, wgrad_halo_eligible,
-                      wgrad_inl_floats, wgrad_splits, small_map)
+from .packing import (bn_fold_eligible, build_pack_table, build_reduce_table, conv_halo_eligible, conv_stats_rows, wgrad_halo_eligible,
+                      wgrad_splits, small_map)
 
 BF16 = torch.bfloat16
 
 FIN_FUSE = os.environ.get('VFS_FIN_FUSE', '1') == '1'      # BatchNorm statistics finished in the apply kernels' prologue
-COARSE_ROWS = int(os.environ.get('VFS_COARSE_ROWS', '0'))      # conv launches sum their statistics rows in groups (vfs_conv_fwd_coarse): 0 off, 1 implicit-GEMM kernels, 2 halo kernels too
-TILES_PER_TICKET = [1 << 16]      # capacity (uint32 words) of the shared ticket buffer
 FIN_MAX_ROWS = int(os.environ.get('VFS_FIN_MAX_ROWS', '128'))   # ... for at most this many statistics rows per group
 FIN_XCHG = os.environ.get('VFS_FIN_XCHG', '0') == '1'      # SyncBN (round 6, opt-in): ... and the window exchange folded into the same launch (vfs_bn_act_fin_xchg / vfs_bn_bwd_apply_fin_xchg) - measured LEVEL with the reduction + exchange launch of rounds 3-5 on one GPU (8.92 vs 8.88 ms), and its waiting workgroups hold their CUs, so the default stays 0
 # timing experiments only: kernel families (Engine.timed labels) whose launches are dropped - results are garbage, the step
@@ -31,8 +30,6 @@ MASK_ADD = os.environ.get('VFS_MASK_ADD', '1') == '1'     # with MASK_BITS: the 
 MASK_BITS = os.environ.get('VFS_MASK_BITS', '1') == '1'   # residual joins also write a bit-packed ReLU mask; their BatchNorm backward reads it instead of y (R50 -0.3 ms)
 NOMASK = os.environ.get('VFS_DEBUG_NOMASK') == '1'     # what-if timing: BatchNorm backward without reading the activation as ReLU mask
 SKIP = frozenset(filter(None, os.environ.get('VFS_DEBUG_SKIP', '').split(',')))
-KSPLIT = os.environ.get('VFS_KSPLIT', '0') == '1'     # split-K for the head's Linear layers (slower as measured)
-WGRAD_INL = os.environ.get('VFS_WGRAD_INL', '0') == '1'      # round 6, opt-in: split-K reduction of the weight gradients inside the launch (vfs_conv_wgrad_inl) - measured SLOWER (R50 7.97 -> 10.8 ms: device-scope sc1 accesses move ~0.2 TB/s, MEASUREMENTS.md); default: kernel + wgrad_reduce
 
 
 class ConvUnit:
@@ -45,16 +42,40 @@ class ConvUnit:
         self.wf = self.wd = None
         self.bnp = self.sums = self.bsums = None
         self.need_wd = True
+        self.relu = False        # head units: the fused Linear + BatchNorm1d + ReLU launch applies the activation itself
+        self.true_w = None       # stem: image width without the NHWC4 row padding
+        self.mask_bits = None    # bit-packed ReLU mask of the last bn_act(want_mask=True), None when it wrote none
+        self.nbt_pending = 0     # BatchNorm.num_batches_tracked increments not yet materialised (Engine.flush_counters)
 
     def out_hw(self, H, W):
         span = self.dil * (self.k - 1) + 1
         return (H + 2 * self.pad - span) // self.stride + 1, (W + 2 * self.pad - span) // self.stride + 1
 
 
+class FinRows(NamedTuple):
+    """conv_fwd -> bn_act: BatchNorm statistics that the apply launch finishes in its prologue"""
+    rows: Optional[torch.Tensor]      # float[G][nrows][2][C] partial sums; None: u.sums already holds the sums over the ranks
+    nrows: int                        # rows per group
+    count: float                      # elements per channel behind one group's statistics (all ranks)
+    xchg: object = None               # SyncBN: the P2PExchange whose window exchange runs inside the same launch
+
+
+class FusedAct(NamedTuple):
+    """conv_fwd -> bn_act: the activation, already produced by the fused Linear + BatchNorm1d + ReLU launch"""
+    act: torch.Tensor
+
+
+class BwdRows(NamedTuple):
+    """conv_bwd -> bn_bwd: the BatchNorm-backward statistics rows of `unit` that the dgrad epilogue emitted"""
+    unit: ConvUnit
+    rows: torch.Tensor
+    nrows: int                        # rows of all groups together
+
+
 class Engine:
     def __init__(self, lib=None):
         self.lib = lib if lib is not None else get_lib()
-        self.n_wgrad_tickets = int(self.lib.cfunc('wgrad_tickets')())      # size of the ticket array of vfs_conv_wgrad_inl
+        self._real_lib = None     # the library itself while self.lib records onto a tape
         self.bufs = {}
         self.units = []
         self._pack = None
@@ -63,6 +84,7 @@ class Engine:
         self._side = {}
         self._side_dirty = False
         self.prof = None     # list collecting (kind, flops, start_event, end_event) when profiling
+        self.prof_pool = None     # optional pre-created timing events for it
         self.tape = None
         # weight-gradient split-K partials: reduced per layer right after the kernel (default), or - inside the trackers'
         # backward chain (defer_wgrad) - kept in per-layer buffers and reduced by ONE table-driven launch per flush
@@ -70,6 +92,7 @@ class Engine:
         self._wpending = []
         self._wtables = {}
         self._p2p, self._p2p_tried = None, False      # SyncBN statistic exchange over xGMI (vfs_amd/p2p.py), set up lazily
+        self._xseq = 0      # number of the next folded SyncBN exchange of the running launch chain
         self.generation = 0  # bumped whenever a persistent buffer is (re)allocated: recorded launch chains hold raw pointers
         for kv in filter(None, os.environ.get('VFS_OPTS', '').split(',')):      # kernel A/B knobs: "name=value,..."
             name, value = kv.split('=')
@@ -118,16 +141,20 @@ class Engine:
             self.generation += 1
         return t
 
-    def ws(self, key, numel, dtype, dev):
+    def ws(self, key, numel, dtype, dev, alloc=torch.empty):
         """grow-only flat workspace"""
         t = self.bufs.get(key)
         if t is None or t.numel() < numel or t.dtype != dtype or t.device != dev:
             if t is not None and dev.type == 'cuda':
                 torch.cuda.synchronize(dev)     # the old block may still be in use on the side stream
-            t = torch.empty(int(numel), dtype=dtype, device=dev)
+            t = alloc(int(numel), dtype=dtype, device=dev)
             self.bufs[key] = t
             self.generation += 1
         return t
+
+    def zeros(self, key, numel, dtype, dev):
+        """grow-only flat buffer that starts zero-filled and that every user leaves zero (ticket counters, constant zero operands)"""
+        return self.ws(key, numel, dtype, dev, alloc=torch.zeros)
 
     @staticmethod
     def conv_kind(u, N, H, W, dgrad=False):
@@ -152,7 +179,7 @@ class Engine:
                 finally:
                     self.tape.next_meta = None
             return fn(*args)
-        pool = getattr(self, 'prof_pool', None)
+        pool = self.prof_pool
         if pool:                       # pre-created events: creation is the expensive part
             e0, e1 = pool.pop(), pool.pop()
         else:
@@ -222,7 +249,7 @@ class Engine:
             self.lib.p2p_chain_start(x.state, self.stream(dev))
 
     def next_xseq(self):
-        n = getattr(self, '_xseq', 0)
+        n = self._xseq
         self._xseq = n + 1
         return n
 
@@ -264,7 +291,8 @@ class Engine:
 
     # ------------------------------------------------------------------ forward primitives
     def conv_fwd(self, u, x, N, H, W, G, train, tag='', in_bn=None, defer_fin=False):
-        """raw = conv(x); BN statistics/params when the unit has a BN.  Returns (raw, Ho, Wo)."""
+        """raw = conv(x); BN statistics/params when the unit has a BN.  Returns (raw, Ho, Wo, fin).  defer_fin: the caller's next
+        launch is bn_act on raw, which gets `fin` - what is left for it to do (FinRows), the finished activation (FusedAct) or None"""
         dev = x.device
         s = self.stream(dev)
         lib = self.lib
@@ -299,106 +327,93 @@ class Engine:
         else:
             want_rows = want_stats
         partial = self.ws('ws.stats', G * nblk_g * 2 * u.cout, torch.float32, dev) if want_rows else None
-        # large maps (more than FIN_MAX_ROWS statistics rows per group): the conv launch sums its rows in groups of 2^L itself, so
-        # that the bn_act behind it can finish the statistics in its prologue and the reduction launch in between disappears
-        coarse_l2, coarse_rows = 0, None
-        if (COARSE_ROWS and want_rows and fused and defer_fin and FIN_FUSE and train and not self.collectives_on and in_bn is None
-                and u.kind != 'stem' and u.dil == 1 and nblk_g > FIN_MAX_ROWS and (COARSE_ROWS >= 2 or self.conv_kind(u, N, H, W) == 'conv_igemm')):
-            L = 1
-            while (nblk_g >> L) > FIN_MAX_ROWS:
-                L += 1
-            if nblk_g % (1 << L) == 0 and L <= 8 and G * (nblk_g >> L) * ((u.cout + 63) // 64) <= TILES_PER_TICKET[0]:
-                coarse_l2 = L
-                coarse_rows = self.ws('ws.stats_coarse', G * (nblk_g >> L) * 2 * u.cout, torch.float32, dev)
         bias = u.bias.data if u.bias is not None else None
-        groups = [(0, N, partial)] if fused else [
-            (g * Ng, Ng, partial[g * nblk_g * 2 * u.cout:] if want_rows else None) for g in range(G)]
+
+        def work(n):      # algorithmic FLOP and HBM bytes (every operand once) of a launch over n images
+            return (2.0 * n * Ho * Wo * u.cout * u.k * u.k * u.cin, 2.0 * (n * H * W * u.cin + n * Ho * Wo * u.cout + u.cout * u.k * u.k * u.cin))
         if lin_fused:
             bn = u.bn
             u.sums = self.buf(f'{u.name}.sums', (G, 2, u.cout), torch.float64, dev)
             u.bnp = self.buf(f'{u.name}.bnp', (G, 4, u.cout), torch.float32, dev)
             act = self.buf(f'{u.name}{tag}.act', (N, u.cout), BF16, dev)      # (the shape bn_act gives the head: raw.view(N, cout))
-            self.timed('conv_igemm', (2.0 * M * u.cout * u.cin, 2.0 * (M * u.cin + 2 * M * u.cout + u.cout * u.cin)), dev, lib.linear_bn_act,
+            flops, nbytes = work(N)
+            self.timed('conv_igemm', (flops, nbytes + 2.0 * M * u.cout), dev, lib.linear_bn_act,      # (raw AND the activation go out)
                        x, u.wf, bias, bn.weight.data, bn.bias.data, y, act, u.bnp, u.sums, bn.running_mean, bn.running_var, M, u.cin, u.cout, mpg,
-                       1 if getattr(u, 'relu', False) else 0, float(mpg), float(bn.eps), float(bn.momentum), s)
-            u.nbt_pending = getattr(u, 'nbt_pending', 0) + G
-            self._fused_act = (u, act)      # the bn_act call that follows hands this tensor out
-            return y, Ho, Wo
+                       1 if u.relu else 0, float(mpg), float(bn.eps), float(bn.momentum), s)
+            u.nbt_pending += G
+            return y, Ho, Wo, FusedAct(act)
+        groups = [(0, N, partial)] if fused else [
+            (g * Ng, Ng, partial[g * nblk_g * 2 * u.cout:] if want_rows else None) for g in range(G)]
         for n0, nn_, part in groups:
             if u.kind == 'stem':
                 self.timed('stem_fwd', (2.0 * nn_ * Ho * Wo * 64 * 147, 2.0 * nn_ * (H * W * 4 + Ho * Wo * 64)), dev, lib.stem_fwd,
                            x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], part, nn_, H, W, Ho, Wo, s)
             elif in_bn is not None:     # x is the producer's RAW output: BatchNorm + ReLU folded into the operand load
                 assert (n0, nn_) == (0, N), 'folded input BatchNorm needs the single-launch (fused statistics) path'
-                self.timed('conv3x3_halo' if u.k == 3 else 'conv_igemm', (2.0 * nn_ * Ho * Wo * u.cout * u.k * u.k * u.cin,
-                                            2.0 * (nn_ * H * W * u.cin + nn_ * Ho * Wo * u.cout + u.cout * u.k * u.k * u.cin)), dev, lib.conv_fwd_bnin,
+                self.timed('conv3x3_halo' if u.k == 3 else 'conv_igemm', work(nn_), dev, lib.conv_fwd_bnin,
                            x, in_bn[0], in_bn[1], u.wf, y, bias, part, nn_, H, W, u.cin, Ho, Wo, u.cout,
                            u.k, u.k, u.stride, u.pad, s)
             elif u.dil != 1:            # dilated taps: implicit-GEMM forward only (frozen backbones)
-                self.timed('conv_igemm', (2.0 * nn_ * Ho * Wo * u.cout * u.k * u.k * u.cin,
-                                          2.0 * (nn_ * H * W * u.cin + nn_ * Ho * Wo * u.cout + u.cout * u.k * u.k * u.cin)), dev,
+                self.timed('conv_igemm', work(nn_), dev,
                            lib.conv_fwd_dilated, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part, nn_, H, W, u.cin, Ho, Wo, u.cout,
                            u.k, u.k, u.stride, u.pad, u.dil, s)
             else:
-                ks, ksws = igemm_ksplit(nn_ * Ho * Wo, u.cout, u.k * u.k * u.cin) if (u.k == 1 and KSPLIT) else (1, 0)
-                work = (2.0 * nn_ * Ho * Wo * u.cout * u.k * u.k * u.cin,
-                        2.0 * (nn_ * H * W * u.cin + nn_ * Ho * Wo * u.cout + u.cout * u.k * u.k * u.cin))
-                if ks > 1:      # few pixels, long reduction (the head's Linear layers): split-K fills the chip
-                    self.timed('conv_igemm', work, dev, lib.conv_fwd_splitk, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part,
-                               self.ksplit_ws(ksws, dev), ks, nn_, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
-                elif coarse_l2:     # ... and the statistics rows summed in groups by the launch itself (vfs_conv_fwd_coarse)
-                    self.timed(self.conv_kind(u, nn_, H, W), work, dev, lib.conv_fwd_coarse, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part,
-                               coarse_rows, self.stats_tickets(dev), coarse_l2, nn_, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
-                else:
-                    self.timed(self.conv_kind(u, nn_, H, W), work, dev, lib.conv_fwd, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part,
-                               nn_, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
-        if u.bn is not None:
-            bn = u.bn
-            assert getattr(self, '_pending_fin', None) is None, 'a deferred BatchNorm finalisation was never consumed'
-            if train:
-                u.sums = self.buf(f'{u.name}.sums', (G, 2, u.cout), torch.float64, dev)
-                u.bnp = self.buf(f'{u.name}.bnp', (G, 4, u.cout), torch.float32, dev)
-                if coarse_l2:
-                    self._pending_fin = (u, coarse_rows, nblk_g >> coarse_l2, float(mpg))
-                elif (defer_fin and FIN_FUSE and fused and not raw_stats and not self.collectives_on and u.kind != 'stem'
-                        and nblk_g <= FIN_MAX_ROWS):
-                    # the caller's next launch is bn_act on this output: it finishes the statistics in its prologue
-                    self._pending_fin = (u, partial, nblk_g, float(mpg))
-                elif raw_stats:
-                    self.timed('bn_stats', (0.0, 2.0 * M * u.cout), dev, lib.bn_stats_raw_finalize, y, u.sums, bn.weight.data, bn.bias.data, u.bnp, bn.running_mean, bn.running_var,
-                                              G, mpg, u.cout, float(mpg), float(bn.eps), float(bn.momentum), s)
-                elif self.collectives_on:     # SyncBN: statistics are summed over the ranks between the two stages
-                    x = self.p2p_exchange(dev)
-                    if (x is not None and x.fits(u.sums) and FIN_XCHG and defer_fin and FIN_FUSE and fused and u.kind != 'stem' and nblk_g <= FIN_MAX_ROWS
-                            and G * 2 * min(u.cout, 64) <= 256 and u.cout <= 4096):
-                        # few rows: the bn_act behind this launch sums them in its prologue AND runs the window exchange there
-                        self._pending_fin = (u, partial, nblk_g, float(mpg * self.world), x)
-                    elif x is not None and x.fits(u.sums):      # rows -> sums -> window exchange, one launch
-                        self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * u.cout), dev, lib.bn_reduce_partials_xchg, partial, u.sums,
-                                   self.bn_scratch(G, u.cout, dev), G, nblk_g, u.cout, *x.tail_args(), s)
-                    else:
-                        self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * u.cout), dev, lib.bn_reduce_partials, partial, u.sums,
-                                   self.bn_scratch(G, u.cout, dev), G, nblk_g, u.cout, s)
-                        self.allreduce(u.sums)
-                    if getattr(self, '_pending_fin', None) is not None:
-                        pass
-                    elif defer_fin and FIN_FUSE and u.kind != 'stem':
-                        # the bn_act that follows turns the all-reduced sums into scale / shift itself (any size)
-                        self._pending_fin = (u, None, 0, float(mpg * self.world))
-                    else:
-                        lib.bn_finalize(u.sums, bn.weight.data, bn.bias.data, u.bnp, bn.running_mean, bn.running_var, G,
-                                        u.cout, float(mpg * self.world), float(bn.eps), float(bn.momentum), s)
-                else:
-                    self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * u.cout), dev, lib.bn_stats_finalize, partial, u.sums,
-                               self.bn_scratch(G, u.cout, dev), bn.weight.data, bn.bias.data,
-                                          u.bnp, bn.running_mean, bn.running_var, G, nblk_g, u.cout, float(mpg),
-                                          float(bn.eps), float(bn.momentum), s)
-                u.nbt_pending = getattr(u, 'nbt_pending', 0) + G   # num_batches_tracked, flushed lazily
-            else:
-                u.bnp = self.buf(f'{u.name}.bnp_eval', (1, 4, u.cout), torch.float32, dev)
-                lib.bn_eval_params(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, u.bnp, u.cout,
-                                   float(bn.eps), s)
-        return y, Ho, Wo
+                self.timed(self.conv_kind(u, nn_, H, W), work(nn_), dev, lib.conv_fwd, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part,
+                           nn_, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
+        fin = None if u.bn is None else self._finish_stats(u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer_fin and u.kind != 'stem')
+        return y, Ho, Wo, fin
+
+    @staticmethod
+    def prologue_can_finish(nrows, G, C, xchg=False):
+        """may an apply kernel (bn_act / bn_bwd_apply) sum `nrows` statistics rows per group in its prologue - and, with xchg, run the
+        SyncBN window exchange of the sums there as well?"""
+        return FIN_FUSE and nrows <= FIN_MAX_ROWS and (not xchg or (FIN_XCHG and G * 2 * min(C, 64) <= 256 and C <= 4096))
+
+    def _finish_stats(self, u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer):
+        """where the BatchNorm statistics of u's fresh output y get finished: eval parameters, from the stored output (raw_stats),
+        in the prologue of the bn_act that follows (defer: there is one; fused: ONE conv launch wrote the rows in `partial`), or by
+        the launches issued here (SyncBN: with the sums over the ranks in between).  Returns the FinRows for that bn_act, or None"""
+        dev = y.device
+        s = self.stream(dev)
+        lib = self.lib
+        bn = u.bn
+        C = u.cout
+        if not train:
+            u.bnp = self.buf(f'{u.name}.bnp_eval', (1, 4, C), torch.float32, dev)
+            lib.bn_eval_params(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, u.bnp, C, float(bn.eps), s)
+            return None
+        u.sums = self.buf(f'{u.name}.sums', (G, 2, C), torch.float64, dev)
+        u.bnp = self.buf(f'{u.name}.bnp', (G, 4, C), torch.float32, dev)
+        u.nbt_pending += G   # num_batches_tracked, flushed lazily
+        params = (bn.weight.data, bn.bias.data, u.bnp, bn.running_mean, bn.running_var)
+        if raw_stats:
+            self.timed('bn_stats', (0.0, 2.0 * y.numel()), dev, lib.bn_stats_raw_finalize, y, u.sums, *params,
+                       G, mpg, C, float(mpg), float(bn.eps), float(bn.momentum), s)
+            return None
+        if not self.collectives_on:
+            if defer and fused and self.prologue_can_finish(nblk_g, G, C):
+                return FinRows(partial, nblk_g, float(mpg))
+            self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * C), dev, lib.bn_stats_finalize, partial, u.sums, self.bn_scratch(G, C, dev), *params,
+                       G, nblk_g, C, float(mpg), float(bn.eps), float(bn.momentum), s)
+            return None
+        # SyncBN: statistics are summed over the ranks between the two stages
+        count = float(mpg * self.world)
+        x = self.p2p_exchange(dev)
+        if x is not None and not x.fits(u.sums):
+            x = None
+        if x is not None and defer and fused and self.prologue_can_finish(nblk_g, G, C, xchg=True):
+            return FinRows(partial, nblk_g, count, x)      # few rows: bn_act sums them AND runs the window exchange
+        if x is not None:      # rows -> sums -> window exchange, one launch
+            self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * C), dev, lib.bn_reduce_partials_xchg, partial, u.sums,
+                       self.bn_scratch(G, C, dev), G, nblk_g, C, *x.tail_args(), s)
+        else:
+            self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * C), dev, lib.bn_reduce_partials, partial, u.sums,
+                       self.bn_scratch(G, C, dev), G, nblk_g, C, s)
+            self.allreduce(u.sums)
+        if defer and FIN_FUSE:
+            return FinRows(None, 0, count)      # bn_act turns the all-reduced sums into scale / shift itself (any size)
+        lib.bn_finalize(u.sums, *params, G, C, count, float(bn.eps), float(bn.momentum), s)
+        return None
 
     def can_fold_input_bn(self, u, N, G, H, W, train):
         """may conv unit u read the raw output of its producer (BatchNorm + ReLU folded into the load)?"""
@@ -420,88 +435,67 @@ class Engine:
             return False
         return bn_fold_eligible(N, G if train else 1, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
 
-    def ksplit_ws(self, need, dev):
-        """workspace of the split-K kernels: 1024 ticket words (zero between launches) + partial tiles"""
-        t = self.bufs.get('ws.ksplit')
-        if t is None or t.numel() < need or t.device != dev:
-            if t is not None and dev.type == 'cuda':
-                torch.cuda.synchronize(dev)
-            t = torch.zeros(int(need), dtype=torch.float32, device=dev)
-            self.bufs['ws.ksplit'] = t
-            self.generation += 1
-        return t
-
     def bn_scratch(self, G, C, dev):
         """scratch of the chunked BatchNorm reductions: 64 ticket counters (must start at zero; every
         launch leaves them at zero) followed by double[G][128][2][C] chunk sums"""
-        need = 32 + G * 128 * 2 * C
-        t = self.bufs.get('ws.bnred')
-        if t is None or t.numel() < need or t.device != dev:
-            t = torch.zeros(need, dtype=torch.float64, device=dev)
-            self.bufs['ws.bnred'] = t
-            self.generation += 1
-        return t
+        return self.zeros('ws.bnred', 32 + G * 128 * 2 * C, torch.float64, dev)
 
-    def bn_act(self, u, raw, M, G, train, relu, res=None, rres=None, rbnp=None, tag='', want_mask=False):
-        """y = [relu](bn(raw) [+ res] [+ bn(rres)]).  want_mask (the join of a residual block, training): also write the
-        bit-packed mask y > 0 (uint8 [M][C/8], left in u.mask_bits) - the unit's BatchNorm backward reads it instead of y"""
+    def bn_act(self, u, raw, M, G, train, relu, fin=None, res=None, rres=None, rbnp=None, tag='', want_mask=False):
+        """y = [relu](bn(raw) [+ res] [+ bn(rres)]).  fin: what the conv_fwd that produced raw returned for this call.
+        want_mask (the join of a residual block, training): also write the bit-packed mask y > 0 (uint8 [M][C/8], left in u.mask_bits) - the unit's BatchNorm backward reads it instead of y"""
         dev = raw.device
-        fa = getattr(self, '_fused_act', None)
-        if fa is not None:      # Linear + BatchNorm1d + ReLU ran as one launch (conv_fwd, lin_fused)
-            self._fused_act = None
-            assert fa[0] is u and res is None and rres is None and not want_mask and bool(relu) == bool(getattr(u, 'relu', False))
+        if isinstance(fin, FusedAct):      # Linear + BatchNorm1d + ReLU ran as one launch (conv_fwd, lin_fused)
+            assert res is None and rres is None and not want_mask and bool(relu) == bool(u.relu)
             u.mask_bits = None
-            return fa[1]
+            return fin.act
         y = self.buf(f'{u.name}{tag}.act', raw.shape, BF16, dev)
         u.mask_bits = self.buf(f'{u.name}{tag}.mbits', (M * u.cout // 8,), torch.uint8, dev) if (want_mask and MASK_BITS and u.cout % 8 == 0 and (u.cout < 64 or u.cout % 64 == 0)) else None      # slab-major layout (mask8_index): whole 64-channel slabs
         mpg = M // G if train else M
         nbytes = 2.0 * M * u.cout * (2 + (res is not None) + (rres is not None)) + (M * u.cout / 8.0 if u.mask_bits is not None else 0.0)      # raw in, activation out, identity in (+ mask bits out)
-        fin = getattr(self, '_pending_fin', None)
-        if fin is not None:
-            assert fin[0] is u, 'deferred BatchNorm finalisation belongs to another unit'
-            self._pending_fin = None
-            bn = u.bn
-            if len(fin) > 4:      # SyncBN: statistics rows summed AND exchanged with the peers inside this launch
-                self.timed('bn_act', (0.0, nbytes), dev, self.lib.bn_act_fin_xchg, raw, fin[1], fin[2], bn.weight.data, bn.bias.data, u.bnp, u.sums, bn.running_mean,
-                           bn.running_var, res, rres, rbnp, y, u.mask_bits, M, u.cout, mpg, 1 if relu else 0, fin[3], float(bn.eps), float(bn.momentum),
-                           *fin[4].tail_args(), self.next_xseq(), self.stream(dev))
-                return y
-            self.timed('bn_act', (0.0, nbytes), dev, self.lib.bn_act_fin_mask, raw, fin[1], fin[2], bn.weight.data, bn.bias.data, u.bnp, u.sums, bn.running_mean, bn.running_var,
-                                res, rres, rbnp, y, u.mask_bits, M, u.cout, mpg, 1 if relu else 0, fin[3], float(bn.eps), float(bn.momentum),
-                                self.stream(dev))
+        if fin is None:
+            self.timed('bn_act', (0.0, nbytes), dev, self.lib.bn_act_mask, raw, u.bnp, res, rres, rbnp, y, u.mask_bits, M, u.cout, mpg, 1 if relu else 0,
+                       self.stream(dev))
             return y
-        self.timed('bn_act', (0.0, nbytes), dev, self.lib.bn_act_mask, raw, u.bnp, res, rres, rbnp, y, u.mask_bits, M, u.cout, mpg, 1 if relu else 0,
-                   self.stream(dev))
+        bn = u.bn
+        # the statistics rows are summed in the prologue; SyncBN (fin.xchg): AND exchanged with the peers inside this launch
+        fn, tail = (self.lib.bn_act_fin_mask, ()) if fin.xchg is None else (self.lib.bn_act_fin_xchg, (*fin.xchg.tail_args(), self.next_xseq()))
+        self.timed('bn_act', (0.0, nbytes), dev, fn, raw, fin.rows, fin.nrows, bn.weight.data, bn.bias.data, u.bnp, u.sums, bn.running_mean, bn.running_var,
+                   res, rres, rbnp, y, u.mask_bits, M, u.cout, mpg, 1 if relu else 0, fin.count, float(bn.eps), float(bn.momentum), *tail, self.stream(dev))
         return y
 
     # ------------------------------------------------------------------ backward primitives
-    def bn_bwd(self, u, g, ymask, raw, M, G, want_gm=False, relu=False):
+    @staticmethod
+    def bwd_row_pixels(mpg, cap):
+        """pixels per BatchNorm-backward statistics row: a divisor of the group size mpg (rows never straddle groups), at most cap;
+        a whole group per row where that divisor would be under 16"""
+        ppb = math.gcd(mpg, cap)
+        return ppb if ppb >= 16 else mpg
+
+    def bn_bwd(self, u, g, ymask, raw, M, G, want_gm=False, relu=False, rows=None):
         """gradient wrt the raw conv output (and optionally the ReLU-masked incoming gradient).
         ymask: the unit's output (residual units); relu=True without ymask: conv->BN->ReLU unit,
-        the mask is recomputed from raw inside the kernels."""
+        the mask is recomputed from raw inside the kernels.
+        rows: the BwdRows the conv_bwd that produced g returned (the reduce pass is skipped), or None."""
+        assert rows is None or rows.unit is u, 'backward statistics rows of another unit'
         if NOMASK:
             ymask = None       # what-if only (WRONG gradients): the step without the mask operand reads
         if not u.bn.training:
-            return self._bn_bwd_eval(u, g, ymask, raw, M, want_gm, relu)
+            return self._bn_bwd_eval(u, g, ymask, raw, M, want_gm, relu, rows)
         dev = raw.device
         s = self.stream(dev)
         lib = self.lib
         C = u.cout
         mpg = M // G
-        ppb = math.gcd(mpg, 512)
-        if ppb < 16:
-            ppb = mpg
+        ppb = self.bwd_row_pixels(mpg, 512)
         nblk = M // ppb
         partial = self.ws('ws.bnbwd', nblk * 2 * C, torch.float32, dev)
         u.bsums = self.buf(f'{u.name}.bsums', (G, 2, C), torch.float64, dev)
         bits = ymask is not None and ymask.dtype == torch.uint8      # bit-packed mask from bn_act(want_mask=True)
         rl = 2 if bits else (1 if relu else 0)
         mask_bytes = 0.0 if ymask is None else (M * C / 8.0 if bits else 2.0 * M * C)
-        fused = getattr(self, '_fused_bn', None)
-        self._fused_bn = None
         raw_row = False
-        if fused is not None and fused[0] is u:     # the producing dgrad already emitted the statistics rows
-            partial, nblk = fused[1], fused[2]
+        if rows is not None:     # the producing dgrad already emitted the statistics rows
+            partial, nblk = rows.rows, rows.nrows
         elif (FIN_FUSE and not self.collectives_on and nblk == G and mpg <= 512 and os.environ.get('VFS_HEAD_FUSE', '1') == '1'):
             raw_row = True      # round 6: one statistics row per group (the head's BatchNorm1d layers): the apply pass computes it itself
         else:
@@ -517,7 +511,7 @@ class Engine:
             self.timed('bn_bwd_apply', (0.0, abytes + 2.0 * M * C * 2 + mask_bytes), dev, lib.bn_bwd_apply_raw, g, ymask, raw, u.bnp, u.bsums, u.bn.weight.grad, u.bn.bias.grad,
                        dx, gm, M, C, mpg, float(mpg), rl, s)
             return dx, gm
-        if FIN_FUSE and FIN_XCHG and self.collectives_on and nblk // G <= FIN_MAX_ROWS and G * 2 * min(C, 64) <= 256 and C <= 4096:
+        if self.collectives_on and self.prologue_can_finish(nblk // G, G, C, xchg=True):
             x = self.p2p_exchange(dev)
             if x is not None and x.fits(u.bsums):
                 # SyncBN, few statistics rows: the apply pass sums them in its prologue, exchanges the sums with the peers there and
@@ -525,7 +519,7 @@ class Engine:
                 self.timed('bn_bwd_apply', (0.0, abytes), dev, lib.bn_bwd_apply_fin_xchg, g, ymask, raw, u.bnp, partial, nblk // G, u.bsums, u.bn.weight.grad, u.bn.bias.grad,
                            dx, gm, M, C, mpg, float(mpg * self.world), rl, *x.tail_args(), self.next_xseq(), s)
                 return dx, gm
-        if FIN_FUSE and not self.collectives_on and nblk // G <= FIN_MAX_ROWS:
+        if not self.collectives_on and self.prologue_can_finish(nblk // G, G, C):
             # few statistics rows: the apply pass sums them in its prologue (and writes bsums, dgamma, dbeta)
             self.timed('bn_bwd_apply', (0.0, abytes), dev, lib.bn_bwd_apply_fin, g, ymask, raw, u.bnp, partial, nblk // G, u.bsums, u.bn.weight.grad, u.bn.bias.grad, dx, gm, M, C,
                                  mpg, float(mpg), rl, s)
@@ -535,26 +529,11 @@ class Engine:
                    float(mpg * self.world), rl, s)
         return dx, gm
 
-    def stats_tickets(self, dev):
-        """uint32 tickets of the coarse statistics rows: zero once, every launch leaves them at zero"""
-        t = self.bufs.get('ws.stats_tickets')
-        if t is None or t.device != dev:
-            t = torch.zeros(TILES_PER_TICKET[0], dtype=torch.int32, device=dev)
-            self.bufs['ws.stats_tickets'] = t
-            self.generation += 1
-        return t
-
     def zero_sums(self, C, dev):
         """double[1][2][C] of zeros (never written): BatchNorm backward without the batch-statistic terms"""
-        key = f'ws.zero_sums.{C}'
-        t = self.bufs.get(key)
-        if t is None or t.device != dev:
-            t = torch.zeros(1, 2, C, dtype=torch.float64, device=dev)
-            self.bufs[key] = t
-            self.generation += 1
-        return t
+        return self.zeros(f'ws.zero_sums.{C}', 2 * C, torch.float64, dev)
 
-    def _bn_bwd_eval(self, u, g, ymask, raw, M, want_gm, relu):
+    def _bn_bwd_eval(self, u, g, ymask, raw, M, want_gm, relu, rows):
         """BatchNorm in eval mode inside a training step (resnet.py:577-654: frozen_stages, norm_eval, partial_bn): the output is
         an affine map of the input with FIXED coefficients, so dx = g * mask * scale - the apply kernel with zero statistic
         sums - and, when gamma / beta are still trained (norm_eval), dgamma = sum g*mask*xhat, dbeta = sum g*mask with xhat
@@ -565,15 +544,11 @@ class Engine:
         C = u.cout
         bits = ymask is not None and ymask.dtype == torch.uint8
         rl = 2 if bits else (1 if relu else 0)
-        fused = getattr(self, '_fused_bn', None)
-        self._fused_bn = None
         if u.bn.weight.requires_grad or u.bn.bias.requires_grad:
-            if fused is not None and fused[0] is u:
-                partial, nblk = fused[1], fused[2]
+            if rows is not None:
+                partial, nblk = rows.rows, rows.nrows
             else:
-                ppb = math.gcd(M, 512)
-                if ppb < 16:
-                    ppb = M
+                ppb = self.bwd_row_pixels(M, 512)
                 nblk = M // ppb
                 partial = self.ws('ws.bnbwd', nblk * 2 * C, torch.float32, dev)
                 self.timed('bn_bwd_reduce', (0.0, 4.0 * M * C), dev, lib.bn_bwd_reduce, g, ymask, raw, u.bnp, partial, M, C, M, ppb, rl, s)
@@ -589,26 +564,19 @@ class Engine:
 
     def _bwd_sums(self, u, partial, G, bpg, C, dev):
         """partial (S1, S2) rows -> u.bsums (all-reduced for SyncBN) and dgamma / dbeta (local sums)"""
-        s = self.stream(dev)
-        if self.collectives_on:     # local sums + local dgamma / dbeta in one launch, then the sums over the ranks (SyncBN)
-            x = self.p2p_exchange(dev)
-            if x is not None and x.fits(u.bsums):      # ... in the same launch: the reduction's last workgroup runs the window exchange
-                self.timed('bn_stats', (0.0, 8.0 * G * bpg * C), dev, self.lib.bn_bwd_sums_paramgrad_xchg, partial, u.bsums,
-                           self.bn_scratch(G, C, dev), u.bn.weight.grad, u.bn.bias.grad, G, bpg, C, *x.tail_args(), s)
-                return
-            self.timed('bn_stats', (0.0, 8.0 * G * bpg * C), dev, self.lib.bn_bwd_sums_paramgrad, partial, u.bsums,
-                       self.bn_scratch(G, C, dev), u.bn.weight.grad, u.bn.bias.grad, G, bpg, C, s)
+        # SyncBN with the window exchange up: the reduction's last workgroup runs it in the same launch; else the sums go over the ranks after it
+        x = self.p2p_exchange(dev) if self.collectives_on else None
+        xchg = x is not None and x.fits(u.bsums)
+        self.timed('bn_stats', (0.0, 8.0 * G * bpg * C), dev, self.lib.bn_bwd_sums_paramgrad_xchg if xchg else self.lib.bn_bwd_sums_paramgrad,
+                   partial, u.bsums, self.bn_scratch(G, C, dev), u.bn.weight.grad, u.bn.bias.grad, G, bpg, C, *(x.tail_args() if xchg else ()), self.stream(dev))
+        if not xchg:
             self.allreduce(u.bsums)
-        else:
-            self.timed('bn_stats', (0.0, 8.0 * G * bpg * C), dev, self.lib.bn_bwd_sums_paramgrad, partial, u.bsums,
-                       self.bn_scratch(G, C, dev), u.bn.weight.grad, u.bn.bias.grad, G, bpg, C, s)
 
     def flush_counters(self):
         """materialise the lazily counted BatchNorm.num_batches_tracked buffers"""
         for u in self.units:
-            n = getattr(u, 'nbt_pending', 0)
-            if n and u.bn is not None:
-                u.bn.num_batches_tracked += n
+            if u.nbt_pending and u.bn is not None:
+                u.bn.num_batches_tracked += u.nbt_pending
                 u.nbt_pending = 0
 
     def stem_pool_bn_bwd(self, u, gp, yp, idx, raw, N, H, W, Hp, Wp, G, xpool=None):
@@ -621,9 +589,7 @@ class Engine:
             G = 1
         npg = N // G
         mpg_p = npg * Hp * Wp
-        ppb = math.gcd(mpg_p, 256)
-        if ppb < 16:
-            ppb = mpg_p
+        ppb = self.bwd_row_pixels(mpg_p, 256)
         nblk = (N * Hp * Wp) // ppb
         partial = self.ws('ws.bnbwd', nblk * 2 * C, torch.float32, dev)
         u.bsums = self.buf(f'{u.name}.bsums', (G, 2, C), torch.float64, dev)
@@ -655,7 +621,7 @@ class Engine:
 
     def wgrad_join(self, dev):
         """the current stream waits for every weight-gradient kernel issued so far"""
-        if dev.type == 'cuda' and getattr(self, '_side_dirty', False):
+        if dev.type == 'cuda' and self._side_dirty:
             side = self._side.get(dev)
             if side is not None:
                 self.record(torch.cuda.current_stream(dev).wait_stream, side)
@@ -682,16 +648,6 @@ class Engine:
             return self.buf(f'{u.name}.wpart', (nsplit * cout * ktot,), torch.float32, dev)
         return self.ws('ws.wgrad', nsplit * cout * ktot, torch.float32, dev)
 
-    def wgrad_tickets(self, dev):
-        """uint32 tickets of the in-launch split-K reductions (vfs_conv_wgrad_inl): zero once, every launch leaves them at zero;
-        shared by all weight-gradient launches - they run one after the other on the side stream"""
-        t = self.bufs.get('ws.wgrad_tickets')
-        if t is None or t.device != dev:
-            t = torch.zeros(self.n_wgrad_tickets, dtype=torch.int32, device=dev)
-            self.bufs['ws.wgrad_tickets'] = t
-            self.generation += 1
-        return t
-
     def wgrad_target(self, u, partial, nsplit, cout, ktot, cin, k, stem):
         """the `grad` argument of the weight-gradient entry points: the gradient itself, or None (= reduce later)"""
         if not self.defer_wgrad:
@@ -716,10 +672,10 @@ class Engine:
             self.lib.wgrad_reduce_table(tab[0], tab[1], tab[2], self.stream(dev))
 
     def conv_bwd(self, u, dx, x_in, N, H, W, Ho, Wo, need_dgrad, add=None, g_out=None, bn_next=None, x_in_bn=None, add_mask=None):
-        """weight (and bias) gradients accumulate into .grad; returns the input gradient or None.
+        """weight (and bias) gradients accumulate into .grad; returns (input gradient or None, BwdRows or None).
         bn_next = (unit, raw, ymask, relu, G): the BatchNorm unit whose backward consumes the input
         gradient; for stride-1 convs the dgrad epilogue also emits that unit's backward statistics
-        (vfs_conv_dgrad_bn) and the following bn_bwd skips its reduce pass."""
+        (vfs_conv_dgrad_bn): handed to its bn_bwd, the returned BwdRows let it skip the reduce pass."""
         dev = dx.device
         s = self.stream(dev)
         lib = self.lib
@@ -734,14 +690,11 @@ class Engine:
                 self.timed('stem_wgrad', (2.0 * M * 64 * 147, 2.0 * (M * 64 + N * H * W * 4)), dev, lib.stem_wgrad,
                            dx, x_in, partial, self.wgrad_target(u, partial, nsplit, 64, 256, 3, 7, 1), N, H, W, Ho, Wo, nsplit, pps,
                            self.stream(dev))
-            return None
+            return None, None
         ktot = u.k * u.k * u.cin
         halo = (N, H, W, u.cin) if wgrad_halo_eligible(N, H, W, u.cin, u.cout, u.k, u.stride, u.pad) else None
         nsplit, pps = wgrad_splits(M, u.cout, ktot, halo_geom=halo)
-        inl = (WGRAD_INL and not self.defer_wgrad and u.cin % 4 == 0 and ((ktot + 127) // 128) * (u.cout // 64) <= self.n_wgrad_tickets
-               and not (x_in_bn is not None and halo is None))      # (the in-launch reduction folds the input BatchNorm in the halo kernel only)
-        partial = ((self.ws('ws.wgrad', wgrad_inl_floats(nsplit, u.cout, ktot), torch.float32, dev) if inl else self.wgrad_partial(u, nsplit, u.cout, ktot, dev))
-                   if u.weight.requires_grad else None)
+        partial = self.wgrad_partial(u, nsplit, u.cout, ktot, dev) if u.weight.requires_grad else None
         flops = 2.0 * M * u.cout * ktot
         # ALGORITHMIC bytes: dY + x once, the fp32 gradient read-modify-write.  (The fp32 split-K partials - written by the
         # kernel, re-read by the reduction: 8 * nsplit * Cout * Ktot bytes - are implementation traffic; they show up in the
@@ -756,25 +709,19 @@ class Engine:
             wtarget = self.wgrad_target(u, partial, nsplit, u.cout, ktot, u.cin, u.k, 0)
             with self.on_side_stream(dev):
                 ss = self.stream(dev)
-                if inl:
-                    # one launch: the last workgroup of a tile sums the split-K partials itself (the launches of ONE stream share the tickets)
-                    inb = x_in_bn if x_in_bn is not None else (None, 0)
-                    self.timed('conv3x3_wgrad_halo' if halo is not None else 'conv_wgrad', (flops, wbytes), dev, lib.conv_wgrad_inl, dx, x_in, inb[0], inb[1],
-                               partial, wtarget, self.wgrad_tickets(dev), N, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, nsplit, pps, ss)
-                elif x_in_bn is not None:     # x_in is the producer's RAW output (see conv_fwd)
-                    self.timed('conv3x3_wgrad_halo' if halo is not None else 'conv_wgrad', (flops, wbytes), dev, lib.conv_wgrad_bnin, dx, x_in, x_in_bn[0], x_in_bn[1], partial,
+                family = 'conv3x3_wgrad_halo' if halo is not None else 'conv_wgrad'
+                if x_in_bn is not None:     # x_in is the producer's RAW output (see conv_fwd)
+                    self.timed(family, (flops, wbytes), dev, lib.conv_wgrad_bnin, dx, x_in, x_in_bn[0], x_in_bn[1], partial,
                                wtarget, N, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, nsplit, pps, ss)
                 else:
-                    self.timed('conv3x3_wgrad_halo' if halo is not None else 'conv_wgrad', (flops, wbytes), dev, lib.conv_wgrad, dx, x_in, partial, wtarget, N, H, W, u.cin, Ho,
+                    self.timed(family, (flops, wbytes), dev, lib.conv_wgrad, dx, x_in, partial, wtarget, N, H, W, u.cin, Ho,
                                Wo, u.cout, u.k, u.k, u.stride, u.pad, nsplit, pps, ss)
                 if u.bias is not None and u.bias.requires_grad:
                     lib.bias_grad(dx, u.bias.grad, M, u.cout, ss)
         if not need_dgrad:
-            return None
+            return None, None
         gin = g_out if g_out is not None else self.buf(f'{u.name}.gin', (N, H, W, u.cin), BF16, dev)
-        self._fused_bn = None
-        ks, ksws = igemm_ksplit(N * H * W, u.cin, ktot // u.cin * u.cout) if (u.k == 1 and u.stride == 1 and KSPLIT) else (1, 0)
-        if ks == 1 and bn_next is not None and u.stride == 1 and os.environ.get('VFS_BN_FUSE', '1') == '1':
+        if bn_next is not None and u.stride == 1 and os.environ.get('VFS_BN_FUSE', '1') == '1':
             pu, praw, pymask, prelu, G = bn_next
             if NOMASK:
                 pymask = None
@@ -791,17 +738,11 @@ class Engine:
                            dev, lib.conv_dgrad_bn_maskadd, dx, u.wd, gin, add, add_mask, praw, pymask, pu.bnp, partial,
                            mpg, 2 if pbits else (1 if (prelu and pymask is None) else 0), N, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k,
                            u.stride, u.pad, s)
-                self._fused_bn = (pu, partial, nblk)
-                return gin
+                return gin, BwdRows(pu, partial, nblk)
         work = (flops, dbytes + (2.0 * N * H * W * u.cin if add is not None else 0.0))
-        if ks > 1:
-            assert add_mask is None, 'the split-K dgrad has no mask-gated add'
-            self.timed('conv_igemm', work, dev, lib.conv_dgrad_splitk, dx, u.wd, gin, add, self.ksplit_ws(ksws, dev), ks, N, H, W, u.cin,
-                       Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
-        else:
-            self.timed(self.conv_kind(u, N, Ho, Wo, dgrad=True), work, dev, lib.conv_dgrad_maskadd, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo, u.cout,
-                       u.k, u.k, u.stride, u.pad, s)
-        return gin
+        self.timed(self.conv_kind(u, N, Ho, Wo, dgrad=True), work, dev, lib.conv_dgrad_maskadd, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo, u.cout,
+                   u.k, u.k, u.stride, u.pad, s)
+        return gin, None
 
 
 _ENGINES = {}

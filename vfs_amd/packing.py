@@ -124,7 +124,7 @@ def bn_fold_eligible(N, G, H, W, Cin, Cout, k, stride, pad):
 def igemm_ksplit(M, Cout, Ktot, target_blocks=256):
     """Split-K plan of the implicit-GEMM kernel for problems that would not fill the chip (the head's Linear
     layers): (ksplit, workspace floats).  ksplit == 1: plain kernel, no workspace.
-    The engine only uses it under VFS_KSPLIT=1: measured on MI355X the exchange of fp32 partial tiles through
+    The engine does not use it: measured on MI355X the exchange of fp32 partial tiles through
     device-coherent memory costs more than the 16-workgroup launches it replaces (R50 step 11.4 -> 11.85 ms)."""
     bc = 128 if Cout % 128 == 0 else 64
     tiles = ((M + 127) // 128) * ((Cout + bc - 1) // bc)

@@ -252,7 +252,7 @@ class ResNet(nn.Module):
         stem = self.conv1.unit
         stem.true_w = W_true
         stem_train = train and self.conv1.bn.training
-        raw, Hs, Ws = eng.conv_fwd(stem, x4, N, H, x4.shape[2], G, stem_train)
+        raw, Hs, Ws, _ = eng.conv_fwd(stem, x4, N, H, x4.shape[2], G, stem_train)
         Hp, Wp = (Hs + 2 - 3) // 2 + 1, (Ws + 2 - 3) // 2 + 1
         dev = x4.device
         pooled = eng.buf('backbone.pool', (N, Hp, Wp, 64), BF16, dev)
@@ -289,7 +289,7 @@ class ResNet(nn.Module):
             # the statistics can be finished by the bn_act that follows directly (not by a folding consumer, and not
             # when the downsample conv - which re-uses the statistics workspace - runs in between)
             defer = (not fold) and not (last and blk.downsample is not None)
-            raw, oh, ow = eng.conv_fwd(c.unit, a, N, ah, aw, G, tr, in_bn=in_bn, defer_fin=defer)
+            raw, oh, ow, fin = eng.conv_fwd(c.unit, a, N, ah, aw, G, tr, in_bn=in_bn, defer_fin=defer)
             bctx['raws'].append(raw)
             bctx['dims'].append((ah, aw, oh, ow))
             M = N * oh * ow
@@ -303,7 +303,7 @@ class ResNet(nn.Module):
                     a = raw
                     bctx['acts'].append(raw)
                 else:
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin)
                     bctx['acts'].append(a)
                 bctx['act_bn'].append(in_bn)
                 ah, aw = oh, ow
@@ -311,12 +311,12 @@ class ResNet(nn.Module):
                 if blk.downsample is not None:
                     d = blk.downsample
                     dtr = train and d.bn.training
-                    draw, dh, dw = eng.conv_fwd(d.unit, x, N, h, w, G, dtr)
+                    draw, dh, dw, _ = eng.conv_fwd(d.unit, x, N, h, w, G, dtr)
                     assert (dh, dw) == (oh, ow)
                     bctx['draw'] = draw
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True, rres=draw, rbnp=d.unit.bnp, want_mask=train)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, rres=draw, rbnp=d.unit.bnp, want_mask=train)
                 else:
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True, res=x, want_mask=train)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, res=x, want_mask=train)
                 bctx['out'] = a
                 # what the backward needs of the block output: its ReLU mask (bit-packed when the engine wrote one)
                 bctx['mask'] = c.unit.mask_bits if c.unit.mask_bits is not None else a
@@ -341,7 +341,7 @@ class ResNet(nn.Module):
             return any(p.requires_grad for p in mod.parameters())
         stem_trains = trainable(self.conv1)
         first = 0 if stem_trains else next((i for i, b in enumerate(blocks) if trainable(b['blk'])), len(blocks))
-        g = None
+        g = rows = None      # rows: BatchNorm-backward statistics rows a block's last dgrad emitted for the join of the block before
         notified = set()
         for i in range(len(blocks) - 1, -1, -1):
             if i < first:
@@ -363,7 +363,7 @@ class ResNet(nn.Module):
             # the BatchNorm unit that consumes this block's INPUT gradient: the join unit of the block before
             prev = blocks[i - 1] if i > 0 else None
             next_bn = None if prev is None else (prev['blk'].convs[-1].unit, prev['raws'][-1], prev['mask'])
-            g = self._block_bwd(eng, blocks[i], g, N, G, next_bn, need_input_grad=stem_trains or i > first)
+            g, rows = self._block_bwd(eng, blocks[i], g, N, G, next_bn, need_input_grad=stem_trains or i > first, rows=rows)
             if on_stage_done is not None and i in stage_start:
                 notified.add(stage_start[i])
                 on_stage_done(getattr(self, self.res_layers[stage_start[i]]))
@@ -388,9 +388,10 @@ class ResNet(nn.Module):
         if on_stage_done is not None:
             on_stage_done(self.conv1)
 
-    def _block_bwd(self, eng, bctx, g, N, G, next_bn=None, need_input_grad=True):
+    def _block_bwd(self, eng, bctx, g, N, G, next_bn=None, need_input_grad=True, rows=None):
         """next_bn = (unit, raw, out) of the preceding block's join: the dgrad that completes this block's
-        input gradient also emits that unit's BatchNorm-backward statistics (Engine.conv_bwd).
+        input gradient also emits that unit's BatchNorm-backward statistics (Engine.conv_bwd), returned next to the
+        input gradient; rows = those the following block emitted for this block's join.
         need_input_grad=False (everything below is frozen): the dgrads towards the block input are skipped."""
         def groups(unit):      # statistics groups of a unit's BatchNorm backward: one when it runs in eval mode
             return G if unit.bn.training else 1
@@ -401,7 +402,7 @@ class ResNet(nn.Module):
         ih, iw, oh, ow = bctx['dims'][last]
         M = N * oh * ow
         # join: y = relu(bn_last(raw) + identity)
-        dx, gm = eng.bn_bwd(convs[last].unit, g, bctx['mask'], bctx['raws'][last], M, G, want_gm=True)
+        dx, gm = eng.bn_bwd(convs[last].unit, g, bctx['mask'], bctx['raws'][last], M, G, want_gm=True, rows=rows)
         gmask = None
         if gm is None:       # bit-packed mask: the masked gradient g * (y > 0) is applied on the fly by its consumers
             gm, gmask = g, bctx['mask']
@@ -419,18 +420,18 @@ class ResNet(nn.Module):
             else:
                 bn_next = None
             x_in_bn = bctx['act_bn'][ci - 1] if ci > 0 else None
-            gin = eng.conv_bwd(c.unit, dx, x_in, N, ih, iw, oh, ow, need_dgrad=(ci > 0 or need_input_grad), add=add, bn_next=bn_next,
+            gin, rows = eng.conv_bwd(c.unit, dx, x_in, N, ih, iw, oh, ow, need_dgrad=(ci > 0 or need_input_grad), add=add, bn_next=bn_next,
                                x_in_bn=x_in_bn, add_mask=gmask if add is not None else None)
             if ci > 0:
                 p = convs[ci - 1]
                 _, _, ph, pw = bctx['dims'][ci - 1]
-                dx, _ = eng.bn_bwd(p.unit, gin, None, bctx['raws'][ci - 1], N * ph * pw, G, relu=True)
+                dx, _ = eng.bn_bwd(p.unit, gin, None, bctx['raws'][ci - 1], N * ph * pw, G, relu=True, rows=rows)
         if blk.downsample is not None:
             d = blk.downsample
             boh, bow = bctx['dims'][last][2:]
             bn_next = None if next_bn is None else (next_bn[0], next_bn[1], next_bn[2], True, groups(next_bn[0]))
-            gin = eng.conv_bwd(d.unit, ddx, bctx['x'], N, h, w, boh, bow, need_dgrad=need_input_grad, add=gin, g_out=gin, bn_next=bn_next)
-        return gin
+            gin, rows = eng.conv_bwd(d.unit, ddx, bctx['x'], N, h, w, boh, bow, need_dgrad=need_input_grad, add=gin, g_out=gin, bn_next=bn_next)
+        return gin, rows
 
     # ------------------------------------------------------------------ module-level forward
     def forward(self, x):

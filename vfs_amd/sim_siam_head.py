@@ -92,11 +92,11 @@ class SimSiamHead(nn.Module):
         for ui, u in enumerate(self.units):
             tr = train and (u.bn.training if u.bn is not None else True)
             ctx['ins'].append(a)
-            raw, _, _ = eng.conv_fwd(u, a.view(N, 1, 1, u.cin), N, 1, 1, G, tr, defer_fin=u.bn is not None)
+            raw, _, _, fin = eng.conv_fwd(u, a.view(N, 1, 1, u.cin), N, 1, 1, G, tr, defer_fin=u.bn is not None)
             raw = raw.view(N, u.cout)
             ctx['raws'].append(raw)
             if u.bn is not None:
-                a = eng.bn_act(u, raw, N, G, tr, u.relu)
+                a = eng.bn_act(u, raw, N, G, tr, u.relu, fin)
             else:
                 a = raw
             ctx['acts'].append(a)
@@ -117,7 +117,7 @@ class SimSiamHead(nn.Module):
                 dx, _ = eng.bn_bwd(u, g, None, ctx['raws'][ui], N, G, relu=u.relu)
             else:
                 dx = g
-            g = eng.conv_bwd(u, dx, ctx['ins'][ui], N, 1, 1, 1, 1, need_dgrad=True)
+            g, _ = eng.conv_bwd(u, dx, ctx['ins'][ui], N, 1, 1, 1, 1, need_dgrad=True)
             g = g.view(N, u.cin)
         gfeat = eng.buf('img_head.gfeat', (N, ctx['h'], ctx['w'], ctx['C']), BF16, dev)
         eng.lib.avgpool_bwd(g, gfeat, N, ctx['h'] * ctx['w'], ctx['C'], eng.stream(dev))

@@ -376,7 +376,7 @@ class SimSiamBaseTracker(BaseTracker):
             inplace = gs.borrowed and imgs.dtype == torch.float32 and imgs.is_contiguous() and not imgs.requires_grad
             gs.imgs = imgs.detach() if inplace else imgs.detach().clone().contiguous().float()
             gs.borrowed = inplace
-            before = {id(u): getattr(u, 'nbt_pending', 0) for u in eng.units}
+            before = {id(u): u.nbt_pending for u in eng.units}
             if mode == 'graph':
                 torch.cuda.synchronize(dev)
                 gs.fwd = torch.cuda.CUDAGraph()
@@ -392,7 +392,7 @@ class SimSiamBaseTracker(BaseTracker):
                 recorded_now = True
             gs.ctx = self._ctx
             gs.means = self._loss_means
-            gs.nbt = [(u, getattr(u, 'nbt_pending', 0) - before[id(u)]) for u in eng.units]
+            gs.nbt = [(u, u.nbt_pending - before[id(u)]) for u in eng.units]
             if mode == 'graph':
                 for u, n in gs.nbt:           # the capture pass itself launched nothing
                     u.nbt_pending = before[id(u)]
@@ -401,8 +401,7 @@ class SimSiamBaseTracker(BaseTracker):
                 gs.imgs.copy_(imgs)
             gs.fwd.replay()
             for u, n in gs.nbt:
-                if n:
-                    u.nbt_pending = getattr(u, 'nbt_pending', 0) + n
+                u.nbt_pending += n
         self._ctx = gs.ctx
         self._loss_means = gs.means
         return gs.loss
