@@ -536,6 +536,34 @@ int vfs_siamfc_loss(const float* responses, const float* labels, float* loss, fl
 int vfs_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, vfs_stream_t stream);
 
+/* ---- SiamFC probe, tracking loop (siamfc_tracker_base.py:222-297 `update`): the per-frame work around the backbone and the
+ * cross-correlation.  The three entry points restate, operation by operation, what vfs_amd/siamfc.py computes on the host
+ * (crop_and_resize, resize_cubic, the tail of SiamFCProbe.update); every reduction has a fixed order.
+ *
+ * vfs_siamfc_crops: S <= 8 square crops of one frame.  frame uint8 [H][W][3] (RGB, device); out fp32 [S][3][out_size][out_size],
+ * values 0..255 (what the probe feeds to its backbone).  params: int32 [S][12] in HOST memory (read before the call returns,
+ * passed on as kernel arguments), one row per crop, computed by the host in float64 as crop_and_resize does:
+ *   [0] valid (0: the crop is all zeros - empty in-image patch or negative pad)   [1] [2] x, y origin of the in-image patch
+ *   [3] [4] its width, height   [5] [6] its width, height after the resize   [7] [8] x, y where it lands in the crop
+ *   [9] [10] [11] fill colour clip(rint(average colour)) of the rest
+ * The patch is resized by OpenCV's 8-bit bilinear arithmetic (11-bit coefficients rint(fr * 2048), >> 4, >> 16, (x + 2) >> 2,
+ * clamped to 0..255), evaluated per output pixel.  A row whose patch or target rectangle leaves its array is REFUSED. */
+int vfs_siamfc_crops(const uint8_t* frame, const int* params, float* out, int H, int W, int S, int out_size, vfs_stream_t stream);
+/* vfs_siamfc_upsample: responses fp32 [S][r][r] -> up_out fp32 [S][up][up], Keys cubic (A = -0.75) with the caller's taps:
+ * tap_idx int32 [up][4] (indices into a row / column, border replicated), tap_w fp32 [up][4], both 16-byte aligned and used for
+ * both axes; horizontal pass then vertical pass, each value ((p0 + p1) + p2) + p3 of four rounded fp32 products (no fused
+ * multiply-add).  Every value is multiplied by penalty[s] (fp32 [S]).  scale_max [S]: the maximum of each penalised map as a
+ * 64-bit key - high half the float mapped to an order-preserving unsigned integer, low half 0xffffffff - flat index (the
+ * lowest index of the maximum wins); consumed by vfs_siamfc_peak.  r * r <= 1024. */
+int vfs_siamfc_upsample(const float* responses, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                        unsigned long long* scale_max, int S, int r, int up, vfs_stream_t stream);
+/* vfs_siamfc_peak (one workgroup): scale_id = the scale with the largest maximum (lowest on ties); on that map x:
+ * x - min(x) in fp32, its sum in fp64 rounded to fp32, (x - min) / (sum + 1e-16) in fp32, times one_minus_wi in fp32, plus
+ * window_influence * hann[i] in fp64 (hann fp64 [up][up], the normalised Hann window); argmax with the lowest flat index on
+ * ties.  record int32 [4] (16-byte aligned) = {scale_id, row, col, 0}. */
+int vfs_siamfc_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
+                    float one_minus_wi, double window_influence, vfs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -552,6 +552,32 @@ int vfs_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
   if (!params || !grads || !exp_avg || !exp_avg_sq) return vfs_set_error(VFS_ERR_ARG, "adam_step: null buffer");
   return vfs_adam_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, S(stream));
 }
+int vfs_siamfc_crops(const uint8_t* frame, const int* params, float* out, int H, int W, int S, int out_size, vfs_stream_t stream) {
+  if (!frame || !params || !out) return vfs_set_error(VFS_ERR_ARG, "siamfc_crops: null buffer");
+  if (S < 1 || S > VFS_SIAMFC_MAX_SCALES) return vfs_set_error(VFS_ERR_SHAPE, "siamfc_crops: 1 <= S <= 8");
+  SiamCropArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frame = frame; a.out = out; a.H = H; a.W = W; a.S = S; a.out_size = out_size;
+  for (int i = 0; i < S; ++i) {      // params is HOST memory: it travels as kernel arguments
+    const int* p = params + 12 * i;
+    SiamCropScale& c = a.sc[i];
+    c.valid = p[0]; c.px0 = p[1]; c.py0 = p[2]; c.iw = p[3]; c.ih = p[4]; c.ow = p[5]; c.oh = p[6]; c.padx = p[7]; c.pady = p[8];
+    c.fill[0] = p[9]; c.fill[1] = p[10]; c.fill[2] = p[11];
+    if (c.valid && c.ow > 0 && c.oh > 0) { c.sx = (double)c.iw / (double)c.ow; c.sy = (double)c.ih / (double)c.oh; }
+  }
+  return vfs_siamfc_crops_launch(a, S(stream));
+}
+int vfs_siamfc_upsample(const float* responses, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                        unsigned long long* scale_max, int S, int r, int up, vfs_stream_t stream) {
+  if (!responses || !tap_idx || !tap_w || !penalty || !up_out || !scale_max) return vfs_set_error(VFS_ERR_ARG, "siamfc_upsample: null buffer");
+  if (((size_t)tap_idx | (size_t)tap_w) & 15) return vfs_set_error(VFS_ERR_ARG, "siamfc_upsample: the tap tables must be 16-byte aligned");
+  return vfs_siamfc_upsample_launch(responses, tap_idx, tap_w, penalty, up_out, scale_max, S, r, up, S(stream));
+}
+int vfs_siamfc_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
+                    float one_minus_wi, double window_influence, vfs_stream_t stream) {
+  if (!up_in || !scale_max || !hann || !record) return vfs_set_error(VFS_ERR_ARG, "siamfc_peak: null buffer");
+  return vfs_siamfc_peak_launch(up_in, scale_max, hann, record, S, up, one_minus_wi, window_influence, S(stream));
+}
 int vfs_loss_means(const float* loss, float* means, int K, int N, vfs_stream_t stream) {
   if (!loss || !means) return vfs_set_error(VFS_ERR_ARG, "loss_means: null buffer");
   return vfs_loss_means_launch(loss, means, K, N, S(stream));

@@ -234,6 +234,29 @@ int vfs_siamfc_loss_launch(const float* x, const float* tgt, float* loss_out, fl
                            hipStream_t s);
 int vfs_adam_launch(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd, int step,
                     hipStream_t s);
+// SiamFC tracking loop (siamfc_track.hip): search crops, response up-sampling, peak search
+#define VFS_SIAMFC_MAX_SCALES 8
+#define VFS_SIAMFC_MAX_RESP 1024      // r * r floats of one response map in LDS
+struct SiamCropScale {
+  int valid;           // 0: the crop is all zeros (empty in-image patch, negative pad)
+  int px0, py0;        // origin of the in-image patch in the frame
+  int iw, ih;          // its size
+  int ow, oh;          // its size after the resize
+  int padx, pady;      // where it lands in the crop; the rest is `fill`
+  int fill[3];
+  double sx, sy;       // iw / ow, ih / oh (float64 division, as the host's)
+};
+struct SiamCropArgs {
+  const uint8_t* frame;      // [H][W][3]
+  float* out;                // [S][3][out_size][out_size]
+  int H, W, S, out_size;
+  SiamCropScale sc[VFS_SIAMFC_MAX_SCALES];
+};
+int vfs_siamfc_crops_launch(const SiamCropArgs& a, hipStream_t s);
+int vfs_siamfc_upsample_launch(const float* resp, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                               unsigned long long* scale_max, int S, int r, int up, hipStream_t s);
+int vfs_siamfc_peak_launch(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
+                           float one_minus_wi, double wi, hipStream_t s);
 int vfs_cosine_loss_fwd_launch(const LossArgs& a, hipStream_t s);
 int vfs_bn_act_fin_launch(const BnActArgs& a, const BnFin& f, hipStream_t s);
 int vfs_bn_bwd_apply_raw_launch(const BnBwdArgs& a, const BnFin& f, hipStream_t s);

@@ -126,9 +126,10 @@ def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=
 class SiamFCProbe:
     """TrackerSiamFC (siamfc_tracker_base.py:88-500): `cfg` = the reference's default_cfg keys (DEFAULT_CFG above)."""
 
-    def __init__(self, cfg=None, depth=50, backbone=None, device=None):
+    def __init__(self, cfg=None, depth=50, backbone=None, device=None, device_loop=False):
         from .resnet import ResNet
         self.cfg = dict(DEFAULT_CFG, **(cfg or {}))
+        self.device_loop = bool(device_loop)      # tracking: crops, up-sampling and peak search on the device (csrc/siamfc_track.hip)
         c = self.cfg
         self.device = torch.device(device) if device is not None else torch.device('cuda:0' if torch.cuda.is_available() else 'cpu')
         self.backbone = backbone if backbone is not None else ResNet(depth, norm_cfg=dict(type='BN', requires_grad=True), **c['backbone'])
@@ -210,12 +211,17 @@ class SiamFCProbe:
         self.z_sz = np.sqrt(np.prod(self.target_sz + context))
         self.x_sz = self.z_sz * c['instance_sz'] / c['exemplar_sz']
         self.avg_color = np.mean(img, axis=(0, 1))
+        if self.device_loop:
+            self._init_device_loop(img)
+            return
         z = crop_and_resize(img, self.center, self.z_sz, c['exemplar_sz'], self.avg_color)
         z = torch.from_numpy(z).to(self.device).permute(2, 0, 1).unsqueeze(0).float()
         self.kernel = self.features(z)
 
     @torch.no_grad()
     def update(self, img):
+        if self.device_loop:
+            return self._update_device(img)
         c = self.cfg
         x = np.stack([crop_and_resize(img, self.center, self.x_sz * f, c['instance_sz'], self.avg_color) for f in self.scale_factors])
         x = torch.from_numpy(x).to(self.device).permute(0, 3, 1, 2).float()
@@ -229,6 +235,11 @@ class SiamFCProbe:
         response /= response.sum() + 1e-16
         response = (1 - c['window_influence']) * response + c['window_influence'] * self.hann_window
         loc = np.unravel_index(response.argmax(), response.shape)
+        return self._apply_peak(scale_id, loc)
+
+    def _apply_peak(self, scale_id, loc):
+        """the peak (scale_id, (row, col) in the up-sampled response) -> new centre and sizes (host state), the frame's ltwh box"""
+        c = self.cfg
         disp_in_response = np.array(loc) - (self.upscale_sz - 1) / 2
         disp_in_instance = disp_in_response * c['total_stride'] / c['response_up']
         disp_in_image = disp_in_instance * self.x_sz * self.scale_factors[scale_id] / c['instance_sz']
@@ -250,6 +261,66 @@ class SiamFCProbe:
             else:
                 boxes.append(self.update(img))
         return np.stack(boxes)
+
+    # ------------------------------------------------------------------ tracking, device loop (csrc/siamfc_track.hip)
+    def _upload_frame(self, img):
+        d = self._dl
+        if tuple(img.shape) != d['shape'] or img.dtype != np.uint8:
+            raise ValueError(f'device_loop: frames must be uint8 {d["shape"]} like the first one, got {img.dtype} {tuple(img.shape)}')
+        d['frame'].copy_(torch.from_numpy(np.ascontiguousarray(img)))
+
+    def _device_crops(self, sizes, out_size, out):
+        """crop_and_resize of the uploaded frame around self.center for every size -> `out` fp32 [len(sizes),3,out_size,out_size]"""
+        d = self._dl
+        params = np.stack([crop_params(d['shape'], self.center, sz, out_size, self.avg_color) for sz in sizes])
+        eng = shared_engine(self.device)
+        eng.lib.siamfc_crops(d['frame'], params.ctypes.data, out, d['shape'][0], d['shape'][1], len(sizes), int(out_size),
+                             eng.stream(self.device))
+
+    def _init_device_loop(self, img):
+        """the exemplar through the crop kernel, then everything update() needs per frame, uploaded / allocated once"""
+        c, dev = self.cfg, self.device
+        S, up = int(c['scale_num']), int(self.upscale_sz)
+        d = self._dl = dict(shape=tuple(img.shape))
+        d['frame'] = torch.empty(d['shape'], dtype=torch.uint8, device=dev)
+        d['z'] = torch.zeros(1, 3, c['exemplar_sz'], c['exemplar_sz'], device=dev)
+        d['x'] = torch.zeros(S, 3, c['instance_sz'], c['instance_sz'], device=dev)
+        self._upload_frame(img)
+        self._device_crops([self.z_sz], c['exemplar_sz'], d['z'])
+        self.kernel = self.features(d['z'])
+        shape = self.head(self.kernel, self.features(d['x'])).shape      # a dry pass on the blank search batch: the response size
+        if shape[0] != S or shape[-1] != shape[-2]:
+            raise ValueError(f'device_loop: {S} square response maps expected, got {tuple(shape)}')
+        d['r'] = r = int(shape[-1])
+        idx, w = _cubic_taps(r, up)
+        d['tap_idx'] = torch.from_numpy(idx.astype(np.int32)).to(dev)
+        d['tap_w'] = torch.from_numpy(w).to(dev)
+        pen = np.ones(S, np.float32)
+        pen[:S // 2] = pen[S // 2 + 1:] = np.float32(c['scale_penalty'])
+        d['penalty'] = torch.from_numpy(pen).to(dev)
+        d['hann'] = torch.from_numpy(np.ascontiguousarray(self.hann_window)).to(dev)
+        d['one_minus_wi'] = float(np.float32(1 - c['window_influence']))      # the host multiplies its fp32 map by this scalar
+        d['up'] = torch.empty(S, up, up, device=dev)
+        d['scale_max'] = torch.zeros(S, dtype=torch.int64, device=dev)
+        d['record'] = torch.zeros(4, dtype=torch.int32, device=dev)
+
+    def _update_device(self, img):
+        """update() with one frame upload and one 16-byte read-back: crops -> features -> head -> up-sampling -> peak on the device;
+        the state (centre, sizes) stays on the host and advances through the same _apply_peak as the host loop"""
+        c, d = self.cfg, self._dl
+        S, r, up = int(c['scale_num']), d['r'], int(self.upscale_sz)
+        eng = shared_engine(self.device)
+        s = eng.stream(self.device)
+        self._upload_frame(img)
+        self._device_crops([self.x_sz * f for f in self.scale_factors], c['instance_sz'], d['x'])
+        d['responses'] = resp = self.head(self.kernel, self.features(d['x']))
+        if tuple(resp.shape) != (S, 1, r, r):
+            raise ValueError(f'device_loop: response maps {tuple(resp.shape)} differ from those init() sized its buffers for')
+        eng.lib.siamfc_upsample(resp, d['tap_idx'], d['tap_w'], d['penalty'], d['up'], d['scale_max'], S, r, up, s)
+        eng.lib.siamfc_peak(d['up'], d['scale_max'], d['hann'], d['record'], S, up, d['one_minus_wi'], float(c['window_influence']), s)
+        scale_id, row, col, _ = d['record'].tolist()      # the frame's only read-back (and its only synchronisation)
+        self.last_peak = (scale_id, row, col)
+        return self._apply_peak(scale_id, (row, col))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -311,21 +382,52 @@ def crop_and_resize(img, center, size, out_size, border_value):
     return patch
 
 
+def crop_params(shape, center, size, out_size, border_value):
+    """the geometry of crop_and_resize(img, ...) for an image of `shape`, as the int32 row vfs_siamfc_crops takes (include/vfs_hip.h):
+    [valid, x / y origin and width / height of the in-image patch, its width / height after the resize, x / y pad, fill colour];
+    valid = 0 where crop_and_resize returns zeros.  Same float64 expressions, same order."""
+    size = max(2, float(size))
+    yc, xc = float(center[0]), float(center[1])
+    box = np.round(np.array([xc - size / 2, yc - size / 2, xc + size / 2, yc + size / 2])).astype(int)     # x0, y0, x1, y1
+    wh = np.array([box[2] - box[0], box[3] - box[1]])
+    H, W = shape[:2]
+    rows = range(*slice(max(box[1], 0), min(box[3], H)).indices(H))      # what the patch slice selects (a negative stop counts from the end)
+    cols = range(*slice(max(box[0], 0), min(box[2], W)).indices(W))
+    out_size = int(out_size)
+    p = np.zeros(12, np.int32)
+    if len(rows) == 0 or len(cols) == 0:
+        return p
+    bounded = np.clip(box, 0, [W, H, W, H])
+    bwh = np.array([bounded[2] - bounded[0], bounded[3] - bounded[1]])
+    ow = max(1, int(np.round(out_size * bwh[0] / wh[0])))
+    oh = max(1, int(np.round(out_size * bwh[1] / wh[1])))
+    pad = np.zeros(4, dtype=int)
+    pad[:2] = np.maximum(0, -box[:2] * out_size / wh)
+    pad[2:] = out_size - (pad[:2] + np.array([ow, oh]))
+    if np.any(pad < 0):
+        return p
+    p[:9] = 1, cols[0], rows[0], len(cols), len(rows), ow, oh, pad[0], pad[1]
+    p[9:] = np.clip(np.rint(np.asarray(border_value, dtype=np.float64)), 0, 255)
+    return p
+
+
+def _cubic_taps(n_in, n_out):
+    """resize_cubic along one axis: the four source indices [n_out,4] (border replicated) and fp32 weights [n_out,4] of every output"""
+    f = (np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5
+    i0 = np.floor(f).astype(np.int64)
+    t = (f - i0).astype(np.float32)
+    A = np.float32(-0.75)
+    w = np.stack([((A * (t + 1) - 5 * A) * (t + 1) + 8 * A) * (t + 1) - 4 * A, ((A + 2) * t - (A + 3)) * t * t + 1,
+                  ((A + 2) * (1 - t) - (A + 3)) * (1 - t) * (1 - t) + 1, np.zeros_like(t)], 1).astype(np.float32)
+    w[:, 3] = 1 - w[:, 0] - w[:, 1] - w[:, 2]
+    idx = np.clip(i0[:, None] + np.arange(-1, 3)[None], 0, n_in - 1)
+    return idx, w
+
+
 def resize_cubic(a, ow, oh):
     """cv2.resize(INTER_CUBIC) of a float32 map: Keys kernel with a = -0.75, pixel centres aligned, replicated border"""
     a = np.asarray(a, dtype=np.float32)
-
-    def taps(n_in, n_out):
-        f = (np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5
-        i0 = np.floor(f).astype(np.int64)
-        t = (f - i0).astype(np.float32)
-        A = np.float32(-0.75)
-        w = np.stack([((A * (t + 1) - 5 * A) * (t + 1) + 8 * A) * (t + 1) - 4 * A, ((A + 2) * t - (A + 3)) * t * t + 1,
-                      ((A + 2) * (1 - t) - (A + 3)) * (1 - t) * (1 - t) + 1, np.zeros_like(t)], 1).astype(np.float32)
-        w[:, 3] = 1 - w[:, 0] - w[:, 1] - w[:, 2]
-        idx = np.clip(i0[:, None] + np.arange(-1, 3)[None], 0, n_in - 1)
-        return idx, w
-    xi, xw = taps(a.shape[1], ow)
-    yi, yw = taps(a.shape[0], oh)
+    xi, xw = _cubic_taps(a.shape[1], ow)
+    yi, yw = _cubic_taps(a.shape[0], oh)
     rows = (a[:, xi] * xw[None]).sum(-1)              # [ih, ow]
     return (rows[yi] * yw[:, :, None]).sum(1).astype(np.float32)

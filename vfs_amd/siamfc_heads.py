@@ -61,6 +61,8 @@ class SiamConvFC(nn.Module):
             self._packed[id(conv)] = (key, wf, tab)
         wf = self._packed[id(conv)][1]
         n, h, w, c = t.shape
+        if c != conv.in_channels:      # the kernel takes C from the tensor: a mismatch would read past the packed weight
+            raise ValueError(f'SiamConvFC: features with {c} channels for a conv with in_channels={conv.in_channels} (cfg out_channels)')
         y = torch.empty(n, h, w, conv.out_channels, dtype=BF16, device=t.device)
         eng.lib.conv_fwd(t, wf, y, conv.bias.data if conv.bias is not None else None, None, n, h, w, c, h, w,
                          conv.out_channels, 1, 1, 1, 0, eng.stream(t.device))
