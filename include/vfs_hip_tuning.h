@@ -13,25 +13,8 @@
 extern "C" {
 #endif
 
-/* tuning knobs for A/B measurements: "halo" (1 = 3x3/stride-1 convs use the halo-tile kernels),
- * "stem_direct", "stem_blocks" (grid cap of the direct stem kernel, 0 = default), "bn_ticket",
- * "igemm_onek" (single-buffer implicit-GEMM variant: 0 never, 1 one-K-step problems, 2 every 1x1, 3 all (default since round 6)),
- * "igemm_ring_tiles" (1x1 problems with at most this many tiles use the LDS-DMA ring, default 512, 0 = off),
- * "igemm_ring_upfront" (ring variant: all fragment reads of a K-step before its MFMAs; default 0: measured, no gain),
- * "igemm_ring_fbn" (the ring also for dgrads with fused BatchNorm-backward statistics, default 1),
- * "igemm_bc" (64 forces the 64-channel tile), "igemm_xcd" (XCD-aware tile order, default 1),
- * "igemm_narrow_below" (64-channel tiles when the 128-channel tiling has fewer tiles than this, default 513),
- * "igemm_mfma_stats" (forward statistics rows on the matrix cores, default 1),
- * "wgrad_lin" (linear-address path of the generic weight gradient for 1x1 / stride-1 problems, default 1),
- * "wgrad_lin2" (the same for evenly tiled 3x3 / stride-2 problems, default 1), "wgrad_ring" (LDS-DMA ring for the 1x1 / stride-1
- * weight gradients with 128 | C and 128 | Cout, default 1), "halo_deep_max" (deep schedule of the 3x3 halo kernels for launches of at
- * most this many workgroups, default 256), "igemm_skinny" (skinny GEMM for <= 128-row Linear layers, default 1), "igemm_ring_mfma32"
- * (the ring on 32x32x16 MFMAs, default 1), "igemm_ring_gather", "igemm_pw", "igemm_pw_min_tiles" (measured, off by default),
- * "wgrad_xcd" / "halo_xcd" (XCD-aware block order of the weight-gradient kernels / the 3x3 halo kernels, default 1),
- * "halo_min_fill", "bn_chunk_rows", "bn_wide" / "bn_wide_min_mb" (plain BatchNorm apply passes on >= 128-channel tensors of at least
- * that many MB stream whole pixel rows per workgroup, default 1 / 8), "lpx_target" (workgroups the KEY FRAMES of the fp32 label propagation are split
- * into; 0 = by channel count), "lpx_wgs" / "lpx_minb" (workgroups reached by also splitting a key frame's window, with at least
- * lpx_minb 64-key blocks each; 0 = 3072 for C >= 512, < 0 = never; default minb 4) */
+/* The knobs - names, defaults and what each one selects - are the VFS_OPTIONS table of vfs_amd/csrc/vfs_options.h, the only list
+ * there is.  An unknown name returns VFS_ERR_ARG ("vfs_set_option: unknown option"). */
 int vfs_set_option(const char* name, int value);
 
 #ifdef __cplusplus

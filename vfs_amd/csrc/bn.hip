@@ -1076,12 +1076,8 @@ static inline int grid_for(long long total_vec) {
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
-int vfs_option_bn_wide = 1;          // plain bn_act / bn_bwd_apply on >= 128-channel tensors: whole pixel rows per workgroup (A/B knob)
-int vfs_option_bn_wide_min_mb = 8;   // ... from this tensor size on
-int vfs_option_bn_ticket = 1;   // capi: vfs_set_option("bn_ticket", 0) = single-workgroup-per-channel-block reduction
 // scratch = [VFS_BN_TICKETS ticket counters (zero before the first use, left zero by every launch)]
 //           [double[G][<=VFS_BN_MAX_CHUNKS][2][C] chunk sums]
-int vfs_option_bn_chunk_rows = 64;   // rows per chunk of the ticket reduction (A/B knob; was 32)
 static inline void bn_chunk_plan(int bpg, int* nchunks, int* rpc) {
   int n = (bpg + vfs_option_bn_chunk_rows - 1) / vfs_option_bn_chunk_rows;
   if (n > VFS_BN_MAX_CHUNKS) n = VFS_BN_MAX_CHUNKS;

@@ -25,21 +25,165 @@ int vfs_check_launch(const char* what) {
   return VFS_OK;
 }
 
-#define S(s) ((hipStream_t)(s))
+static hipStream_t stream_of(vfs_stream_t s) { return (hipStream_t)s; }
+// "<who>: <what>" as the error text: checks shared by several entry points name the one that was called
+static int fail(int code, const char* who, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  return vfs_set_error(code, buf);
+}
 
-int vfs_option_halo = 1;
-int vfs_option_stem_blocks = 0;
-extern int vfs_option_bn_ticket, vfs_option_bn_chunk_rows, vfs_option_bn_wide, vfs_option_bn_wide_min_mb;
-int vfs_option_stem_direct = 1;
-extern int vfs_option_igemm_xcd, vfs_option_igemm_narrow_below;
-extern int vfs_option_igemm_ring_mfma32, vfs_option_igemm_ring_gather, vfs_option_igemm_bc, vfs_option_igemm_onek, vfs_option_igemm_ring_tiles, vfs_option_igemm_ring_upfront, vfs_option_igemm_ring_fbn, vfs_option_wgrad_lin, vfs_option_wgrad_lin2, vfs_option_wgrad_ring, vfs_option_wgrad_xcd, vfs_option_halo_xcd, vfs_option_igemm_mfma_stats, vfs_option_lpx_target, vfs_option_lpx_wgs, vfs_option_lpx_minb, vfs_option_lp2, vfs_option_lp2_fpb, vfs_option_lp2_cap, vfs_option_lp2_xcd, vfs_option_lp2_trim, vfs_option_lp2_dbg, vfs_option_conv_f32_variant, vfs_option_conv_f32_dbg;
+// the A/B knobs (vfs_options.h): their definitions and the name table of vfs_set_option
+#define VFS_OPTION_DEFINE(name, dflt) int vfs_option_##name = dflt;
+VFS_OPTIONS(VFS_OPTION_DEFINE)
+#undef VFS_OPTION_DEFINE
+static const struct { const char* name; int* var; } g_options[] = {
+#define VFS_OPTION_ENTRY(name, dflt) {#name, &vfs_option_##name},
+    VFS_OPTIONS(VFS_OPTION_ENTRY)
+#undef VFS_OPTION_ENTRY
+};
 
 static ConvGeom make_geom(int N, int H, int W, int C, int Ho, int Wo, int KH, int KW, int stride, int pad, int Ktot) {
-  ConvGeom g;
+  ConvGeom g{};
   g.N = N; g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo;
   g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad; g.Ktot = Ktot;
   g.M = N * Ho * Wo;
   return g;
+}
+
+// ---- one builder per argument struct: every struct is value-initialised (fields without a default are zero), an entry point
+// calls the builder and then sets only what distinguishes it
+
+// forward convolution: gather source = x [N,H,W,Cin], destination grid = y [N,Ho,Wo,Cout]
+static ConvArgs conv_fwd_args(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, int N, int H, int W,
+                              int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad) {
+  ConvArgs a{};
+  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
+  a.src = x; a.wgt = wf; a.out = y; a.bias = bias; a.stats = stats; a.Cout = Cout;
+  return a;
+}
+// dgrad: gather source = dy [N,Ho,Wo,Cout]; destination grid = dx [N,H,W,Cin]
+static ConvArgs conv_dgrad_args(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int N, int H, int W, int Cin,
+                                int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad) {
+  ConvArgs a{};
+  a.g = make_geom(N, Ho, Wo, Cout, H, W, KH, KW, stride, pad, KH * KW * Cout);
+  a.src = dy; a.wgt = wd; a.out = dx; a.add = add; a.Cout = Cin;
+  return a;
+}
+static int set_add_mask(ConvArgs& a, const vfs_bf16* add, const uint8_t* add_mask, int N, int H, int W, int Cin) {
+  if (!add_mask) return VFS_OK;
+  if (!add || Cin % 64) return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad: add_mask needs an add operand and Cin % 64 == 0");
+  a.add_mask = add_mask; a.add_rows = (long long)N * H * W;
+  return VFS_OK;
+}
+
+static WgradArgs wgrad_args(const vfs_bf16* dy, const vfs_bf16* x, const float* in_bnp, int in_npg, float* partial, int N, int H, int W,
+                            int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int nsplit, int pix_per_split) {
+  WgradArgs a{};
+  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
+  a.dy = dy; a.x = x; a.partial = partial; a.Cout = Cout; a.pix_per_split = pix_per_split; a.nsplit = nsplit;
+  a.in_bnp = in_bnp; a.in_npg = in_npg;
+  return a;
+}
+// the tail of a weight gradient whose kernel used `nsplit` splits: reduce the partials into grad now, or (grad == null) leave them to
+// the caller's vfs_wgrad_reduce_table - its table needs the split count it offered, so plan_error (when given) is raised if the
+// kernel took fewer.  Cin: channels of the OIHW gradient (the stem: 3 of the 4 stored ones).
+static int finish_wgrad(const WgradArgs& a, float* grad, int nsplit, int Cin, int stem, const char* plan_error, hipStream_t stream) {
+  if (!grad) return plan_error && nsplit != a.nsplit ? vfs_set_error(VFS_ERR_SHAPE, plan_error) : VFS_OK;
+  return vfs_wgrad_reduce_launch(a.partial, grad, nsplit, a.Cout, a.g.Ktot, Cin, a.g.KH, a.g.KW, stem, stream);
+}
+
+static BnActArgs bn_act_args(const vfs_bf16* x, const float* bnp, const vfs_bf16* res, const vfs_bf16* rres, const float* rbnp, vfs_bf16* y,
+                             uint8_t* mask_bits, long long M, int C, int mpg, int relu) {
+  BnActArgs a{};
+  a.x = x; a.bnp = bnp; a.res = res; a.rres = rres; a.rbnp = rbnp; a.y = y; a.M = M; a.C = C; a.mpg = mpg; a.relu = relu;
+  a.mbits = mask_bits;
+  return a;
+}
+// in-kernel statistics finalisation of the forward apply pass (G = M / mpg groups) ...
+static BnFin bn_fin_fwd(const float* partial, int bpg, int G, const float* gamma, const float* beta, float* bnp, double* sums,
+                        float* running_mean, float* running_var, double count, float eps, float momentum) {
+  BnFin f{};
+  f.partial = partial; f.bpg = bpg; f.G = G; f.gamma = gamma; f.beta = beta; f.bnp = bnp; f.sums = sums;
+  f.running_mean = running_mean; f.running_var = running_var; f.count = count; f.eps = eps; f.momentum = momentum;
+  return f;
+}
+// ... and of the backward one
+static BnFin bn_fin_bwd(const float* partial, int bpg, int G, double* sums, float* dgamma, float* dbeta) {
+  BnFin f{};
+  f.partial = partial; f.bpg = bpg; f.G = G; f.sums = sums; f.dgamma = dgamma; f.dbeta = dbeta;
+  return f;
+}
+// BatchNorm backward: the operands of both passes and the outputs of pass 2 (dx, gm, count; pass 1 has none of them); what a pass
+// adds - partial / ppb, sums - is set by its entry point
+static BnBwdArgs bn_bwd_args(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, vfs_bf16* dx, vfs_bf16* gm,
+                             long long M, int C, int mpg, double count, int relu) {
+  BnBwdArgs a{};
+  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.dx = dx; a.gm = gm; a.M = M; a.C = C; a.mpg = mpg; a.count = count; a.relu = relu;
+  return a;
+}
+static P2PTail make_tail(const void* peers, int rank, int world, void* state, long long spin_limit, int seq = 0) {
+  P2PTail x{};
+  x.peers = (void* const*)peers; x.rank = rank; x.world = world; x.state = (unsigned long long*)state;
+  x.spin_limit = (unsigned long long)(spin_limit < 1 ? 1 : spin_limit);
+  x.seq = seq;
+  return x;
+}
+// preconditions of the apply passes with the SyncBN exchange folded in (vfs_bn_act_fin_xchg, vfs_bn_bwd_apply_fin_xchg)
+static int xchg_check(const char* who, int seq, const void* peers, const void* state, const void* partial) {
+  if (seq < 0 || seq >= 4095) return fail(VFS_ERR_ARG, who, "0 <= seq < 4095");
+  if (!peers || !state || !partial) return fail(VFS_ERR_ARG, who, "statistics rows, peers and state must be given");
+  return VFS_OK;
+}
+static StemBwdArgs stem_bwd_args(const vfs_bf16* gp, const vfs_bf16* yp, const uint8_t* idx, const vfs_bf16* x, const float* bnp, int N,
+                                 int H, int W, int C, int Hp, int Wp, int npg) {
+  StemBwdArgs a{};
+  a.gp = gp; a.yp = yp; a.idx = idx; a.x = x; a.bnp = bnp;
+  a.N = N; a.H = H; a.W = W; a.C = C; a.Hp = Hp; a.Wp = Wp; a.npg = npg;
+  return a;
+}
+static LossArgs loss_args(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, int N, int C, int T, int K,
+                          int negative, float weight) {
+  LossArgs a{};
+  a.p1 = p1; a.z1 = z1; a.p2 = p2; a.z2 = z2; a.N = N; a.C = C; a.T = T; a.K = K; a.negative = negative; a.weight = weight;
+  return a;
+}
+
+// label propagation: the key list, the dense kernels' workspace (dense_workspace = false: the caller has a requirement of its own)
+// and the unmasked prefix of the key list (radius <= 0, no spatial mask: every key frame may be "unmasked")
+static long long lp_workspace_need(int H, int W) { return (long long)LP_MAX_SPLIT * H * W * 10 * 8; }
+static int lp_check(const char* who, int nkeys, int radius, int non_mask_len, bool dense_workspace, const void* workspace,
+                    long long workspace_bytes, int H, int W) {
+  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return fail(VFS_ERR_SHAPE, who, "1 <= nkeys <= 64");
+  if (dense_workspace && (H <= 0 || W <= 0 || !workspace || workspace_bytes < lp_workspace_need(H, W)))
+    return fail(VFS_ERR_ARG, who, "workspace smaller than vfs_labelprop_workspace_bytes(H, W)");
+  if (non_mask_len < 0 || non_mask_len >= nkeys + (radius <= 0)) return fail(VFS_ERR_ARG, who, "0 <= non_mask_len < nkeys");
+  return VFS_OK;
+}
+static void lp_fill_kslot(int (&dst)[LP_MAX_KEYS], const int* kslot, int nkeys) {      // kslot is a HOST array
+  for (int i = 0; i < LP_MAX_KEYS; ++i) dst[i] = i < nkeys ? kslot[i] : 0;
+}
+// the dense kernels' workspace: [LP_MAX_SPLIT][H*W][10] partial top-k values, then as many key ids
+static int* lp_pidx(void* workspace, int H, int W) { return workspace ? (int*)((float*)workspace + (size_t)LP_MAX_SPLIT * H * W * 10) : nullptr; }
+static LabelPropF32Args lp_f32_args(const float* fbank, const float* sbank, float* out, void* workspace, int qframe, const int* kslot,
+                                    int nkeys, int H, int W, int C, int CO, int radius, int non_mask_len, int topk, float temperature) {
+  LabelPropF32Args a{};
+  a.fbank = fbank; a.sbank = sbank; a.out = out; a.qframe = qframe; a.nkeys = nkeys;
+  a.pval = (float*)workspace; a.pidx = lp_pidx(workspace, H, W);
+  lp_fill_kslot(a.kslot, kslot, nkeys);
+  a.H = H; a.W = W; a.C = C; a.CO = CO; a.radius = radius; a.topk = topk; a.temperature = temperature; a.non_mask_len = non_mask_len;
+  return a;
+}
+
+static PipelineArgs pipeline_args(const uint8_t* src, const int* boxes, const uint8_t* flips, float* imgs, vfs_bf16* x4, int B, int V, int T,
+                                  int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r,
+                                  double std_g, double std_b) {
+  PipelineArgs a{};
+  a.src = src; a.boxes = boxes; a.flips = flips; a.imgs = imgs; a.x4 = x4;
+  a.B = B; a.V = V; a.T = T; a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo; a.Wp = Wp;
+  a.mean[0] = mean_r; a.mean[1] = mean_g; a.mean[2] = mean_b;
+  a.stdinv[0] = 1.0 / std_r; a.stdinv[1] = 1.0 / std_g; a.stdinv[2] = 1.0 / std_b;
+  return a;
 }
 
 extern "C" {
@@ -47,155 +191,95 @@ extern "C" {
 const char* vfs_last_error(void) { return g_err; }
 int vfs_abi_version(void) { return 2; }      // 2: vfs_sgd_step(skip_flag), vfs_labelprop*(workspace_bytes)
 int vfs_set_option(const char* name, int value) {
-  if (!strcmp(name, "halo")) { vfs_option_halo = value; return VFS_OK; }
-  if (!strcmp(name, "halo_min_fill")) { vfs_option_halo_min_fill = value; return VFS_OK; }
-  if (!strcmp(name, "stem_blocks")) { vfs_option_stem_blocks = value; return VFS_OK; }
-  if (!strcmp(name, "bn_ticket")) { vfs_option_bn_ticket = value; return VFS_OK; }
-  if (!strcmp(name, "bn_wide")) { vfs_option_bn_wide = value; return VFS_OK; }
-  if (!strcmp(name, "bn_wide_min_mb")) { vfs_option_bn_wide_min_mb = value; return VFS_OK; }
-  if (!strcmp(name, "bn_chunk_rows")) { vfs_option_bn_chunk_rows = value > 0 ? value : 64; return VFS_OK; }
-  if (!strcmp(name, "stem_direct")) { vfs_option_stem_direct = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_bc")) { vfs_option_igemm_bc = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_xcd")) { vfs_option_igemm_xcd = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_narrow_below")) { vfs_option_igemm_narrow_below = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_onek")) { vfs_option_igemm_onek = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_ring_tiles")) { vfs_option_igemm_ring_tiles = value; return VFS_OK; }
-  if (!strcmp(name, "lpx_target")) { vfs_option_lpx_target = value; return VFS_OK; }
-  if (!strcmp(name, "lpx_wgs")) { vfs_option_lpx_wgs = value; return VFS_OK; }
-  if (!strcmp(name, "lpx_minb")) { vfs_option_lpx_minb = value; return VFS_OK; }
-  if (!strcmp(name, "conv_f32_dbg")) { vfs_option_conv_f32_dbg = value; return VFS_OK; }
-  if (!strcmp(name, "conv_f32_variant")) { vfs_option_conv_f32_variant = value; return VFS_OK; }
-  if (!strcmp(name, "lp2")) { vfs_option_lp2 = value; return VFS_OK; }
-  if (!strcmp(name, "lp2_fpb")) { vfs_option_lp2_fpb = value; return VFS_OK; }
-  if (!strcmp(name, "lp2_trim")) { vfs_option_lp2_trim = value; return VFS_OK; }
-  if (!strcmp(name, "lp2_xcd")) { vfs_option_lp2_xcd = value; return VFS_OK; }
-  if (!strcmp(name, "lp2_dbg")) { vfs_option_lp2_dbg = value; return VFS_OK; }
-  if (!strcmp(name, "lp2_cap")) { vfs_option_lp2_cap = value <= 0 ? 0 : (value < 16 ? 16 : value); return VFS_OK; }
-  if (!strcmp(name, "igemm_mfma_stats")) { vfs_option_igemm_mfma_stats = value; return VFS_OK; }
-  if (!strcmp(name, "wgrad_lin2")) { vfs_option_wgrad_lin2 = value; return VFS_OK; }
-  if (!strcmp(name, "wgrad_ring")) { vfs_option_wgrad_ring = value; return VFS_OK; }
-  if (!strcmp(name, "wgrad_lin")) { vfs_option_wgrad_lin = value; return VFS_OK; }
-  if (!strcmp(name, "wgrad_xcd")) { vfs_option_wgrad_xcd = value; return VFS_OK; }
-  if (!strcmp(name, "halo_deep_max")) { vfs_option_halo_deep_max = value; return VFS_OK; }
-  if (!strcmp(name, "halo_xcd")) { vfs_option_halo_xcd = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_ring_fbn")) { vfs_option_igemm_ring_fbn = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_ring_mfma32")) { vfs_option_igemm_ring_mfma32 = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_ring_gather")) { vfs_option_igemm_ring_gather = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_skinny")) { vfs_option_igemm_skinny = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_pw")) { vfs_option_igemm_pw = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_pw_min_tiles")) { vfs_option_igemm_pw_min_tiles = value; return VFS_OK; }
-  if (!strcmp(name, "igemm_ring_upfront")) { vfs_option_igemm_ring_upfront = value; return VFS_OK; }
+  for (const auto& o : g_options) {
+    if (strcmp(name, o.name)) continue;
+    if (o.var == &vfs_option_bn_chunk_rows) value = value > 0 ? value : 64;
+    if (o.var == &vfs_option_lp2_cap) value = value <= 0 ? 0 : (value < 16 ? 16 : value);
+    *o.var = value;
+    return VFS_OK;
+  }
   return vfs_set_error(VFS_ERR_ARG, "vfs_set_option: unknown option");
 }
 
 int vfs_imgs_to_nhwc4(const float* imgs, vfs_bf16* out, int B, int V, int T, int H, int W, int Wp, vfs_stream_t stream) {
   if (Wp < W || (Wp & 1)) return vfs_set_error(VFS_ERR_SHAPE, "imgs_to_nhwc4: Wp must be even and >= W");
-  return vfs_imgs_to_nhwc4_launch(imgs, out, B, V, T, H, W, Wp, S(stream));
+  return vfs_imgs_to_nhwc4_launch(imgs, out, B, V, T, H, W, Wp, stream_of(stream));
 }
 
 int vfs_pack_weights(const void* desc, int ntensors, long long total, vfs_stream_t stream) {
-  return vfs_pack_weights_launch((const PackDesc*)desc, ntensors, total, S(stream));
+  return vfs_pack_weights_launch((const PackDesc*)desc, ntensors, total, stream_of(stream));
 }
 
 int vfs_conv_fwd(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, int N, int H, int W,
                  int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, vfs_stream_t stream) {
-  ConvArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.src = x; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = bias; a.stats = stats; a.Cout = Cout; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
-  return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  const ConvArgs a = conv_fwd_args(x, wf, y, bias, stats, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
+  return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 int vfs_conv_fwd_coarse(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, float* stats_coarse,
                         uint32_t* tickets, int coarse_log2, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
                         int stride, int pad, vfs_stream_t stream) {
   if (!stats || !stats_coarse || !tickets || coarse_log2 < 1 || coarse_log2 > 8)
     return vfs_set_error(VFS_ERR_ARG, "conv_fwd_coarse: stats, stats_coarse, tickets and 1 <= coarse_log2 <= 8");
-  ConvArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.src = x; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = bias; a.stats = stats; a.Cout = Cout; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
+  ConvArgs a = conv_fwd_args(x, wf, y, bias, stats, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   a.stats_coarse = stats_coarse; a.stats_tickets = tickets; a.coarse_log2 = coarse_log2;
-  return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 int vfs_conv_fwd_dilated(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, int N, int H, int W,
                          int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int dilation, vfs_stream_t stream) {
   if (dilation < 1) return vfs_set_error(VFS_ERR_ARG, "conv_fwd_dilated: dilation >= 1");
   if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 || Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1)
     return vfs_set_error(VFS_ERR_SHAPE, "conv_fwd_dilated: output size does not match (H + 2 pad - dilation (K - 1) - 1) / stride + 1");
-  ConvArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
+  ConvArgs a = conv_fwd_args(x, wf, y, bias, stats, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   a.g.dil = dilation;
-  a.src = x; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = bias; a.stats = stats; a.Cout = Cout; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
-  return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 int vfs_conv_fwd_splitk(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, float* ks_ws, int ksplit,
                         int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                         vfs_stream_t stream) {
   if (ksplit < 1 || (ksplit > 1 && !ks_ws)) return vfs_set_error(VFS_ERR_ARG, "conv_fwd_splitk: workspace");
-  ConvArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.src = x; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = bias; a.stats = stats; a.Cout = Cout; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
+  ConvArgs a = conv_fwd_args(x, wf, y, bias, stats, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   a.ks_ws = ks_ws; a.ksplit = ksplit;
-  return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 int vfs_conv_dgrad_splitk(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, float* ks_ws, int ksplit, int N,
                           int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                           vfs_stream_t stream) {
   if (ksplit < 1 || (ksplit > 1 && !ks_ws)) return vfs_set_error(VFS_ERR_ARG, "conv_dgrad_splitk: workspace");
   if (stride != 1) return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad_splitk: stride 1 only");
-  ConvArgs a;
-  a.g = make_geom(N, Ho, Wo, Cout, H, W, KH, KW, stride, pad, KH * KW * Cout);
-  a.src = dy; a.wgt = wd; a.out = dx; a.add = add; a.bias = nullptr; a.stats = nullptr; a.Cout = Cin; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
+  ConvArgs a = conv_dgrad_args(dy, wd, dx, add, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   a.ks_ws = ks_ws; a.ksplit = ksplit;
-  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
 }
 int vfs_conv_fwd_bnin(const vfs_bf16* x_raw, const float* in_bnp, int in_npg, const vfs_bf16* wf, vfs_bf16* y, const float* bias,
                       float* stats, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                       vfs_stream_t stream) {
   if (!in_bnp || in_npg <= 0) return vfs_set_error(VFS_ERR_ARG, "conv_fwd_bnin: BatchNorm parameters of the input");
-  ConvArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.src = x_raw; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = bias; a.stats = stats; a.Cout = Cout; a.bn = BnBwdFuse{};
+  ConvArgs a = conv_fwd_args(x_raw, wf, y, bias, stats, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   a.in_bnp = in_bnp; a.in_npg = in_npg;
   const bool smallw = vfs_small_map(H, W);
   // round 6: also the 1x1 / stride-1 forward of the implicit-GEMM kernel (the conv2 -> conv3 edge), groups of whole 128-pixel tiles
   const bool pw = KH * KW == 1 && stride == 1 && pad == 0 && H == Ho && W == Wo && Cin % 64 == 0 && ((long long)in_npg * H * W) % 128 == 0;
-  if (pw) return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  if (pw) return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
   if (!vfs_option_halo || Cin % 64 || (size_t)N * H * W * Cin * 2 >= 0xFFFFFFF0ull || !vfs_conv_halo_eligible(a, GATHER_FWD) ||
       (smallw && in_npg % 2))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_fwd_bnin: the 3x3/stride-1 halo-tile kernel and the 1x1/stride-1 kernel fold the input BatchNorm");
-  return vfs_conv_igemm_dispatch(a, GATHER_FWD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 
 int vfs_stem_fwd(const vfs_bf16* x4, const vfs_bf16* wf, vfs_bf16* y, float* stats, int N, int H, int Wp, int Ho, int Wo,
                  vfs_stream_t stream) {
   if (Wp & 1) return vfs_set_error(VFS_ERR_SHAPE, "stem_fwd: padded width must be even");
-  ConvArgs a;
-  a.g = make_geom(N, H, Wp, 4, Ho, Wo, 7, 7, 2, 3, 256);
-  a.src = x4; a.wgt = wf; a.out = y; a.add = nullptr; a.bias = nullptr; a.stats = stats; a.Cout = 64; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
-  if (vfs_option_stem_direct && (size_t)N * H * Wp * 8 < 0xFFFFFFF0ull) return vfs_stem_fwd_direct_launch(a, S(stream));
-  return vfs_conv_igemm_dispatch(a, GATHER_STEM, S(stream));
+  ConvArgs a = conv_fwd_args(x4, wf, y, nullptr, stats, N, H, Wp, 4, Ho, Wo, 64, 7, 7, 2, 3);
+  a.g.Ktot = 256;      // 8 x 8 x 4: the taps and channels as the stem gather pads them (vfs_conv.h, GATHER_STEM)
+  if (vfs_option_stem_direct && (size_t)N * H * Wp * 8 < 0xFFFFFFF0ull) return vfs_stem_fwd_direct_launch(a, stream_of(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_STEM, stream_of(stream));
 }
 
-static int set_add_mask(ConvArgs& a, const vfs_bf16* add, const uint8_t* add_mask, int N, int H, int W, int Cin) {
-  if (!add_mask) return VFS_OK;
-  if (!add || Cin % 64) return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad: add_mask needs an add operand and Cin % 64 == 0");
-  a.add_mask = add_mask; a.add_rows = (long long)N * H * W;
-  return VFS_OK;
-}
 int vfs_conv_dgrad_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, const uint8_t* add_mask, int N,
                            int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, vfs_stream_t stream) {
-  // gather source = dy [N,Ho,Wo,Cout]; destination grid = dx [N,H,W,Cin]
-  ConvArgs a;
-  a.g = make_geom(N, Ho, Wo, Cout, H, W, KH, KW, stride, pad, KH * KW * Cout);
-  a.src = dy; a.wgt = wd; a.out = dx; a.add = add; a.bias = nullptr; a.stats = nullptr; a.Cout = Cin; a.bn = BnBwdFuse{};
-  a.in_bnp = nullptr; a.in_npg = 0;
+  ConvArgs a = conv_dgrad_args(dy, wd, dx, add, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   if (int rc = set_add_mask(a, add, add_mask, N, H, W, Cin)) return rc;
-  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
 }
 int vfs_conv_dgrad(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int N, int H, int W, int Cin,
                    int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, vfs_stream_t stream) {
@@ -208,10 +292,7 @@ int vfs_conv_dgrad_bn_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* 
   if (stride != 1) return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad_bn: stride 1 only (strided dgrads run per parity class)");
   if (!bn_x || !bnp || !bn_partial || bn_mpg <= 0) return vfs_set_error(VFS_ERR_ARG, "conv_dgrad_bn: null statistics operand");
   const long long M = (long long)N * H * W;
-  ConvArgs a;
-  a.g = make_geom(N, Ho, Wo, Cout, H, W, KH, KW, stride, pad, KH * KW * Cout);
-  a.src = dy; a.wgt = wd; a.out = dx; a.add = add; a.bias = nullptr; a.stats = nullptr; a.Cout = Cin;
-  a.in_bnp = nullptr; a.in_npg = 0;
+  ConvArgs a = conv_dgrad_args(dy, wd, dx, add, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   if (int rc = set_add_mask(a, add, add_mask, N, H, W, Cin)) return rc;
   a.bn.x = bn_x; a.bn.y = bn_y; a.bn.bnp = bnp; a.bn.partial = bn_partial; a.bn.mpg = bn_mpg; a.bn.relu = bn_relu;
   // a statistics row must belong to ONE group: spatial tiles never straddle images (halo kernels: groups of whole
@@ -219,7 +300,7 @@ int vfs_conv_dgrad_bn_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* 
   const bool tiles = vfs_option_halo && Cout % 64 == 0 && vfs_conv_halo_eligible(a, GATHER_DGRAD);
   if (bn_mpg < M && (tiles ? bn_mpg % ((long long)H * W) != 0 : bn_mpg % 128 != 0))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad_bn: groups must be whole images (tile kernels) / multiples of 128 pixels");
-  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, S(stream));
+  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
 }
 int vfs_conv_dgrad_bn(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, const vfs_bf16* bn_x,
                       const vfs_bf16* bn_y, const float* bnp, float* bn_partial, int bn_mpg, int bn_relu, int N, int H, int W,
@@ -230,45 +311,31 @@ int vfs_conv_dgrad_bn(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, cons
 
 int vfs_conv_wgrad(const vfs_bf16* dy, const vfs_bf16* x, float* partial, float* grad, int N, int H, int W, int Cin, int Ho,
                    int Wo, int Cout, int KH, int KW, int stride, int pad, int nsplit, int pix_per_split, vfs_stream_t stream) {
-  WgradArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.dy = dy; a.x = x; a.partial = partial; a.Cout = Cout; a.pix_per_split = pix_per_split; a.nsplit = nsplit;
-  a.in_bnp = nullptr; a.in_npg = 0;
+  const WgradArgs a = wgrad_args(dy, x, nullptr, 0, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, nsplit, pix_per_split);
   int rc;
   if (vfs_option_halo && vfs_wgrad_halo_eligible(a, GATHER_FWD)) {
-    rc = vfs_wgrad_halo_dispatch(a, S(stream), &nsplit);   // may use fewer splits than offered
+    rc = vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);   // may use fewer splits than offered
   } else {
-    rc = vfs_conv_wgrad_dispatch(a, GATHER_FWD, S(stream));
+    rc = vfs_conv_wgrad_dispatch(a, GATHER_FWD, stream_of(stream));
   }
   if (rc) return rc;
-  if (!grad) {      // the caller reduces the partials later (vfs_wgrad_reduce_table): its table needs the split count it offered
-    if (nsplit != a.nsplit) return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad: deferred reduction needs a split plan the kernel takes as offered");
-    return VFS_OK;
-  }
-  return vfs_wgrad_reduce_launch(partial, grad, nsplit, Cout, a.g.Ktot, Cin, KH, KW, 0, S(stream));
+  return finish_wgrad(a, grad, nsplit, Cin, 0, "conv_wgrad: deferred reduction needs a split plan the kernel takes as offered", stream_of(stream));
 }
 int vfs_conv_wgrad_bnin(const vfs_bf16* dy, const vfs_bf16* x_raw, const float* in_bnp, int in_npg, float* partial, float* grad, int N,
                         int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int nsplit,
                         int pix_per_split, vfs_stream_t stream) {
   if (!in_bnp || in_npg <= 0) return vfs_set_error(VFS_ERR_ARG, "conv_wgrad_bnin: BatchNorm parameters of the input");
-  WgradArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.dy = dy; a.x = x_raw; a.partial = partial; a.Cout = Cout; a.pix_per_split = pix_per_split; a.nsplit = nsplit;
-  a.in_bnp = in_bnp; a.in_npg = in_npg;
+  const WgradArgs a = wgrad_args(dy, x_raw, in_bnp, in_npg, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, nsplit, pix_per_split);
   if (KH * KW == 1 && stride == 1 && pad == 0 && H == Ho && W == Wo) {      // round 6: the 1x1 / stride-1 kernel (register-staged) folds it too
-    int rc1 = vfs_conv_wgrad_dispatch(a, GATHER_FWD, S(stream));
-    if (rc1 || !grad) return rc1;
-    return vfs_wgrad_reduce_launch(partial, grad, nsplit, Cout, a.g.Ktot, Cin, KH, KW, 0, S(stream));
+    int rc1 = vfs_conv_wgrad_dispatch(a, GATHER_FWD, stream_of(stream));
+    if (rc1) return rc1;
+    return finish_wgrad(a, grad, nsplit, Cin, 0, nullptr, stream_of(stream));      // (this kernel takes every plan as offered)
   }
   if (!vfs_option_halo || !vfs_wgrad_halo_eligible(a, GATHER_FWD) || (vfs_small_map(H, W) && in_npg % 2))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad_bnin: the 3x3/stride-1 halo-tile kernel and the 1x1/stride-1 kernel fold the input BatchNorm");
-  int rc = vfs_wgrad_halo_dispatch(a, S(stream), &nsplit);
+  int rc = vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);
   if (rc) return rc;
-  if (!grad) {
-    if (nsplit != a.nsplit) return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad_bnin: deferred reduction needs a split plan the kernel takes as offered");
-    return VFS_OK;
-  }
-  return vfs_wgrad_reduce_launch(partial, grad, nsplit, Cout, a.g.Ktot, Cin, KH, KW, 0, S(stream));
+  return finish_wgrad(a, grad, nsplit, Cin, 0, "conv_wgrad_bnin: deferred reduction needs a split plan the kernel takes as offered", stream_of(stream));
 }
 
 int vfs_wgrad_tickets(void) { return VFS_WGRAD_TICKETS; }
@@ -277,82 +344,75 @@ int vfs_conv_wgrad_inl(const vfs_bf16* dy, const vfs_bf16* x, const float* in_bn
                        int pad, int nsplit, int pix_per_split, vfs_stream_t stream) {
   if (!grad || !tickets || !partial) return vfs_set_error(VFS_ERR_ARG, "conv_wgrad_inl: partial, grad and tickets must be given");
   if (in_bnp && in_npg <= 0) return vfs_set_error(VFS_ERR_ARG, "conv_wgrad_inl: images per BatchNorm group of the input");
-  WgradArgs a;
-  a.g = make_geom(N, H, W, Cin, Ho, Wo, KH, KW, stride, pad, KH * KW * Cin);
-  a.dy = dy; a.x = x; a.partial = partial; a.Cout = Cout; a.pix_per_split = pix_per_split; a.nsplit = nsplit;
-  a.in_bnp = in_bnp; a.in_npg = in_bnp ? in_npg : 0;
+  WgradArgs a = wgrad_args(dy, x, in_bnp, in_bnp ? in_npg : 0, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, nsplit, pix_per_split);
   a.grad = grad; a.tickets = tickets;
   if (vfs_option_halo && vfs_wgrad_halo_eligible(a, GATHER_FWD) && !(in_bnp && vfs_small_map(H, W) && in_npg % 2))
-    return vfs_wgrad_halo_dispatch(a, S(stream), &nsplit);
+    return vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);
   if (in_bnp) return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad_inl: only the 3x3/stride-1 halo-tile kernel folds the input BatchNorm");
-  return vfs_conv_wgrad_dispatch(a, GATHER_FWD, S(stream));
+  return vfs_conv_wgrad_dispatch(a, GATHER_FWD, stream_of(stream));
 }
 
 int vfs_stem_wgrad(const vfs_bf16* dy, const vfs_bf16* x4, float* partial, float* grad, int N, int H, int Wp, int Ho, int Wo,
                    int nsplit, int pix_per_split, vfs_stream_t stream) {
-  WgradArgs a;
-  a.g = make_geom(N, H, Wp, 4, Ho, Wo, 7, 7, 2, 3, 256);
-  a.dy = dy; a.x = x4; a.partial = partial; a.Cout = 64; a.pix_per_split = pix_per_split; a.nsplit = nsplit;
-  int rc = vfs_conv_wgrad_dispatch(a, GATHER_STEM, S(stream));
-  if (rc || !grad) return rc;
-  return vfs_wgrad_reduce_launch(partial, grad, nsplit, 64, 256, 3, 7, 7, 1, S(stream));
+  WgradArgs a = wgrad_args(dy, x4, nullptr, 0, partial, N, H, Wp, 4, Ho, Wo, 64, 7, 7, 2, 3, nsplit, pix_per_split);
+  a.g.Ktot = 256;      // (as vfs_stem_fwd)
+  int rc = vfs_conv_wgrad_dispatch(a, GATHER_STEM, stream_of(stream));
+  if (rc) return rc;
+  return finish_wgrad(a, grad, nsplit, 3, 1, nullptr, stream_of(stream));      // (this kernel takes every plan as offered)
 }
 
 int vfs_wgrad_reduce_table(const void* desc, int nrecords, int total_blocks, vfs_stream_t stream) {
   if (nrecords > 0 && !desc) return vfs_set_error(VFS_ERR_ARG, "wgrad_reduce_table: null table");
-  return vfs_wgrad_reduce_table_launch((const WgradReduceDesc*)desc, nrecords, total_blocks, S(stream));
+  return vfs_wgrad_reduce_table_launch((const WgradReduceDesc*)desc, nrecords, total_blocks, stream_of(stream));
 }
 
 int vfs_bias_grad(const vfs_bf16* dy, float* db, int M, int C, vfs_stream_t stream) {
-  return vfs_bias_grad_launch(dy, db, M, C, S(stream));
+  return vfs_bias_grad_launch(dy, db, M, C, stream_of(stream));
 }
 
 int vfs_bn_reduce_partials(const float* partial, double* sums, double* scratch, int G, int bpg, int C, vfs_stream_t stream) {
-  return vfs_bn_reduce_partials_launch(partial, sums, scratch, G, bpg, C, S(stream));
+  return vfs_bn_reduce_partials_launch(partial, sums, scratch, G, bpg, C, stream_of(stream));
 }
 int vfs_bn_finalize(const double* sums, const float* gamma, const float* beta, float* bnp, float* running_mean,
                     float* running_var, int G, int C, double count, float eps, float momentum, vfs_stream_t stream) {
-  return vfs_bn_finalize_launch(sums, gamma, beta, bnp, running_mean, running_var, G, C, count, eps, momentum, S(stream));
+  return vfs_bn_finalize_launch(sums, gamma, beta, bnp, running_mean, running_var, G, C, count, eps, momentum, stream_of(stream));
 }
 int vfs_bn_stats_finalize(const float* partial, double* sums, double* scratch, const float* gamma, const float* beta, float* bnp,
                           float* running_mean, float* running_var, int G, int bpg, int C, double count, float eps, float momentum,
                           vfs_stream_t stream) {
   return vfs_bn_reduce_fused_launch(0, partial, sums, scratch, G, bpg, C, gamma, beta, bnp, running_mean, running_var, count, eps,
-                                    momentum, nullptr, nullptr, S(stream));
+                                    momentum, nullptr, nullptr, stream_of(stream));
 }
 int vfs_bn_stats_raw_finalize(const vfs_bf16* raw, double* sums, const float* gamma, const float* beta, float* bnp, float* running_mean,
                               float* running_var, int G, int rows_per_group, int C, double count, float eps, float momentum,
                               vfs_stream_t stream) {
   if (!raw || !sums || !gamma || !beta || !bnp) return vfs_set_error(VFS_ERR_ARG, "bn_stats_raw_finalize: null buffer");
   return vfs_bn_stats_raw_launch(raw, sums, G, rows_per_group, C, gamma, beta, bnp, running_mean, running_var, count, eps, momentum,
-                                 S(stream));
+                                 stream_of(stream));
 }
 int vfs_linear_bn_act(const vfs_bf16* x, const vfs_bf16* wf, const float* bias, const float* gamma, const float* beta, vfs_bf16* raw,
                       vfs_bf16* act, float* bnp, double* sums, float* running_mean, float* running_var, int M, int K, int C, int mpg,
                       int relu, double count, float eps, float momentum, vfs_stream_t stream) {
   if (!x || !wf || !gamma || !beta || !raw || !act || !bnp || !sums) return vfs_set_error(VFS_ERR_ARG, "linear_bn_act: null buffer");
   if (mpg <= 0 || M % mpg) return vfs_set_error(VFS_ERR_SHAPE, "linear_bn_act: M % mpg");
-  LinBnArgs a;
+  LinBnArgs a{};
   a.x = x; a.w = wf; a.bias = bias; a.gamma = gamma; a.beta = beta; a.raw = raw; a.act = act; a.bnp = bnp; a.sums = sums;
   a.rm = running_mean; a.rv = running_var; a.M = M; a.K = K; a.C = C; a.G = M / mpg; a.mpg = mpg; a.relu = relu; a.count = count;
   a.eps = eps; a.momentum = momentum;
-  return vfs_linear_bn_act_launch(a, S(stream));
+  return vfs_linear_bn_act_launch(a, stream_of(stream));
 }
 int vfs_bn_bwd_sums_paramgrad(const float* partial, double* sums, double* scratch, float* dgamma, float* dbeta, int G, int bpg,
                               int C, vfs_stream_t stream) {
   return vfs_bn_reduce_fused_launch(1, partial, sums, scratch, G, bpg, C, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 0.f, 0.f,
-                                    dgamma, dbeta, S(stream));
+                                    dgamma, dbeta, stream_of(stream));
 }
 int vfs_bn_eval_params(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float* bnp,
                        int C, float eps, vfs_stream_t stream) {
-  return vfs_bn_eval_params_launch(gamma, beta, running_mean, running_var, bnp, C, eps, S(stream));
+  return vfs_bn_eval_params_launch(gamma, beta, running_mean, running_var, bnp, C, eps, stream_of(stream));
 }
 int vfs_bn_act_mask(const vfs_bf16* x, const float* bnp, const vfs_bf16* res, const vfs_bf16* rres, const float* rbnp, vfs_bf16* y,
                     uint8_t* mask_bits, long long M, int C, int mpg, int relu, vfs_stream_t stream) {
-  BnActArgs a;
-  a.x = x; a.bnp = bnp; a.res = res; a.rres = rres; a.rbnp = rbnp; a.y = y; a.M = M; a.C = C; a.mpg = mpg; a.relu = relu;
-  a.mbits = mask_bits;
-  return vfs_bn_act_launch(a, S(stream));
+  return vfs_bn_act_launch(bn_act_args(x, bnp, res, rres, rbnp, y, mask_bits, M, C, mpg, relu), stream_of(stream));
 }
 int vfs_bn_act(const vfs_bf16* x, const float* bnp, const vfs_bf16* res, const vfs_bf16* rres, const float* rbnp, vfs_bf16* y,
                long long M, int C, int mpg, int relu, vfs_stream_t stream) {
@@ -363,56 +423,35 @@ int vfs_bn_act_fin_mask(const vfs_bf16* x, const float* partial, int bpg, const 
                         uint8_t* mask_bits, long long M, int C, int mpg, int relu, double count, float eps, float momentum,
                         vfs_stream_t stream) {
   if (mpg <= 0 || M % mpg) return vfs_set_error(VFS_ERR_SHAPE, "bn_act_fin: M % mpg");
-  BnActArgs a;
-  a.x = x; a.bnp = bnp; a.res = res; a.rres = rres; a.rbnp = rbnp; a.y = y; a.M = M; a.C = C; a.mpg = mpg; a.relu = relu;
-  a.mbits = mask_bits;
-  BnFin f;
-  f.partial = partial; f.bpg = bpg; f.G = (int)(M / mpg); f.gamma = gamma; f.beta = beta; f.bnp = bnp; f.sums = sums;
-  f.running_mean = running_mean; f.running_var = running_var; f.count = count; f.eps = eps; f.momentum = momentum;
-  return vfs_bn_act_fin_launch(a, f, S(stream));
-}
-static P2PTail make_tail(const void* peers, int rank, int world, void* state, long long spin_limit) {
-  P2PTail x;
-  x.peers = (void* const*)peers; x.rank = rank; x.world = world; x.state = (unsigned long long*)state;
-  x.spin_limit = (unsigned long long)(spin_limit < 1 ? 1 : spin_limit);
-  return x;
+  const BnActArgs a = bn_act_args(x, bnp, res, rres, rbnp, y, mask_bits, M, C, mpg, relu);
+  const BnFin f = bn_fin_fwd(partial, bpg, (int)(M / mpg), gamma, beta, bnp, sums, running_mean, running_var, count, eps, momentum);
+  return vfs_bn_act_fin_launch(a, f, stream_of(stream));
 }
 int vfs_bn_act_fin_xchg(const vfs_bf16* x, const float* partial, int bpg, const float* gamma, const float* beta, float* bnp, double* sums,
                         float* running_mean, float* running_var, const vfs_bf16* res, const vfs_bf16* rres, const float* rbnp, vfs_bf16* y,
                         uint8_t* mask_bits, long long M, int C, int mpg, int relu, double count, float eps, float momentum,
                         const void* peers, int rank, int world, void* state, long long spin_limit, int seq, vfs_stream_t stream) {
   if (mpg <= 0 || M % mpg) return vfs_set_error(VFS_ERR_SHAPE, "bn_act_fin_xchg: M % mpg");
-  if (seq < 0 || seq >= 4095) return vfs_set_error(VFS_ERR_ARG, "bn_act_fin_xchg: 0 <= seq < 4095");
-  if (!peers || !state || !partial) return vfs_set_error(VFS_ERR_ARG, "bn_act_fin_xchg: statistics rows, peers and state must be given");
-  BnActArgs a;
-  a.x = x; a.bnp = bnp; a.res = res; a.rres = rres; a.rbnp = rbnp; a.y = y; a.M = M; a.C = C; a.mpg = mpg; a.relu = relu;
-  a.mbits = mask_bits;
-  BnFin f;
-  f.partial = partial; f.bpg = bpg; f.G = (int)(M / mpg); f.gamma = gamma; f.beta = beta; f.bnp = bnp; f.sums = sums;
-  f.running_mean = running_mean; f.running_var = running_var; f.count = count; f.eps = eps; f.momentum = momentum;
-  f.x = make_tail(peers, rank, world, state, spin_limit);
-  f.x.seq = seq;
-  return vfs_bn_act_fin_launch(a, f, S(stream));
+  if (int rc = xchg_check("bn_act_fin_xchg", seq, peers, state, partial)) return rc;
+  const BnActArgs a = bn_act_args(x, bnp, res, rres, rbnp, y, mask_bits, M, C, mpg, relu);
+  BnFin f = bn_fin_fwd(partial, bpg, (int)(M / mpg), gamma, beta, bnp, sums, running_mean, running_var, count, eps, momentum);
+  f.x = make_tail(peers, rank, world, state, spin_limit, seq);
+  return vfs_bn_act_fin_launch(a, f, stream_of(stream));
 }
 int vfs_bn_bwd_apply_fin_xchg(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, const float* partial, int bpg,
                               double* sums, float* dgamma, float* dbeta, vfs_bf16* dx, vfs_bf16* gm, long long M, int C, int mpg,
                               double count, int relu, const void* peers, int rank, int world, void* state, long long spin_limit,
                               int seq, vfs_stream_t stream) {
   if (mpg <= 0 || M % mpg) return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_apply_fin_xchg: M % mpg");
-  if (seq < 0 || seq >= 4095) return vfs_set_error(VFS_ERR_ARG, "bn_bwd_apply_fin_xchg: 0 <= seq < 4095");
-  if (!peers || !state || !partial) return vfs_set_error(VFS_ERR_ARG, "bn_bwd_apply_fin_xchg: statistics rows, peers and state must be given");
-  BnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.dx = dx; a.gm = gm; a.M = M; a.C = C; a.mpg = mpg; a.count = count; a.relu = relu;
-  BnFin f;
-  f.partial = partial; f.bpg = bpg; f.G = (int)(M / mpg); f.sums = sums; f.dgamma = dgamma; f.dbeta = dbeta;
-  f.x = make_tail(peers, rank, world, state, spin_limit);
-  f.x.seq = seq;
-  return vfs_bn_bwd_apply_fin_launch(a, f, S(stream));
+  if (int rc = xchg_check("bn_bwd_apply_fin_xchg", seq, peers, state, partial)) return rc;
+  const BnBwdArgs a = bn_bwd_args(g, y, x, bnp, dx, gm, M, C, mpg, count, relu);
+  BnFin f = bn_fin_bwd(partial, bpg, (int)(M / mpg), sums, dgamma, dbeta);
+  f.x = make_tail(peers, rank, world, state, spin_limit, seq);
+  return vfs_bn_bwd_apply_fin_launch(a, f, stream_of(stream));
 }
 int vfs_p2p_chain_start(void* state, vfs_stream_t stream) {
   if (!state) return vfs_set_error(VFS_ERR_ARG, "p2p_chain_start: null state");
-  return vfs_p2p_chain_start_launch((unsigned long long*)state, S(stream));
+  return vfs_p2p_chain_start_launch((unsigned long long*)state, stream_of(stream));
 }
 int vfs_bn_act_fin(const vfs_bf16* x, const float* partial, int bpg, const float* gamma, const float* beta, float* bnp, double* sums,
                    float* running_mean, float* running_var, const vfs_bf16* res, const vfs_bf16* rres, const float* rbnp, vfs_bf16* y,
@@ -422,42 +461,36 @@ int vfs_bn_act_fin(const vfs_bf16* x, const float* partial, int bpg, const float
 }
 int vfs_bn_relu_maxpool(const vfs_bf16* x, const float* bnp, vfs_bf16* y, uint8_t* idx, vfs_bf16* xpool, int N, int H, int W, int C,
                         int Hp, int Wp, int npg, vfs_stream_t stream) {
-  BnPoolArgs a;
+  BnPoolArgs a{};
   a.x = x; a.bnp = bnp; a.y = y; a.idx = idx; a.xpool = xpool; a.N = N; a.H = H; a.W = W; a.C = C; a.Hp = Hp; a.Wp = Wp; a.npg = npg;
-  return vfs_bn_relu_maxpool_launch(a, S(stream));
+  return vfs_bn_relu_maxpool_launch(a, stream_of(stream));
 }
 int vfs_maxpool_relu_bwd(const vfs_bf16* gp, const vfs_bf16* yp, const uint8_t* idx, vfs_bf16* ga, int N, int H, int W, int C,
                          int Hp, int Wp, vfs_stream_t stream) {
-  PoolBwdArgs a;
+  PoolBwdArgs a{};
   a.gp = gp; a.yp = yp; a.idx = idx; a.ga = ga; a.N = N; a.H = H; a.W = W; a.C = C; a.Hp = Hp; a.Wp = Wp;
-  return vfs_maxpool_relu_bwd_launch(a, S(stream));
+  return vfs_maxpool_relu_bwd_launch(a, stream_of(stream));
 }
 int vfs_bn_bwd_reduce(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, float* partial, long long M,
                       int C, int mpg, int ppb, int relu, vfs_stream_t stream) {
   if (ppb <= 0 || mpg % ppb) return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_reduce: pixels-per-group % pixels-per-block");
-  BnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.partial = partial; a.M = M; a.C = C; a.mpg = mpg; a.ppb = ppb; a.relu = relu;
-  return vfs_bn_bwd_reduce_launch(a, (int)((M + ppb - 1) / ppb), S(stream));
+  BnBwdArgs a = bn_bwd_args(g, y, x, bnp, nullptr, nullptr, M, C, mpg, 0.0, relu);
+  a.partial = partial; a.ppb = ppb;
+  return vfs_bn_bwd_reduce_launch(a, (int)((M + ppb - 1) / ppb), stream_of(stream));
 }
 int vfs_bn_bwd_apply(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, const double* sums,
                      vfs_bf16* dx, vfs_bf16* gm, long long M, int C, int mpg, double count, int relu, vfs_stream_t stream) {
-  BnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.sums = sums; a.dx = dx; a.gm = gm; a.M = M; a.C = C; a.mpg = mpg; a.count = count;
-  a.relu = relu;
-  return vfs_bn_bwd_apply_launch(a, S(stream));
+  BnBwdArgs a = bn_bwd_args(g, y, x, bnp, dx, gm, M, C, mpg, count, relu);
+  a.sums = sums;
+  return vfs_bn_bwd_apply_launch(a, stream_of(stream));
 }
 int vfs_bn_bwd_apply_fin(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, const float* partial, int bpg,
                          double* sums, float* dgamma, float* dbeta, vfs_bf16* dx, vfs_bf16* gm, long long M, int C, int mpg,
                          double count, int relu, vfs_stream_t stream) {
   if (mpg <= 0 || M % mpg) return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_apply_fin: M % mpg");
-  BnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.dx = dx; a.gm = gm; a.M = M; a.C = C; a.mpg = mpg; a.count = count; a.relu = relu;
-  BnFin f;
-  f.partial = partial; f.bpg = bpg; f.G = (int)(M / mpg); f.sums = sums; f.dgamma = dgamma; f.dbeta = dbeta;
-  return vfs_bn_bwd_apply_fin_launch(a, f, S(stream));
+  const BnBwdArgs a = bn_bwd_args(g, y, x, bnp, dx, gm, M, C, mpg, count, relu);
+  const BnFin f = bn_fin_bwd(partial, bpg, (int)(M / mpg), sums, dgamma, dbeta);
+  return vfs_bn_bwd_apply_fin_launch(a, f, stream_of(stream));
 }
 int vfs_bn_bwd_apply_raw(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x, const float* bnp, double* sums, float* dgamma,
                          float* dbeta, vfs_bf16* dx, vfs_bf16* gm, long long M, int C, int mpg, double count, int relu,
@@ -466,13 +499,10 @@ int vfs_bn_bwd_apply_raw(const vfs_bf16* g, const vfs_bf16* y, const vfs_bf16* x
   int gcd = mpg, r = 512;      // ONE statistics row per group: the shapes the two-launch form serves with ppb == mpg (gcd(mpg, 512) == mpg or < 16)
   while (r) { const int q = gcd % r; gcd = r; r = q; }
   if (mpg > 512 || !(gcd == mpg || gcd < 16)) return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_apply_raw: one statistics row per group (mpg <= 512 and gcd(mpg, 512) == mpg or < 16)");
-  const int ppb = mpg;
-  BnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = g; a.y = y; a.x = x; a.bnp = bnp; a.dx = dx; a.gm = gm; a.M = M; a.C = C; a.mpg = mpg; a.ppb = ppb; a.count = count; a.relu = relu;
-  BnFin f;
-  f.partial = nullptr; f.bpg = 1; f.G = (int)(M / mpg); f.sums = sums; f.dgamma = dgamma; f.dbeta = dbeta;
-  return vfs_bn_bwd_apply_raw_launch(a, f, S(stream));
+  BnBwdArgs a = bn_bwd_args(g, y, x, bnp, dx, gm, M, C, mpg, count, relu);
+  a.ppb = mpg;
+  const BnFin f = bn_fin_bwd(nullptr, 1, (int)(M / mpg), sums, dgamma, dbeta);
+  return vfs_bn_bwd_apply_raw_launch(a, f, stream_of(stream));
 }
 int vfs_stem_pool_bn_bwd_reduce(const vfs_bf16* gp, const vfs_bf16* yp, const uint8_t* idx, const vfs_bf16* x, const vfs_bf16* xpool,
                                 const float* bnp, float* partial, int N, int H, int W, int C, int Hp, int Wp, int npg, int ppb,
@@ -480,83 +510,74 @@ int vfs_stem_pool_bn_bwd_reduce(const vfs_bf16* gp, const vfs_bf16* yp, const ui
   const long long mpg = (long long)npg * Hp * Wp;
   if (ppb <= 0 || mpg % ppb) return vfs_set_error(VFS_ERR_SHAPE, "stem_pool_bn_bwd_reduce: pooled pixels per group % ppb");
   if (!gp || !idx || !bnp || !partial || (!x && !xpool) || (!xpool && !yp)) return vfs_set_error(VFS_ERR_ARG, "stem_pool_bn_bwd_reduce: null buffer");
-  StemBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gp = gp; a.yp = yp; a.idx = idx; a.x = x; a.xp = xpool; a.bnp = bnp; a.partial = partial;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Hp = Hp; a.Wp = Wp; a.npg = npg; a.ppb = ppb;
+  StemBwdArgs a = stem_bwd_args(gp, yp, idx, x, bnp, N, H, W, C, Hp, Wp, npg);
+  a.xp = xpool; a.partial = partial; a.ppb = ppb;
   const long long P = (long long)N * Hp * Wp;
-  return vfs_stem_pool_bn_bwd_reduce_launch(a, (int)((P + ppb - 1) / ppb), S(stream));
+  return vfs_stem_pool_bn_bwd_reduce_launch(a, (int)((P + ppb - 1) / ppb), stream_of(stream));
 }
 int vfs_stem_pool_bn_bwd_apply(const vfs_bf16* gp, const vfs_bf16* yp, const uint8_t* idx, const vfs_bf16* x, const float* bnp,
                                const double* sums, vfs_bf16* dx, int N, int H, int W, int C, int Hp, int Wp, int npg,
                                double count, vfs_stream_t stream) {
-  StemBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gp = gp; a.yp = yp; a.idx = idx; a.x = x; a.bnp = bnp; a.sums = sums; a.dx = dx;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Hp = Hp; a.Wp = Wp; a.npg = npg; a.count = count;
-  return vfs_stem_pool_bn_bwd_apply_launch(a, S(stream));
+  StemBwdArgs a = stem_bwd_args(gp, yp, idx, x, bnp, N, H, W, C, Hp, Wp, npg);
+  a.sums = sums; a.dx = dx; a.count = count;
+  return vfs_stem_pool_bn_bwd_apply_launch(a, stream_of(stream));
 }
 int vfs_stem_wgrad_fused(const vfs_bf16* x4, const vfs_bf16* xraw, const vfs_bf16* gp, const vfs_bf16* yp, const uint8_t* idx,
                          const float* bnp, const double* sums, float* partial, float* grad, int N, int Hin, int Win, int Ho,
                          int Wo, int Hp, int Wp, int npg, double count, int nblocks, vfs_stream_t stream) {
-  StemBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gp = gp; a.yp = yp; a.idx = idx; a.x = xraw; a.bnp = bnp; a.sums = sums;
-  a.N = N; a.H = Ho; a.W = Wo; a.C = 64; a.Hp = Hp; a.Wp = Wp; a.npg = npg; a.count = count;
+  StemBwdArgs a = stem_bwd_args(gp, yp, idx, xraw, bnp, N, Ho, Wo, 64, Hp, Wp, npg);
+  a.sums = sums; a.count = count;
   if ((size_t)N * Hin * Win * 8 >= 0xFFFFFFF0ull) return vfs_set_error(VFS_ERR_SHAPE, "stem_wgrad_fused: input >= 4 GiB");
-  int rc = vfs_stem_wgrad_fused_launch(a, x4, Hin, Win, partial, nblocks, S(stream));
+  int rc = vfs_stem_wgrad_fused_launch(a, x4, Hin, Win, partial, nblocks, stream_of(stream));
   if (rc || !grad) return rc;
-  return vfs_wgrad_reduce_launch(partial, grad, nblocks, 64, 224, 3, 7, 7, 1, S(stream));
+  return vfs_wgrad_reduce_launch(partial, grad, nblocks, 64, 224, 3, 7, 7, 1, stream_of(stream));
 }
 int vfs_bn_param_grad(const double* sums, float* dgamma, float* dbeta, int G, int C, vfs_stream_t stream) {
-  return vfs_bn_param_grad_launch(sums, dgamma, dbeta, G, C, S(stream));
+  return vfs_bn_param_grad_launch(sums, dgamma, dbeta, G, C, stream_of(stream));
 }
 
 int vfs_avgpool_fwd(const vfs_bf16* x, vfs_bf16* y, int N, int HW, int C, vfs_stream_t stream) {
-  return vfs_avgpool_fwd_launch(x, y, N, HW, C, S(stream));
+  return vfs_avgpool_fwd_launch(x, y, N, HW, C, stream_of(stream));
 }
 int vfs_avgpool_bwd(const vfs_bf16* g, vfs_bf16* gx, int N, int HW, int C, vfs_stream_t stream) {
-  return vfs_avgpool_bwd_launch(g, gx, N, HW, C, S(stream));
+  return vfs_avgpool_bwd_launch(g, gx, N, HW, C, stream_of(stream));
 }
 
 int vfs_cosine_loss_fwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, float* loss, int N,
                         int C, int T, int K, int negative, float weight, vfs_stream_t stream) {
   if (N % T) return vfs_set_error(VFS_ERR_SHAPE, "cosine_loss: N % T");
-  LossArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p1 = p1; a.z1 = z1; a.p2 = p2; a.z2 = z2; a.loss = loss; a.N = N; a.C = C; a.T = T; a.K = K; a.negative = negative;
-  a.weight = weight;
-  return vfs_cosine_loss_fwd_launch(a, S(stream));
+  LossArgs a = loss_args(p1, z1, p2, z2, N, C, T, K, negative, weight);
+  a.loss = loss;
+  return vfs_cosine_loss_fwd_launch(a, stream_of(stream));
 }
 int vfs_xcorr_fwd(const vfs_bf16* z, const vfs_bf16* x, float* out, int nz, int nx, int Hz, int Wz, int H, int W, int C, float scale,
                   vfs_stream_t stream) {
   if (!z || !x || !out) return vfs_set_error(VFS_ERR_ARG, "xcorr_fwd: null buffer");
-  XcorrArgs a;
+  XcorrArgs a{};
   a.z = z; a.x = x; a.out = out; a.nz = nz; a.nx = nx; a.Hz = Hz; a.Wz = Wz; a.H = H; a.W = W; a.C = C; a.scale = scale;
-  return vfs_xcorr_fwd_launch(a, S(stream));
+  return vfs_xcorr_fwd_launch(a, stream_of(stream));
 }
 int vfs_xcorr_bwd(const vfs_bf16* z, const vfs_bf16* x, const float* g, vfs_bf16* dz, vfs_bf16* dx, int nz, int nx, int Hz, int Wz, int H, int W,
                   int C, float scale, vfs_stream_t stream) {
   if (!z || !x || !g || (!dz && !dx)) return vfs_set_error(VFS_ERR_ARG, "xcorr_bwd: null buffer");
-  XcorrBwdArgs a;
+  XcorrBwdArgs a{};
   a.z = z; a.x = x; a.g = g; a.dz = dz; a.dx = dx; a.nz = nz; a.nx = nx; a.Hz = Hz; a.Wz = Wz; a.H = H; a.W = W; a.C = C; a.scale = scale;
-  return vfs_xcorr_bwd_launch(a, S(stream));
+  return vfs_xcorr_bwd_launch(a, stream_of(stream));
 }
 int vfs_siamfc_loss(const float* responses, const float* labels, float* loss, float* grad, int n, int mode, float param, float scale,
                     vfs_stream_t stream) {
   if (!responses || !labels || !loss) return vfs_set_error(VFS_ERR_ARG, "siamfc_loss: null buffer");
-  return vfs_siamfc_loss_launch(responses, labels, loss, grad, n, mode, param, scale, S(stream));
+  return vfs_siamfc_loss_launch(responses, labels, loss, grad, n, mode, param, scale, stream_of(stream));
 }
 int vfs_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int step, vfs_stream_t stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq) return vfs_set_error(VFS_ERR_ARG, "adam_step: null buffer");
-  return vfs_adam_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, S(stream));
+  return vfs_adam_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, stream_of(stream));
 }
 int vfs_siamfc_crops(const uint8_t* frame, const int* params, float* out, int H, int W, int S, int out_size, vfs_stream_t stream) {
   if (!frame || !params || !out) return vfs_set_error(VFS_ERR_ARG, "siamfc_crops: null buffer");
   if (S < 1 || S > VFS_SIAMFC_MAX_SCALES) return vfs_set_error(VFS_ERR_SHAPE, "siamfc_crops: 1 <= S <= 8");
-  SiamCropArgs a;
-  memset(&a, 0, sizeof(a));
+  SiamCropArgs a{};
   a.frame = frame; a.out = out; a.H = H; a.W = W; a.S = S; a.out_size = out_size;
   for (int i = 0; i < S; ++i) {      // params is HOST memory: it travels as kernel arguments
     const int* p = params + 12 * i;
@@ -565,46 +586,44 @@ int vfs_siamfc_crops(const uint8_t* frame, const int* params, float* out, int H,
     c.fill[0] = p[9]; c.fill[1] = p[10]; c.fill[2] = p[11];
     if (c.valid && c.ow > 0 && c.oh > 0) { c.sx = (double)c.iw / (double)c.ow; c.sy = (double)c.ih / (double)c.oh; }
   }
-  return vfs_siamfc_crops_launch(a, S(stream));
+  return vfs_siamfc_crops_launch(a, stream_of(stream));
 }
 int vfs_siamfc_upsample(const float* responses, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
                         unsigned long long* scale_max, int S, int r, int up, vfs_stream_t stream) {
   if (!responses || !tap_idx || !tap_w || !penalty || !up_out || !scale_max) return vfs_set_error(VFS_ERR_ARG, "siamfc_upsample: null buffer");
   if (((size_t)tap_idx | (size_t)tap_w) & 15) return vfs_set_error(VFS_ERR_ARG, "siamfc_upsample: the tap tables must be 16-byte aligned");
-  return vfs_siamfc_upsample_launch(responses, tap_idx, tap_w, penalty, up_out, scale_max, S, r, up, S(stream));
+  return vfs_siamfc_upsample_launch(responses, tap_idx, tap_w, penalty, up_out, scale_max, S, r, up, stream_of(stream));
 }
 int vfs_siamfc_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
                     float one_minus_wi, double window_influence, vfs_stream_t stream) {
   if (!up_in || !scale_max || !hann || !record) return vfs_set_error(VFS_ERR_ARG, "siamfc_peak: null buffer");
-  return vfs_siamfc_peak_launch(up_in, scale_max, hann, record, S, up, one_minus_wi, window_influence, S(stream));
+  return vfs_siamfc_peak_launch(up_in, scale_max, hann, record, S, up, one_minus_wi, window_influence, stream_of(stream));
 }
 int vfs_loss_means(const float* loss, float* means, int K, int N, vfs_stream_t stream) {
   if (!loss || !means) return vfs_set_error(VFS_ERR_ARG, "loss_means: null buffer");
-  return vfs_loss_means_launch(loss, means, K, N, S(stream));
+  return vfs_loss_means_launch(loss, means, K, N, stream_of(stream));
 }
 int vfs_cosine_loss_bwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, const float* gloss,
                         vfs_bf16* dp1, vfs_bf16* dp2, int N, int C, int T, int K, int negative, float weight,
                         vfs_stream_t stream) {
   if (N % T) return vfs_set_error(VFS_ERR_SHAPE, "cosine_loss: N % T");
-  LossArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p1 = p1; a.z1 = z1; a.p2 = p2; a.z2 = z2; a.gloss = gloss; a.dp1 = dp1; a.dp2 = dp2;
-  a.N = N; a.C = C; a.T = T; a.K = K; a.negative = negative; a.weight = weight;
-  return vfs_cosine_loss_bwd_launch(a, S(stream));
+  LossArgs a = loss_args(p1, z1, p2, z2, N, C, T, K, negative, weight);
+  a.gloss = gloss; a.dp1 = dp1; a.dp2 = dp2;
+  return vfs_cosine_loss_bwd_launch(a, stream_of(stream));
 }
 
 int vfs_bn_reduce_partials_xchg(const float* partial, double* sums, double* scratch, int G, int bpg, int C, const void* peers, int rank,
                                 int world, void* state, long long spin_limit, vfs_stream_t stream) {
   if (!partial || !sums || !peers || !state || spin_limit <= 0) return vfs_set_error(VFS_ERR_ARG, "bn_reduce_partials_xchg: bad argument");
   const P2PTail x = make_tail(peers, rank, world, state, spin_limit);
-  return vfs_bn_reduce_partials_launch(partial, sums, scratch, G, bpg, C, S(stream), &x);
+  return vfs_bn_reduce_partials_launch(partial, sums, scratch, G, bpg, C, stream_of(stream), &x);
 }
 int vfs_bn_bwd_sums_paramgrad_xchg(const float* partial, double* sums, double* scratch, float* dgamma, float* dbeta, int G, int bpg, int C,
                                    const void* peers, int rank, int world, void* state, long long spin_limit, vfs_stream_t stream) {
   if (!partial || !sums || !peers || !state || spin_limit <= 0) return vfs_set_error(VFS_ERR_ARG, "bn_bwd_sums_paramgrad_xchg: bad argument");
   const P2PTail x = make_tail(peers, rank, world, state, spin_limit);
   return vfs_bn_reduce_fused_launch(1, partial, sums, scratch, G, bpg, C, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 0.f, 0.f,
-                                    dgamma, dbeta, S(stream), &x);
+                                    dgamma, dbeta, stream_of(stream), &x);
 }
 int vfs_p2p_window_bytes(long long* bytes, int* max_doubles, int* max_world) {
   if (!bytes || !max_doubles || !max_world) return vfs_set_error(VFS_ERR_ARG, "p2p_window_bytes: null");
@@ -623,75 +642,66 @@ int vfs_p2p_allreduce_f64(double* buf, int n, const void* peers, int rank, int w
                           vfs_stream_t stream) {
   if (!buf || !peers || !state || !(phase & 3) || spin_limit <= 0) return vfs_set_error(VFS_ERR_ARG, "p2p_allreduce_f64: bad argument");
   return vfs_p2p_allreduce_f64_launch(buf, n, reinterpret_cast<void* const*>(peers), rank, world,
-                                      reinterpret_cast<unsigned long long*>(state), phase, (unsigned long long)spin_limit, S(stream));
+                                      reinterpret_cast<unsigned long long*>(state), phase, (unsigned long long)spin_limit, stream_of(stream));
 }
 
 int vfs_simloss_colnorm(const float* x, float* inv, int B, int C, int S, vfs_stream_t stream) {
   if (!x || !inv || B <= 0 || C <= 0 || S <= 0) return vfs_set_error(VFS_ERR_ARG, "simloss_colnorm: bad argument");
-  return vfs_simloss_colnorm_launch(x, inv, B, C, S, S(stream));
+  return vfs_simloss_colnorm_launch(x, inv, B, C, S, stream_of(stream));
 }
 int vfs_simloss_fwd(const float* a, const float* l, const float* inva, const float* invl, const float* mask, float* partial, float* loss,
                     int B, int C, int Sa, int Sl, int pairwise, int negative, float weight, vfs_stream_t stream) {
   if (!a || !l || !partial || !loss || B <= 0 || C <= 0 || Sa <= 0 || Sl <= 0) return vfs_set_error(VFS_ERR_ARG, "simloss_fwd: bad argument");
   if (!pairwise && Sa != Sl) return vfs_set_error(VFS_ERR_SHAPE, "simloss_fwd: non-pairwise operands must have the same positions");
   if (!pairwise && mask) return vfs_set_error(VFS_ERR_ARG, "simloss_fwd: a mask needs pairwise (sim_loss.py:46-47)");
-  return vfs_simloss_fwd_launch(a, l, inva, invl, mask, partial, loss, B, C, Sa, Sl, pairwise, negative, weight, S(stream));
+  return vfs_simloss_fwd_launch(a, l, inva, invl, mask, partial, loss, B, C, Sa, Sl, pairwise, negative, weight, stream_of(stream));
 }
 int vfs_simloss_bwd(const float* other, const float* invo, const float* mask, int mask_transposed, const float* gloss, float* d, int B,
                     int C, int Sself, int Sother, int pairwise, int negative, float weight, vfs_stream_t stream) {
   if (!other || !gloss || !d || B <= 0 || C <= 0 || Sself <= 0 || Sother <= 0) return vfs_set_error(VFS_ERR_ARG, "simloss_bwd: bad argument");
   if (!pairwise && Sself != Sother) return vfs_set_error(VFS_ERR_SHAPE, "simloss_bwd: non-pairwise operands must have the same positions");
-  return vfs_simloss_bwd_launch(other, invo, mask, mask_transposed, gloss, d, B, C, Sself, Sother, pairwise, negative, weight, S(stream));
+  return vfs_simloss_bwd_launch(other, invo, mask, mask_transposed, gloss, d, B, C, Sself, Sother, pairwise, negative, weight, stream_of(stream));
 }
 int vfs_simloss_norm_bwd(const float* x, const float* inv, const float* d, float* dx, int B, int C, int S, vfs_stream_t stream) {
   if (!x || !d || !dx || B <= 0 || C <= 0 || S <= 0) return vfs_set_error(VFS_ERR_ARG, "simloss_norm_bwd: bad argument");
-  return vfs_simloss_norm_bwd_launch(x, inv, d, dx, B, C, S, S(stream));
+  return vfs_simloss_norm_bwd_launch(x, inv, d, dx, B, C, S, stream_of(stream));
 }
 
 int vfs_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
                  float weight_decay, const void* skip_flag, vfs_stream_t stream) {
-  return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, static_cast<const unsigned long long*>(skip_flag), S(stream));
+  return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
 }
-int vfs_scale(float* x, long long n, float scale, vfs_stream_t stream) { return vfs_scale_launch(x, n, scale, S(stream)); }
+int vfs_scale(float* x, long long n, float scale, vfs_stream_t stream) { return vfs_scale_launch(x, n, scale, stream_of(stream)); }
 int vfs_f32_to_bf16(const float* src, vfs_bf16* dst, long long n, float scale, vfs_stream_t stream) {
-  return vfs_f32_to_bf16_launch(src, dst, n, scale, S(stream));
+  return vfs_f32_to_bf16_launch(src, dst, n, scale, stream_of(stream));
 }
-int vfs_bf16_to_f32(const vfs_bf16* src, float* dst, long long n, vfs_stream_t stream) { return vfs_bf16_to_f32_launch(src, dst, n, S(stream)); }
+int vfs_bf16_to_f32(const vfs_bf16* src, float* dst, long long n, vfs_stream_t stream) { return vfs_bf16_to_f32_launch(src, dst, n, stream_of(stream)); }
 
 int vfs_l2norm_rows(const vfs_bf16* x, vfs_bf16* y, long long P, int C, vfs_stream_t stream) {
-  return vfs_l2norm_rows_launch(x, y, P, C, S(stream));
+  return vfs_l2norm_rows_launch(x, y, P, C, stream_of(stream));
 }
 int vfs_labelprop_workspace_bytes(int H, int W, long long* bytes) {
   if (!bytes || H <= 0 || W <= 0) return vfs_set_error(VFS_ERR_ARG, "labelprop_workspace_bytes: bad argument");
-  *bytes = (long long)LP_MAX_SPLIT * H * W * 10 * 8;
+  *bytes = lp_workspace_need(H, W);
   return VFS_OK;
-}
-static int lp_workspace_ok(const void* workspace, long long workspace_bytes, int H, int W) {
-  long long need = 0;
-  if (vfs_labelprop_workspace_bytes(H, W, &need) != VFS_OK) return 0;
-  return workspace != nullptr && workspace_bytes >= need;
 }
 int vfs_labelprop(const vfs_bf16* fbank, const float* sbank, float* out, void* workspace, long long workspace_bytes, int qframe,
                   const int* kslot, int nkeys, int H, int W, int C, int CO, int radius, int non_mask_len, int topk, float temperature,
                   vfs_stream_t stream) {
-  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: 1 <= nkeys <= 64");
-  if (!lp_workspace_ok(workspace, workspace_bytes, H, W))
-    return vfs_set_error(VFS_ERR_ARG, "labelprop: workspace smaller than vfs_labelprop_workspace_bytes(H, W)");
-  if (non_mask_len < 0 || non_mask_len >= nkeys + (radius <= 0)) return vfs_set_error(VFS_ERR_ARG, "labelprop: 0 <= non_mask_len < nkeys");
-  LabelPropArgs a;
+  if (int rc = lp_check("labelprop", nkeys, radius, non_mask_len, true, workspace, workspace_bytes, H, W)) return rc;
+  LabelPropArgs a{};
   a.fbank = fbank; a.sbank = sbank; a.out = out; a.qframe = qframe; a.nkeys = nkeys;
-  a.pval = (float*)workspace;
-  a.pidx = workspace ? (int*)((float*)workspace + (size_t)LP_MAX_SPLIT * H * W * 10) : nullptr;
-  for (int i = 0; i < LP_MAX_KEYS; ++i) a.kslot[i] = i < nkeys ? kslot[i] : 0;   // kslot is a HOST array
+  a.pval = (float*)workspace; a.pidx = lp_pidx(workspace, H, W);
+  lp_fill_kslot(a.kslot, kslot, nkeys);
   a.H = H; a.W = W; a.C = C; a.CO = CO; a.radius = radius; a.non_mask_len = non_mask_len; a.topk = topk; a.inv_temp = 1.0f / temperature;
-  return vfs_labelprop_launch(a, S(stream));
+  return vfs_labelprop_launch(a, stream_of(stream));
 }
 int vfs_seg_postprocess(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                         vfs_stream_t stream) {
-  return vfs_seg_postprocess_launch(seg, partial, label, H, W, CO, Ho, Wo, S(stream));
+  return vfs_seg_postprocess_launch(seg, partial, label, H, W, CO, Ho, Wo, stream_of(stream));
 }
 int vfs_onehot(const uint8_t* labels, float* out, int P, int CO, vfs_stream_t stream) {
-  return vfs_onehot_launch(labels, out, P, CO, S(stream));
+  return vfs_onehot_launch(labels, out, P, CO, stream_of(stream));
 }
 
 // ---- fp32 evaluation path (exact_f32.hip) ----
@@ -699,40 +709,31 @@ int vfs_conv_f32_fwd(const float* x, const float* w, const float* scale, const f
                      int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int dilation, int relu,
                      vfs_stream_t stream) {
   if (!x || !w || !y) return vfs_set_error(VFS_ERR_ARG, "conv_f32_fwd: null buffer");
-  ConvF32Args a;
+  ConvF32Args a{};
   a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW;
   a.stride = stride; a.pad = pad; a.dil = dilation; a.relu = relu;
-  return vfs_conv_f32_launch(a, S(stream));
+  return vfs_conv_f32_launch(a, stream_of(stream));
 }
 int vfs_imgs_to_nhwc4_f32(const float* imgs, float* out, int B, int V, int T, int H, int W, vfs_stream_t stream) {
-  return vfs_imgs_to_nhwc4_f32_launch(imgs, out, B, V, T, H, W, S(stream));
+  return vfs_imgs_to_nhwc4_f32_launch(imgs, out, B, V, T, H, W, stream_of(stream));
 }
 int vfs_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, vfs_stream_t stream) {
-  return vfs_maxpool_f32_launch(x, y, N, H, W, C, Ho, Wo, S(stream));
+  return vfs_maxpool_f32_launch(x, y, N, H, W, C, Ho, Wo, stream_of(stream));
 }
 int vfs_l2norm_rows_f32(const float* x, float* y, long long P, int C, vfs_stream_t stream) {
-  return vfs_l2norm_rows_f32_launch(x, y, P, C, S(stream));
+  return vfs_l2norm_rows_f32_launch(x, y, P, C, stream_of(stream));
 }
 int vfs_labelprop_f32(const float* fbank, const float* sbank, float* out, void* workspace, long long workspace_bytes, int qframe,
                       const int* kslot, int nkeys, int H, int W, int C, int CO, int radius, int non_mask_len, int topk, float temperature,
                       vfs_stream_t stream) {
-  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: 1 <= nkeys <= 64");
-  if (!lp_workspace_ok(workspace, workspace_bytes, H, W))
-    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: workspace smaller than vfs_labelprop_workspace_bytes(H, W)");
-  if (non_mask_len < 0 || non_mask_len >= nkeys + (radius <= 0)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: 0 <= non_mask_len < nkeys");
-  LabelPropF32Args a;
-  a.fbank = fbank; a.sbank = sbank; a.out = out; a.qframe = qframe; a.nkeys = nkeys;
-  a.pval = (float*)workspace;
-  a.pidx = workspace ? (int*)((float*)workspace + (size_t)LP_MAX_SPLIT * H * W * 10) : nullptr;
-  for (int i = 0; i < LP_MAX_KEYS; ++i) a.kslot[i] = i < nkeys ? kslot[i] : 0;   // kslot is a HOST array
-  a.H = H; a.W = W; a.C = C; a.CO = CO; a.radius = radius; a.topk = topk; a.temperature = temperature;
-  a.non_mask_len = non_mask_len;
-  return vfs_labelprop_f32_launch(a, S(stream));
+  if (int rc = lp_check("labelprop_f32", nkeys, radius, non_mask_len, true, workspace, workspace_bytes, H, W)) return rc;
+  const LabelPropF32Args a = lp_f32_args(fbank, sbank, out, workspace, qframe, kslot, nkeys, H, W, C, CO, radius, non_mask_len, topk, temperature);
+  return vfs_labelprop_f32_launch(a, stream_of(stream));
 }
 int vfs_split_rows_bf16x2(const float* x, vfs_bf16* hl, long long P, int C, vfs_stream_t stream) {
   if (!x || !hl) return vfs_set_error(VFS_ERR_ARG, "split_rows_bf16x2: null buffer");
-  return vfs_split_rows_bf16x2_launch(x, hl, P, C, S(stream));
+  return vfs_split_rows_bf16x2_launch(x, hl, P, C, stream_of(stream));
 }
 static long long lp2_lists_bytes(int H, int W, int entries) { return (long long)entries * H * W * 8; }
 static long long lp2_counts_bytes(int H, int W) { return ((long long)(LP2_MAX_SPLIT + 1) * H * W * 4 + 15) / 16 * 16; }      // counts + thresholds
@@ -757,13 +758,12 @@ int vfs_labelprop_f32_2pass(const float* fbank, const vfs_bf16* hlbank, const fl
   if (!hlbank || !unit_rows || !vfs_lp2_eligible(C) || (long long)H * W >= (1 << 21))      // (2^21 positions: the float index arithmetic of pass 1)
     return vfs_labelprop_f32(fbank, sbank, out, workspace, workspace_bytes, qframe, kslot, nkeys, H, W, C, CO, radius, non_mask_len, topk,
                              temperature, stream);
-  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: 1 <= nkeys <= 64");
-  if (non_mask_len < 0 || non_mask_len >= nkeys + (radius <= 0)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass: 0 <= non_mask_len < nkeys");
+  if (int rc = lp_check("labelprop_f32_2pass", nkeys, radius, non_mask_len, false, workspace, workspace_bytes, H, W)) return rc;      // its workspace: below
   long long need = 0, dense = 0;
   if (vfs_labelprop_f32_2pass_workspace_bytes_for(H, W, 16, &need) != VFS_OK || vfs_labelprop_workspace_bytes(H, W, &dense) != VFS_OK || !workspace ||
       workspace_bytes < need)
     return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass: workspace smaller than vfs_labelprop_f32_2pass_workspace_bytes_for(H, W, 16)");
-  Lp2Args p;
+  Lp2Args p{};
   p.fbank = fbank; p.hl = hlbank; p.sbank = sbank; p.out = out;
   const long long entries = (workspace_bytes - dense - lp2_counts_bytes(H, W) - 16) / ((long long)H * W * 8);
   p.entries = (int)(entries > LP2_MAX_SPLIT * LP2_MAX_CAP ? LP2_MAX_SPLIT * LP2_MAX_CAP : entries);
@@ -773,40 +773,34 @@ int vfs_labelprop_f32_2pass(const float* fbank, const vfs_bf16* hlbank, const fl
   p.gthr = p.counts + (size_t)LP2_MAX_SPLIT * H * W;
   p.flags = (int*)(ws + lp2_lists_bytes(H, W, p.entries) + lp2_counts_bytes(H, W));
   p.qframe = qframe; p.nkeys = nkeys;
-  for (int i = 0; i < LP_MAX_KEYS; ++i) p.kslot[i] = i < nkeys ? kslot[i] : 0;
+  lp_fill_kslot(p.kslot, kslot, nkeys);
   p.H = H; p.W = W; p.C = C; p.CO = CO; p.radius = radius; p.topk = topk; p.non_mask_len = non_mask_len; p.temperature = temperature;
-  p.margin = 0.f; p.cap = 0; p.nsplit = 0; p.xcd_order = 0; p.dbg = 0;
-  int rc = vfs_labelprop_f32_2pass_launch(p, S(stream));
+  int rc = vfs_labelprop_f32_2pass_launch(p, stream_of(stream));
   if (rc) return rc;
   // the dense kernel as the overflow fallback: its workgroups read the flag and leave when no list overflowed
-  LabelPropF32Args a;
-  a.fbank = fbank; a.sbank = sbank; a.out = out; a.qframe = qframe; a.nkeys = nkeys;
-  a.pval = (float*)workspace;
-  a.pidx = (int*)((float*)workspace + (size_t)LP_MAX_SPLIT * H * W * 10);
-  for (int i = 0; i < LP_MAX_KEYS; ++i) a.kslot[i] = p.kslot[i];
-  a.H = H; a.W = W; a.C = C; a.CO = CO; a.radius = radius; a.topk = topk; a.temperature = temperature; a.non_mask_len = non_mask_len;
+  LabelPropF32Args a = lp_f32_args(fbank, sbank, out, workspace, qframe, kslot, nkeys, H, W, C, CO, radius, non_mask_len, topk, temperature);
   a.run_flag = p.flags;
-  return vfs_labelprop_f32_launch(a, S(stream));
+  return vfs_labelprop_f32_launch(a, stream_of(stream));
 }
 int vfs_bilinear_resize_f32(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
                             vfs_stream_t stream) {
   if (!src || !dst) return vfs_set_error(VFS_ERR_ARG, "bilinear_resize_f32: null buffer");
-  return vfs_bilinear_resize_f32_launch(src, dst, C, H, W, Ho, Wo, src_nhwc, dst_nhwc, S(stream));
+  return vfs_bilinear_resize_f32_launch(src, dst, C, H, W, Ho, Wo, src_nhwc, dst_nhwc, stream_of(stream));
 }
 int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                               vfs_stream_t stream) {
-  return vfs_seg_postprocess_exact_launch(seg, partial, label, H, W, CO, Ho, Wo, S(stream));
+  return vfs_seg_postprocess_exact_launch(seg, partial, label, H, W, CO, Ho, Wo, stream_of(stream));
 }
 
 int vfs_davis_counts(const uint8_t* pred, const uint8_t* gt, int* counts, void* scratch, int T, int H, int W, int nobj, int radius,
                      int use_void, vfs_stream_t stream) {
   if (T >= 3 && nobj > 0 && (!pred || !gt || !counts || !scratch)) return vfs_set_error(VFS_ERR_ARG, "davis_counts: null buffer");
-  DavisArgs a;
+  DavisArgs a{};
   a.pred = pred; a.gt = gt; a.counts = counts;
   a.bp = (unsigned*)scratch;
   a.bg = scratch ? (unsigned*)scratch + (size_t)(T > 2 ? T - 2 : 0) * H * W : nullptr;
   a.T = T; a.H = H; a.W = W; a.nobj = nobj; a.radius = radius; a.use_void = use_void;
-  return vfs_davis_counts_launch(a, S(stream));
+  return vfs_davis_counts_launch(a, stream_of(stream));
 }
 
 int vfs_heatmap_topk(const float* maps, float* vals, int* idx, float* minv, int* flags, long long N, int H, int W, int topk,
@@ -814,28 +808,28 @@ int vfs_heatmap_topk(const float* maps, float* vals, int* idx, float* minv, int*
   if (N > 0 && (!maps || !vals || !idx || !minv || !flags)) return vfs_set_error(VFS_ERR_ARG, "heatmap_topk: null buffer");
   if (((uintptr_t)maps & 3u) != 0) return vfs_set_error(VFS_ERR_ARG, "heatmap_topk: maps must be 4-byte aligned");
   if (H < 1 || W < 1 || (long long)H * W > (1LL << 28)) return vfs_set_error(VFS_ERR_SHAPE, "heatmap_topk: 1 <= H*W <= 2^28");
-  HeatmapTopkArgs a;
+  HeatmapTopkArgs a{};
   a.maps = maps; a.vals = vals; a.idx = idx; a.minv = minv; a.flags = flags;
   a.N = N; a.HW = H * W; a.topk = topk;
-  return vfs_heatmap_topk_launch(a, S(stream));
+  return vfs_heatmap_topk_launch(a, stream_of(stream));
 }
 
 int vfs_label_counts(const uint8_t* pred, const uint8_t* gt, unsigned long long* counts, long long n, int num_classes,
                      int ignore_index, vfs_stream_t stream) {
   if (n > 0 && (!pred || !gt || !counts)) return vfs_set_error(VFS_ERR_ARG, "label_counts: null buffer");
   if (((uintptr_t)counts & 7u) != 0) return vfs_set_error(VFS_ERR_ARG, "label_counts: counts must be 8-byte aligned");
-  LabelCountsArgs a;
+  LabelCountsArgs a{};
   a.pred = pred; a.gt = gt; a.counts = counts;
-  a.n = n; a.nvec = 0; a.num_classes = num_classes; a.ignore_index = ignore_index;
-  return vfs_label_counts_launch(a, S(stream));
+  a.n = n; a.num_classes = num_classes; a.ignore_index = ignore_index;
+  return vfs_label_counts_launch(a, stream_of(stream));
 }
 
 int vfs_pose_heatmaps(const float* patch, const int* kp, float* out, int K, int H, int W, int P, vfs_stream_t stream) {
   if (K > 0 && (!patch || !kp || !out)) return vfs_set_error(VFS_ERR_ARG, "pose_heatmaps: null buffer");
-  PoseHeatmapArgs a;
+  PoseHeatmapArgs a{};
   a.patch = patch; a.kp = kp; a.out = out;
   a.K = K; a.H = H; a.W = W; a.P = P;
-  return vfs_pose_heatmaps_launch(a, S(stream));
+  return vfs_pose_heatmaps_launch(a, stream_of(stream));
 }
 
 int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_t* flips, float* imgs, vfs_bf16* x4, int B, int V, int T,
@@ -843,12 +837,8 @@ int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_
                               double std_g, double std_b, vfs_stream_t stream) {
   if (!src || !boxes || !flips || (!imgs && !x4)) return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_norm: null buffer");
   if (x4 && Wp < Wo) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_norm: Wp < Wo");
-  PipelineArgs a;
-  a.src = src; a.boxes = boxes; a.flips = flips; a.imgs = imgs; a.x4 = x4;
-  a.B = B; a.V = V; a.T = T; a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo; a.Wp = Wp;
-  a.mean[0] = mean_r; a.mean[1] = mean_g; a.mean[2] = mean_b;
-  a.stdinv[0] = 1.0 / std_r; a.stdinv[1] = 1.0 / std_g; a.stdinv[2] = 1.0 / std_b;
-  return vfs_crop_resize_flip_norm_launch(a, S(stream));
+  const PipelineArgs a = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
+  return vfs_crop_resize_flip_norm_launch(a, stream_of(stream));
 }
 
 int vfs_crop_resize_flip_photo_norm_workspace_bytes(int frames, int Ho, int Wo, long long* bytes) {
@@ -867,16 +857,12 @@ int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const 
   long long need = 0;
   if (vfs_crop_resize_flip_photo_norm_workspace_bytes(B * V * T, Ho, Wo, &need) != VFS_OK || !workspace || workspace_bytes < need)
     return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm: workspace smaller than vfs_crop_resize_flip_photo_norm_workspace_bytes");
-  PhotoArgs pa;
-  PipelineArgs& a = pa.p;
-  a.src = src; a.boxes = boxes; a.flips = flips; a.imgs = imgs; a.x4 = x4;
-  a.B = B; a.V = V; a.T = T; a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo; a.Wp = Wp;
-  a.mean[0] = mean_r; a.mean[1] = mean_g; a.mean[2] = mean_b;
-  a.stdinv[0] = 1.0 / std_r; a.stdinv[1] = 1.0 / std_g; a.stdinv[2] = 1.0 / std_b;
+  PhotoArgs pa{};
+  pa.p = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
   pa.photo = photo;
   pa.sums = (unsigned long long*)workspace;
   pa.pix = (uint32_t*)((char*)workspace + (size_t)B * V * T * 8);
-  return vfs_crop_resize_flip_photo_norm_launch(pa, S(stream));
+  return vfs_crop_resize_flip_photo_norm_launch(pa, stream_of(stream));
 }
 
 }  // extern "C"

@@ -655,8 +655,6 @@ __global__ __launch_bounds__(256, NW > 2 ? 1 : 2) void conv3x3_halo_kernel(ConvA
   halo_epilogue_dispatch<BC, SMALLW, RAGGED>(a, acc, &sRed[0][0][0], smem, tile, tn0, y0, x0, c0, wc, wp, lr, lq, t);
 }
 
-int vfs_option_halo_deep_max = 256;   // the four-stage weight ring (one workgroup per CU) for launches of at most this many workgroups (0: never)
-
 template <int BC, bool DGRAD, bool SMALLW>
 static int launch_halo(const ConvArgs& a0, hipStream_t stream) {
   ConvArgs a = a0;
@@ -676,9 +674,6 @@ static int launch_halo(const ConvArgs& a0, hipStream_t stream) {
   else hipLaunchKernelGGL((conv3x3_halo_kernel<BC, DGRAD, SMALLW, false>), dim3(tiles * ncb), dim3(256), 0, stream, a);
   return vfs_check_launch("conv3x3_halo");
 }
-
-int vfs_option_halo_xcd = 1;          // XCD-aware tile order of the halo kernels (A/B knob)
-int vfs_option_halo_min_fill = 70;    // percent of a ragged tiling that must be real pixels (100: exact tilings only)
 
 // eligibility: 3x3 / stride 1 / pad 1, 64-channel granularity, and a spatial tiling that keeps the
 // per-128-pixel statistics rows aligned with the two halves of the batch:

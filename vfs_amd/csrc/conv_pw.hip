@@ -21,8 +21,6 @@
 #include "vfs_igemm_epi.h"
 #include "vfs_ops.h"
 
-int vfs_option_igemm_pw = 0;          // 0: off (default: measured slower than the one-tile kernels, MEASUREMENTS.md round 5); 1: where the plan below says so; 2: every eligible 1x1
-int vfs_option_igemm_pw_min_tiles = 192;   // fewer 128-pixel tiles than this leave CUs idle: the split-channel kernels take over
 
 template <int BC, bool FBN>
 constexpr int pw_ring_stages() {
@@ -193,7 +191,6 @@ int vfs_conv_pw_dispatch(const ConvArgs& a, int mode, hipStream_t stream) {
 // workgroup owns 16 output channels x 32 rows, its four waves each take a QUARTER of K with fragments loaded straight from global
 // memory into MFMA operand registers (a lane's 16 bytes = 8 consecutive k of one row: exactly the 16x16x32 fragment) - no LDS
 // stage, no barrier in the loop, many independent loads in flight - and meet once in LDS.  Cout / 16 x ceil(M / 32) workgroups.
-int vfs_option_igemm_skinny = 1;      // A/B knob
 
 __global__ __launch_bounds__(256) void conv_skinny_kernel(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) float sAcc[4][2][64][4];

@@ -452,10 +452,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_ring_kernel(WgradArgs a) {
   }
 }
 
-int vfs_option_wgrad_ring = 1;  // the LDS-DMA ring for 1x1 / stride-1 weight gradients with 128 | C, 128 | Cout (0: the register-staged kernel, A/B knob)
-int vfs_option_wgrad_xcd = 1;   // XCD-aware block order of the generic weight-gradient kernel (A/B knob)
-int vfs_option_wgrad_lin2 = 1;  // ... and its generalisation to evenly tiled 3x3 / stride-2 problems (A/B knob)
-int vfs_option_wgrad_lin = 1;   // the linear-address path for 1x1 / stride-1 problems (A/B knob)
 
 template <int BCW, int MODE, int LIN = 0>
 static int launch_wgrad(const WgradArgs& a0, hipStream_t stream) {

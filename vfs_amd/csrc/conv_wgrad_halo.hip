@@ -35,7 +35,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int lo_off, int hi
   return f;
 }
 
-extern int vfs_option_wgrad_xcd;      // conv_wgrad.hip
 
 template <bool SMALLW, bool BNIN>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_halo_kernel(WgradArgs a, int tiles_per_split, int ntiles) {

@@ -378,8 +378,6 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void conv_f32_db_kernel(Con
   }
 }
 
-int vfs_option_conv_f32_variant = 0;      // A/B knob: 321 = conv_f32_kernel (two barriers per chunk)
-int vfs_option_conv_f32_dbg = 0;
 int vfs_conv_f32_launch(const ConvF32Args& a_in, hipStream_t s) {
   ConvF32Args a = a_in;
   a.dbg = vfs_option_conv_f32_dbg;
@@ -709,10 +707,6 @@ __global__ __launch_bounds__(256) void labelprop_f32_merge_kernel(LabelPropF32Ar
   }
 }
 
-int vfs_option_lpx_target = 0;   // workgroups the key frames of a query tile are split into; 0 = auto (A/B knob)
-int vfs_option_lpx_wgs = 0;      // workgroups a launch should reach by ALSO splitting a key frame's window; 0 = auto (3072 for C >= 512:
-                                 // R50 5.33-5.39 vs 5.45-5.50 ms per frame; R18 is faster without: 1.48 vs 1.54), < 0 = never
-int vfs_option_lpx_minb = 4;     // ... with at least this many 64-key blocks per workgroup
 int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
   if (a.C % 4) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: C % 4");
   if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: 1 <= nkeys <= 64");

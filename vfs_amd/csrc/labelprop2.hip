@@ -816,15 +816,6 @@ __global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-int vfs_option_lp2 = 1;            // 0: always the dense kernel (A/B knob)
-int vfs_option_lp2_dbg = 0;        // what-if timing (WRONG results): 2 = cache-hot key traffic, 4 = no lists; 16 = list every in-mask candidate (results unchanged: tests read the s~ of the lists)
-int vfs_option_lp2_fpb = 0;        // pass 1: key frames per workgroup; 0 = chosen per launch (vfs_lp2_splits)
-int vfs_option_lp2_trim = 1;       // pass 1: windows of masked key frames trimmed to the columns the tile can reach (0: rectangles, A/B knob)
-int vfs_option_lp2_cap = 0;        // list entries per (key-frame split, query); 0 = the workspace shared out among the splits in use
-int vfs_option_lp2_xcd = -1;       // pass 1 work order: 1 / 2 = XCD-aware (/ staggered), 0 = dispatch order, -1 = by bank width: XCD-aware for
-                                   // C = 1024 (ResNet-50: level in time, 2.986 vs 3.004 ms per frame, 4.7 instead of 8.3 GB fetched per launch), dispatch order for
-                                   // narrower banks (ResNet-18, C = 256: 1.015 vs 1.054 ms per frame - short key blocks, the tiles of an XCD wait for the same lines)
-
 // Key frames per workgroup: about four workgroups per CU and launch (pass 1 runs ONE workgroup per CU at a time: the query tile fills
 // the register file).  Measured on the MI355X, 21 key frames: 1 / 2 / 3 frames per workgroup = 2.21 / 2.24 / 2.27 ms (ResNet-50) and
 // 0.78 / 0.75 / 0.77 (ResNet-18) - flat; two workgroups of 11 frames per tile: 0.92.

@@ -216,5 +216,7 @@ __device__ __forceinline__ unsigned mask8_load(const void* bits, long long m, in
 #define VFS_ERR_LAUNCH (-2)
 #define VFS_ERR_ARG (-3)
 
-int vfs_set_error(int code, const char* msg);  // capi.cpp
-int vfs_check_launch(const char* what);        // capi.cpp
+int vfs_set_error(int code, const char* msg);  // capi.hip
+int vfs_check_launch(const char* what);        // capi.hip
+
+#include "vfs_options.h"      // the A/B knobs the dispatchers read (extern int vfs_option_*)

@@ -143,22 +143,17 @@ __device__ __forceinline__ void vfs_stats_coarsen_finish(const ConvArgs& a, unsi
 // conv_pw.hip: persistent producer / consumer kernel for pure-GEMM (1x1, stride 1) problems
 bool vfs_conv_pw_eligible(const ConvArgs& a, int mode);
 int vfs_conv_pw_dispatch(const ConvArgs& a, int mode, hipStream_t stream);
-extern int vfs_option_igemm_pw, vfs_option_igemm_pw_min_tiles, vfs_option_igemm_skinny;
 bool vfs_conv_skinny_eligible(const ConvArgs& a, int mode);      // M <= 128 rows: the head's Linear layers
 int vfs_conv_skinny_dispatch(const ConvArgs& a, hipStream_t stream);
 bool vfs_conv_halo_eligible(const ConvArgs& a, int mode);
 // maps of at most 8x8 pixels that fill most of an 8x8 tile (8x8, 7x7 with the default 70 %): the halo kernels take
 // two whole images per workgroup
-extern int vfs_option_halo_min_fill, vfs_option_halo_xcd, vfs_option_halo_deep_max;
 static inline bool vfs_small_map(int H, int W) { return H <= 8 && W <= 8 && H * W * 100 >= 64 * vfs_option_halo_min_fill; }
 int vfs_conv_halo_dispatch(const ConvArgs& a, int mode, hipStream_t stream);
 bool vfs_wgrad_halo_eligible(const WgradArgs& a, int mode);
 int vfs_wgrad_halo_dispatch(const WgradArgs& a, hipStream_t stream, int* eff_nsplit);
 int vfs_stem_tiles(int N, int Ho, int Wo);
 int vfs_stem_fwd_direct_launch(const ConvArgs& a, hipStream_t stream);
-extern int vfs_option_stem_direct;
-extern int vfs_option_stem_blocks;   // grid cap of the direct stem kernel (0 = default 2048); tests walk many tiles per block
-extern int vfs_option_halo;   // 1: 3x3/s1 convs use the halo-tile kernel (capi: vfs_set_option)
 int vfs_conv_wgrad_dispatch(const WgradArgs& a, int mode, hipStream_t stream);
 
 struct PixCoord {

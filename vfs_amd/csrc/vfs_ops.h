@@ -1,8 +1,10 @@
-// Argument structs + host launchers of the element-wise / reduction kernels (bn.hip, misc.hip).
+// Argument structs + host launchers of every kernel file except the convolutions (vfs_conv.h), grouped by the .hip file that
+// defines the launchers.  A new launcher goes under its file's heading.
 #pragma once
 #include "vfs_common.h"
 #include "vfs_p2p.h"
 
+// ---- bn.hip -----------------------------------------------------------------------------------------------
 // y = [relu]( x*scale + shift  [+ res]  [+ rres*rscale + rshift] )
 struct BnActArgs {
   const bf16_t* x;      // [M][C] raw conv output
@@ -24,7 +26,6 @@ __device__ __forceinline__ void bn_running_update(float& rm, float& rv, float mo
   rm = __builtin_fmaf(momentum, (float)mean, keep * rm);
   rv = __builtin_fmaf(momentum, (float)unbiased, keep * rv);
 }
-
 
 // Optional in-kernel statistics finalisation for the apply passes (bn_act / bn_bwd_apply, SMALL row counts): the
 // workgroup reduces the partial rows of its own (group, channel slab) in its prologue - every workgroup gets the same
@@ -108,11 +109,8 @@ struct StemBwdArgs {
   int N, H, W, C, Hp, Wp, npg, ppb;   // images per group, pooled pixels per block (pass 1)
   double count;
 };
-
 int vfs_stem_pool_bn_bwd_reduce_launch(const StemBwdArgs& a, int nblk, hipStream_t s);
 int vfs_stem_pool_bn_bwd_apply_launch(const StemBwdArgs& a, hipStream_t s);
-int vfs_stem_wgrad_fused_launch(const StemBwdArgs& a, const bf16_t* x4, int Hin, int Win, float* partial, int nblocks,
-                                hipStream_t stream);
 int vfs_bn_reduce_partials_launch(const float* partial, double* sums, double* scratch, int G, int bpg, int C, hipStream_t s,
                                   const P2PTail* tail = nullptr);
 int vfs_bn_reduce_fused_launch(int mode, const float* partial, double* sums, double* scratch, int G, int bpg, int C,
@@ -128,6 +126,17 @@ int vfs_maxpool_relu_bwd_launch(const PoolBwdArgs& a, hipStream_t s);
 int vfs_bn_bwd_reduce_launch(const BnBwdArgs& a, int nblk, hipStream_t s);
 int vfs_bn_bwd_apply_launch(const BnBwdArgs& a, hipStream_t s);
 int vfs_bn_param_grad_launch(const double* sums, float* dgamma, float* dbeta, int G, int C, hipStream_t s);
+int vfs_bn_stats_raw_launch(const bf16_t* x, double* sums, int G, int rows, int C, const float* gamma, const float* beta, float* bnp,
+                            float* rm, float* rv, double count, float eps, float momentum, hipStream_t s);
+int vfs_bn_act_fin_launch(const BnActArgs& a, const BnFin& f, hipStream_t s);
+int vfs_bn_bwd_apply_raw_launch(const BnBwdArgs& a, const BnFin& f, hipStream_t s);
+int vfs_bn_bwd_apply_fin_launch(const BnBwdArgs& a, const BnFin& f, hipStream_t s);
+
+// ---- stem.hip: the stem's weight gradient with the pool / BatchNorm backward folded in --------------------
+int vfs_stem_wgrad_fused_launch(const StemBwdArgs& a, const bf16_t* x4, int Hin, int Win, float* partial, int nblocks,
+                                hipStream_t stream);
+
+// ---- conv_wgrad.hip: reduction of the split-K partials ----------------------------------------------------
 int vfs_wgrad_reduce_launch(const float* partial, float* grad, int nsplit, int Cout, int Ktot, int Cin, int KH, int KW,
                             int stem, hipStream_t stream);
 // one record per layer of the table-driven split-K reduction (conv_wgrad.hip; 56 bytes, mirrored by vfs_amd/packing.py)
@@ -142,7 +151,7 @@ struct WgradReduceDesc {
 };
 int vfs_wgrad_reduce_table_launch(const WgradReduceDesc* tab, int n, int total_blocks, hipStream_t stream);
 
-// ---- misc.hip ------------------------------------------------------------------------------
+// ---- misc.hip ---------------------------------------------------------------------------------------------
 // imgs fp32 [B][V][3][T][H][W] (reference layout, FormatShape 'NCTHW') -> bf16 NHWC4
 // out[(v*B + b)*T + t][h][w][0..3], channel 3 = 0, width padded to Wp (even) with zeros
 int vfs_imgs_to_nhwc4_launch(const float* imgs, bf16_t* out, int B, int V, int T, int H, int W, int Wp, hipStream_t s);
@@ -174,24 +183,18 @@ struct LossArgs {
   int N, C, T, K, negative;
   float weight;
 };
-int vfs_bn_stats_raw_launch(const bf16_t* x, double* sums, int G, int rows, int C, const float* gamma, const float* beta, float* bnp,
-                            float* rm, float* rv, double count, float eps, float momentum, hipStream_t s);
-// SiamFC cross-correlation (xcorr.hip)
-struct XcorrArgs {
-  const bf16_t* z;   // [nz][Hz][Wz][C] exemplar features
-  const bf16_t* x;   // [nx][H][W][C] search features
-  float* out;        // [nx][H-Hz+1][W-Wz+1]
-  int nz, nx, Hz, Wz, H, W, C;
-  float scale;
-};
-// p2p.hip: SyncBN statistic exchange through IPC-mapped windows
-int vfs_p2p_window_bytes_host(long long* bytes, int* max_doubles, int* max_world);
-int vfs_p2p_alloc_host(void** ptr);
-int vfs_p2p_free_host(void* ptr);
-int vfs_p2p_export_host(void* ptr, void* handle64);
-int vfs_p2p_import_host(const void* handle64, void** ptr);
-int vfs_p2p_unimport_host(void* ptr);
-// nn.Linear + BatchNorm1d + ReLU in one launch (conv_pw.hip: linear_bn_act_kernel)
+int vfs_cosine_loss_fwd_launch(const LossArgs& a, hipStream_t s);
+int vfs_cosine_loss_bwd_launch(const LossArgs& a, hipStream_t s);
+int vfs_loss_means_launch(const float* loss, float* means, int K, int N, hipStream_t s);
+
+// fused SGD over the flat parameter arena (torch.optim.SGD, dampening 0, no nesterov)
+int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const unsigned long long* skip,
+                   hipStream_t s);
+int vfs_scale_launch(float* p, long long n, float scale, hipStream_t s);
+int vfs_f32_to_bf16_launch(const float* src, bf16_t* dst, long long n, float scale, hipStream_t s);
+int vfs_bf16_to_f32_launch(const bf16_t* src, float* dst, long long n, hipStream_t s);
+
+// ---- conv_pw.hip: nn.Linear + BatchNorm1d + ReLU in one launch (linear_bn_act_kernel) ---------------------
 struct LinBnArgs {
   const bf16_t* x;      // [M][K]
   const bf16_t* w;      // [C][K]
@@ -208,18 +211,24 @@ struct LinBnArgs {
   double count;
   float eps, momentum;
 };
-int vfs_linear_bn_act_launch(const LinBnArgs& a, hipStream_t stream);      // conv_pw.hip
-int vfs_p2p_chain_start_launch(unsigned long long* state, hipStream_t s);
-int vfs_p2p_allreduce_f64_launch(double* buf, int n, void* const* peers, int rank, int world, unsigned long long* state, int phase,
-                                 unsigned long long spin_limit, hipStream_t s);
-// simloss.hip: CosineSimLoss on spatial inputs (pairwise affinity on the matrix cores, fp32)
+int vfs_linear_bn_act_launch(const LinBnArgs& a, hipStream_t stream);
+
+// ---- simloss.hip: CosineSimLoss on spatial inputs (pairwise affinity on the matrix cores, fp32) -----------
 int vfs_simloss_colnorm_launch(const float* x, float* inv, int B, int C, int S, hipStream_t s);
 int vfs_simloss_fwd_launch(const float* a, const float* l, const float* inva, const float* invl, const float* mask, float* partial,
                            float* loss, int B, int C, int Sa, int Sl, int pairwise, int negative, float weight, hipStream_t s);
 int vfs_simloss_bwd_launch(const float* other, const float* invo, const float* mask, int mask_transposed, const float* gloss, float* d,
                            int B, int C, int Sself, int Sother, int pairwise, int negative, float weight, hipStream_t s);
 int vfs_simloss_norm_bwd_launch(const float* x, const float* inv, const float* d, float* dx, int B, int C, int S, hipStream_t s);
-int vfs_xcorr_fwd_launch(const XcorrArgs& a, hipStream_t s);
+
+// ---- xcorr.hip: SiamFC cross-correlation, its loss and optimizer step -------------------------------------
+struct XcorrArgs {
+  const bf16_t* z;   // [nz][Hz][Wz][C] exemplar features
+  const bf16_t* x;   // [nx][H][W][C] search features
+  float* out;        // [nx][H-Hz+1][W-Wz+1]
+  int nz, nx, Hz, Wz, H, W, C;
+  float scale;
+};
 struct XcorrBwdArgs {
   const bf16_t* z;   // [nz][Hz][Wz][C]
   const bf16_t* x;   // [nx][H][W][C]
@@ -229,12 +238,14 @@ struct XcorrBwdArgs {
   int nz, nx, Hz, Wz, H, W, C;
   float scale;
 };
+int vfs_xcorr_fwd_launch(const XcorrArgs& a, hipStream_t s);
 int vfs_xcorr_bwd_launch(const XcorrBwdArgs& a, hipStream_t s);
 int vfs_siamfc_loss_launch(const float* x, const float* tgt, float* loss_out, float* grad, int n, int mode, float param, float scale,
                            hipStream_t s);
 int vfs_adam_launch(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd, int step,
                     hipStream_t s);
-// SiamFC tracking loop (siamfc_track.hip): search crops, response up-sampling, peak search
+
+// ---- siamfc_track.hip: SiamFC tracking loop (search crops, response up-sampling, peak search) -------------
 #define VFS_SIAMFC_MAX_SCALES 8
 #define VFS_SIAMFC_MAX_RESP 1024      // r * r floats of one response map in LDS
 struct SiamCropScale {
@@ -257,21 +268,19 @@ int vfs_siamfc_upsample_launch(const float* resp, const int* tap_idx, const floa
                                unsigned long long* scale_max, int S, int r, int up, hipStream_t s);
 int vfs_siamfc_peak_launch(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
                            float one_minus_wi, double wi, hipStream_t s);
-int vfs_cosine_loss_fwd_launch(const LossArgs& a, hipStream_t s);
-int vfs_bn_act_fin_launch(const BnActArgs& a, const BnFin& f, hipStream_t s);
-int vfs_bn_bwd_apply_raw_launch(const BnBwdArgs& a, const BnFin& f, hipStream_t s);
-int vfs_bn_bwd_apply_fin_launch(const BnBwdArgs& a, const BnFin& f, hipStream_t s);
-int vfs_loss_means_launch(const float* loss, float* means, int K, int N, hipStream_t s);
-int vfs_cosine_loss_bwd_launch(const LossArgs& a, hipStream_t s);
 
-// fused SGD over the flat parameter arena (torch.optim.SGD, dampening 0, no nesterov)
-int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const unsigned long long* skip,
-                   hipStream_t s);
-int vfs_scale_launch(float* p, long long n, float scale, hipStream_t s);
-int vfs_f32_to_bf16_launch(const float* src, bf16_t* dst, long long n, float scale, hipStream_t s);
-int vfs_bf16_to_f32_launch(const bf16_t* src, float* dst, long long n, hipStream_t s);
+// ---- p2p.hip: SyncBN statistic exchange through IPC-mapped windows ----------------------------------------
+int vfs_p2p_window_bytes_host(long long* bytes, int* max_doubles, int* max_world);
+int vfs_p2p_alloc_host(void** ptr);
+int vfs_p2p_free_host(void* ptr);
+int vfs_p2p_export_host(void* ptr, void* handle64);
+int vfs_p2p_import_host(const void* handle64, void** ptr);
+int vfs_p2p_unimport_host(void* ptr);
+int vfs_p2p_chain_start_launch(unsigned long long* state, hipStream_t s);
+int vfs_p2p_allreduce_f64_launch(double* buf, int n, void* const* peers, int rank, int world, unsigned long long* state, int phase,
+                                 unsigned long long spin_limit, hipStream_t s);
 
-// ---- labelprop.hip -------------------------------------------------------------------------
+// ---- labelprop.hip ----------------------------------------------------------------------------------------
 #define LP_MAX_KEYS 64      // key frames per propagation step (precede_frames + the first frame); round 3: 24 -> 64
 #define LP_MAX_CLASSES 256
 #define LP_POST_BLOCKS 64
@@ -298,7 +307,7 @@ int vfs_seg_postprocess_launch(const float* seg, float* partial, uint8_t* label,
                                hipStream_t s);
 int vfs_onehot_launch(const uint8_t* lab, float* out, int P, int CO, hipStream_t s);
 
-// ---- exact_f32.hip: the fp32 evaluation path (bit-defined arithmetic, see the file header) -----------
+// ---- exact_f32.hip: the fp32 evaluation path (bit-defined arithmetic, see the file header) ----------------
 // unsigned division by a launch constant (Granlund-Montgomery, any 32-bit numerator): q = (t + ((n - t) >> s1)) >> s2, t = mulhi(n, m)
 struct VfsFastDiv {
   unsigned m, s1, s2;
@@ -335,7 +344,17 @@ struct LabelPropF32Args {
   float temperature;
   const int* run_flag = nullptr;   // device word: when given and zero, the dense kernels exit at once (fallback of the two-pass path)
 };
-// two-pass exact label propagation (labelprop2.hip): bf16 hi/lo prefilter on the matrix cores + exact rescoring of the survivors
+int vfs_conv_f32_launch(const ConvF32Args& a, hipStream_t s);
+int vfs_imgs_to_nhwc4_f32_launch(const float* imgs, float* out, int B, int V, int T, int H, int W, hipStream_t s);
+int vfs_maxpool_f32_launch(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s);
+int vfs_l2norm_rows_f32_launch(const float* x, float* y, long long P, int C, hipStream_t s);
+int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s);
+int vfs_bilinear_resize_f32_launch(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
+                                   hipStream_t s);
+int vfs_seg_postprocess_exact_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
+                                     hipStream_t s);
+
+// ---- labelprop2.hip: two-pass exact label propagation (bf16 hi/lo prefilter on the matrix cores + exact rescoring of the survivors) 
 #define LP2_MAX_SPLIT 24     // key-frame splits of pass 1 (= candidate lists per query)
 #define LP2_MAX_CAP 192      // list entries per (split, query): the workspace is sized for this (seeded thresholds: a handful are used)
 #define LP2_LIST_MAX 2048    // longest single list
@@ -361,17 +380,8 @@ struct Lp2Args {
 int vfs_split_rows_bf16x2_launch(const float* x, bf16_t* hl, long long P, int C, hipStream_t s);
 int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s);
 bool vfs_lp2_eligible(int C);
-int vfs_conv_f32_launch(const ConvF32Args& a, hipStream_t s);
-int vfs_imgs_to_nhwc4_f32_launch(const float* imgs, float* out, int B, int V, int T, int H, int W, hipStream_t s);
-int vfs_maxpool_f32_launch(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s);
-int vfs_l2norm_rows_f32_launch(const float* x, float* y, long long P, int C, hipStream_t s);
-int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s);
-int vfs_bilinear_resize_f32_launch(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
-                                   hipStream_t s);
-int vfs_seg_postprocess_exact_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
-                                     hipStream_t s);
 
-// DAVIS J&F ingredients (davis.hip)
+// ---- davis.hip: DAVIS J&F ingredients ---------------------------------------------------------------------
 struct DavisArgs {
   const uint8_t* pred;   // [T][H][W] predicted labels
   const uint8_t* gt;     // [T][H][W] ground-truth labels (255 = void when use_void)
@@ -382,7 +392,7 @@ struct DavisArgs {
 };
 int vfs_davis_counts_launch(const DavisArgs& a, hipStream_t s);
 
-// JHMDB / VIP evaluation around forward_test (propeval.hip)
+// ---- propeval.hip: JHMDB / VIP evaluation around forward_test ---------------------------------------------
 #define VFS_TOPK_ALL_ZERO 1u   // flags of vfs_heatmap_topk (include/vfs_hip.h)
 #define VFS_TOPK_NAN 2u
 #define VFS_TOPK_NEG_INF 4u
@@ -412,7 +422,7 @@ struct PoseHeatmapArgs {
 };
 int vfs_pose_heatmaps_launch(const PoseHeatmapArgs& a, hipStream_t s);
 
-// training input pipeline (pipeline.hip)
+// ---- pipeline.hip: training input pipeline ----------------------------------------------------------------
 struct PipelineArgs {
   const uint8_t* src;    // [F][Hs][Ws][3] decoded RGB frames, F = B*V*T in pipeline order (b, v, t)
   const int* boxes;      // [F][4] crop box left, top, right, bottom (img[top:bottom, left:right])
@@ -431,4 +441,3 @@ struct PhotoArgs {
 };
 long long vfs_photo_workspace_bytes(int F, int Ho, int Wo);
 int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& a, hipStream_t s);
-
