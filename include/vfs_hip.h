@@ -281,6 +281,23 @@ int vfs_cosine_loss_bwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* 
                         const vfs_bf16* z2, const float* gloss, vfs_bf16* dp1, vfs_bf16* dp2, int N,
                         int C, int T, int K, int negative, float weight, vfs_stream_t stream);
 
+/* ---- DenseSimSiamHead.loss over all temporal rolls (sim_siam_head.py:277-284: CosineSimLoss(with_norm=True, pairwise=False)
+ * on 4-D operands, sim_loss.py:43-62, inside the roll loop of sim_siam_base_tracker.py:39-55), on the head's own bf16 NHWC
+ * output: p1, z1, p2, z2 = [N][S][C], N = B*T images of one view, S = h*w positions, 16-byte aligned.
+ *   loss[k][i] = weight * (0.5 * L(p1[i], z2[j]) + 0.5 * L(p2[j], z1[i])),  j = roll_k(i) within i's video of T frames,
+ *   L(a, b) = negative ? -m : 2 - 2 m,  m = mean over the S positions of <a[s], b[s]> / (max(|a[s]|, 1e-12) max(|b[s]|, 1e-12)).
+ *   bwd: dp1, dp2 [N][S][C] = gradient wrt p (z is detached), summed over the K rolls with gloss[K][N].
+ * N % T == 0, 1 <= K <= T, S >= 1, C % 8 == 0, C <= 2048 (the backward keeps a position's operands and gradient in registers:
+ * 4 16-byte chunks per lane at most).  No atomics: equal inputs give equal bits.  workspace: per-workgroup partial sums of the
+ * forward, at least vfs_dense_cosine_loss_workspace_bytes(N, S, C, K) bytes (host-only query); a smaller buffer is REFUSED. */
+int vfs_dense_cosine_loss_workspace_bytes(int N, int S, int C, int K, long long* bytes);
+int vfs_dense_cosine_loss_fwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, float* loss,
+                              void* workspace, long long workspace_bytes, int N, int S, int C, int T, int K, int negative,
+                              float weight, vfs_stream_t stream);
+int vfs_dense_cosine_loss_bwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2,
+                              const float* gloss, vfs_bf16* dp1, vfs_bf16* dp2, int N, int S, int C, int T, int K,
+                              int negative, float weight, vfs_stream_t stream);
+
 /* ---- CosineSimLoss on spatial inputs, incl. pairwise=True / mask / with_norm=False (sim_loss.py:42-63) -------------
  * fp32 [B][C][S] operands = the reference's [B,C,*] tensors flattened (`.flatten(2)`); Sa / Sl: positions of cls_score / label.
  * colnorm: inv[b][s] = 1 / max(||x[b][:][s]||_2, 1e-12)   (F.normalize(p=2, dim=1), :44-45); pass inv = NULL for with_norm=False.

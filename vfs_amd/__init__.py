@@ -9,7 +9,7 @@ from .config import Config, ConfigDict  # noqa: F401
 from .registry import BACKBONES, HEADS, LOSSES, TRACKERS, Registry, build_from_cfg  # noqa: F401
 from .resnet import ResNet  # noqa: F401
 from .sim_loss import CosineSimLoss  # noqa: F401
-from .sim_siam_head import SimSiamHead  # noqa: F401
+from .sim_siam_head import DenseSimSiamHead, SimSiamHead  # noqa: F401
 from .trackers import BaseTracker, SimSiamBaseTracker, VanillaTracker  # noqa: F401
 from .optim import SGD, build_optimizer  # noqa: F401
 from .davis_eval import DavisEvaluator, evaluate_sequences  # noqa: F401

@@ -148,6 +148,24 @@ static LossArgs loss_args(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16
   a.p1 = p1; a.z1 = z1; a.p2 = p2; a.z2 = z2; a.N = N; a.C = C; a.T = T; a.K = K; a.negative = negative; a.weight = weight;
   return a;
 }
+// the per-position loss of DenseSimSiamHead: what forward and backward check alike, then the operands they share
+static int dense_loss_check(const char* who, const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, int N, int S,
+                            int C, int T, int K) {
+  if (T < 1 || N < 1 || N % T) return fail(VFS_ERR_SHAPE, who, "N % T");
+  if (K < 1 || K > T) return fail(VFS_ERR_SHAPE, who, "1 <= K <= T");
+  if (S < 1) return fail(VFS_ERR_SHAPE, who, "S >= 1");
+  if (C < 8 || C % 8) return fail(VFS_ERR_SHAPE, who, "C % 8");
+  if (C > VFS_DENSE_LOSS_MAX_C) return fail(VFS_ERR_SHAPE, who, "C > 2048");
+  if (!p1 || !z1 || !p2 || !z2 || (((size_t)p1 | (size_t)z1 | (size_t)p2 | (size_t)z2) & 15)) return fail(VFS_ERR_ARG, who, "null or unaligned operand (16 bytes)");
+  return VFS_OK;
+}
+static long long dense_loss_workspace_need(int N, int S, int C, int K) { return (long long)K * N * vfs_dense_loss_split(S, C) * 2 * 4; }
+static DenseLossArgs dense_loss_args(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, int N, int S, int C,
+                                     int T, int K, int negative, float weight) {
+  DenseLossArgs a{};
+  a.p1 = p1; a.z1 = z1; a.p2 = p2; a.z2 = z2; a.N = N; a.S = S; a.C = C; a.T = T; a.K = K; a.negative = negative; a.weight = weight;
+  return a;
+}
 
 // label propagation: the key list, the dense kernels' workspace (dense_workspace = false: the caller has a requirement of its own)
 // and the unmasked prefix of the key list (radius <= 0, no spatial mask: every key frame may be "unmasked")
@@ -610,6 +628,34 @@ int vfs_cosine_loss_bwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* 
   LossArgs a = loss_args(p1, z1, p2, z2, N, C, T, K, negative, weight);
   a.gloss = gloss; a.dp1 = dp1; a.dp2 = dp2;
   return vfs_cosine_loss_bwd_launch(a, stream_of(stream));
+}
+
+int vfs_dense_cosine_loss_workspace_bytes(int N, int S, int C, int K, long long* bytes) {
+  if (!bytes) return vfs_set_error(VFS_ERR_ARG, "dense_cosine_loss_workspace_bytes: null");
+  if (N < 1 || S < 1 || K < 1 || C < 8 || C % 8 || C > VFS_DENSE_LOSS_MAX_C)
+    return vfs_set_error(VFS_ERR_SHAPE, "dense_cosine_loss_workspace_bytes: N, S, K >= 1, C % 8 == 0, C <= 2048");
+  *bytes = dense_loss_workspace_need(N, S, C, K);
+  return VFS_OK;
+}
+int vfs_dense_cosine_loss_fwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, float* loss, void* workspace,
+                              long long workspace_bytes, int N, int S, int C, int T, int K, int negative, float weight,
+                              vfs_stream_t stream) {
+  if (int rc = dense_loss_check("dense_cosine_loss_fwd", p1, z1, p2, z2, N, S, C, T, K)) return rc;
+  if (!loss) return vfs_set_error(VFS_ERR_ARG, "dense_cosine_loss_fwd: null loss");
+  if (!workspace || workspace_bytes < dense_loss_workspace_need(N, S, C, K))
+    return vfs_set_error(VFS_ERR_ARG, "dense_cosine_loss_fwd: workspace smaller than vfs_dense_cosine_loss_workspace_bytes(N, S, C, K)");
+  DenseLossArgs a = dense_loss_args(p1, z1, p2, z2, N, S, C, T, K, negative, weight);
+  a.loss = loss; a.partial = (float*)workspace;
+  return vfs_dense_cosine_loss_fwd_launch(a, stream_of(stream));
+}
+int vfs_dense_cosine_loss_bwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, const float* gloss,
+                              vfs_bf16* dp1, vfs_bf16* dp2, int N, int S, int C, int T, int K, int negative, float weight,
+                              vfs_stream_t stream) {
+  if (int rc = dense_loss_check("dense_cosine_loss_bwd", p1, z1, p2, z2, N, S, C, T, K)) return rc;
+  if (!gloss || !dp1 || !dp2 || (((size_t)dp1 | (size_t)dp2) & 15)) return vfs_set_error(VFS_ERR_ARG, "dense_cosine_loss_bwd: null or unaligned gradient buffer");
+  DenseLossArgs a = dense_loss_args(p1, z1, p2, z2, N, S, C, T, K, negative, weight);
+  a.gloss = gloss; a.dp1 = dp1; a.dp2 = dp2;
+  return vfs_dense_cosine_loss_bwd_launch(a, stream_of(stream));
 }
 
 int vfs_bn_reduce_partials_xchg(const float* partial, double* sums, double* scratch, int G, int bpg, int C, const void* peers, int rank,

@@ -284,12 +284,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
-__device__ __forceinline__ int roll_src(int i, int T, int k) {  // index of roll(k)[i] within i's video
-  const int b = i / T, t = i - b * T;
-  int u = t - k;
-  if (u < 0) u += T;
-  return b * T + u;
-}
 // one wave per (k, i):  loss[k][i] = w * (0.5*L(p1[i], z2[j]) + 0.5*L(p2[j], z1[i])),  j = roll_k(i)
 __global__ __launch_bounds__(64) void cosine_loss_fwd_kernel(LossArgs a) {
   const int i = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;

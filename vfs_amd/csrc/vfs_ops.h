@@ -186,6 +186,12 @@ struct LossArgs {
 int vfs_cosine_loss_fwd_launch(const LossArgs& a, hipStream_t s);
 int vfs_cosine_loss_bwd_launch(const LossArgs& a, hipStream_t s);
 int vfs_loss_means_launch(const float* loss, float* means, int K, int N, hipStream_t s);
+__device__ __forceinline__ int roll_src(int i, int T, int k) {  // index of roll(k)[i] within i's video
+  const int b = i / T, t = i - b * T;
+  int u = t - k;
+  if (u < 0) u += T;
+  return b * T + u;
+}
 
 // fused SGD over the flat parameter arena (torch.optim.SGD, dampening 0, no nesterov)
 int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const unsigned long long* skip,
@@ -220,6 +226,24 @@ int vfs_simloss_fwd_launch(const float* a, const float* l, const float* inva, co
 int vfs_simloss_bwd_launch(const float* other, const float* invo, const float* mask, int mask_transposed, const float* gloss, float* d,
                            int B, int C, int Sself, int Sother, int pairwise, int negative, float weight, hipStream_t s);
 int vfs_simloss_norm_bwd_launch(const float* x, const float* inv, const float* d, float* dx, int B, int C, int S, hipStream_t s);
+
+// ---- simloss_dense.hip: the same loss per spatial position of bf16 NHWC maps (DenseSimSiamHead, sim_siam_head.py:277-284) ----
+#define DSL_MAX_CHUNKS 4                          // 16-byte chunks a lane of the backward keeps in registers (a, b, gradient)
+#define VFS_DENSE_LOSS_MAX_C (64 * DSL_MAX_CHUNKS * 8)      // = 2048
+#define DSL_MAX_SPLIT 32                          // workgroups that share the positions of one (image, roll)
+struct DenseLossArgs {
+  const bf16_t *p1, *z1, *p2, *z2;  // [N][S][C], N = B*T images of one view, S = h*w positions
+  float* loss;                      // fwd out [K][N]
+  float* partial;                   // fwd scratch [K][N][Z][2], Z = vfs_dense_loss_split(S, C)
+  const float* gloss;               // bwd in  [K][N]
+  bf16_t *dp1, *dp2;                // bwd out [N][S][C]
+  int N, S, C, T, K, negative;
+  float weight;
+  int lpp;                          // lanes per position (set by the launcher)
+};
+int vfs_dense_loss_split(int S, int C);
+int vfs_dense_cosine_loss_fwd_launch(const DenseLossArgs& a, hipStream_t s);
+int vfs_dense_cosine_loss_bwd_launch(const DenseLossArgs& a, hipStream_t s);
 
 // ---- xcorr.hip: SiamFC cross-correlation, its loss and optimizer step -------------------------------------
 struct XcorrArgs {

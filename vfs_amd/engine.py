@@ -111,6 +111,11 @@ class Engine:
     def end_tape(self):
         self.lib, self.tape = self._real_lib, None
 
+    @property
+    def host_lib(self):
+        """the library itself, also while a tape is recording: for host-only entry points (size queries) that are no part of a chain"""
+        return self._real_lib if self.tape is not None else self.lib
+
     def record(self, fn, *args):
         """run a Python-side action of the chain (stream wait, collective) and put it on the tape if one is recording"""
         if self.tape is not None:

@@ -469,12 +469,11 @@ class SimSiamBaseTracker(BaseTracker):
         z, p, hctx = self.img_head.forward_nhwc(eng, feat, N, h, w, C, V, True)
         K = T if self.intra_video else 1
         weight = (1.0 / T if self.intra_video else 1.0) * float(self.img_head.loss_feat.loss_weight)
-        neg = int(self.img_head.loss_feat.negative)
         loss = torch.empty(K, Nv, dtype=torch.float32, device=dev)
-        eng.lib.cosine_loss_fwd(p[:Nv], z[:Nv], p[Nv:], z[Nv:], loss, Nv, p.shape[1], T, K, neg, weight, s)
+        self.img_head.loss_fwd_nhwc(eng, p, z, loss, Nv, T, K, weight)      # the head's own loss launch: per frame or per position
         self._loss_means = eng.buf('img_head.loss_means', (K + 1,), torch.float32, dev)
         eng.lib.loss_means(loss, self._loss_means, K, Nv, s)       # what _parse_losses needs, inside the forward chain
-        self._ctx = dict(bctx=bctx, hctx=hctx, z=z, p=p, Nv=Nv, T=T, K=K, weight=weight, neg=neg, last=last)
+        self._ctx = dict(bctx=bctx, hctx=hctx, z=z, p=p, Nv=Nv, T=T, K=K, weight=weight, last=last)
         return loss
 
     def _hip_backward(self, gl):
@@ -484,12 +483,10 @@ class SimSiamBaseTracker(BaseTracker):
             raise RuntimeError('backward called without a matching forward_train')
         z, p, Nv = c['z'], c['p'], c['Nv']
         dev = p.device
-        s = eng.stream(dev)
         dp = eng.buf('img_head.dp', p.shape, BF16, dev)
         eng.p2p_chain_start(dev)
         gl = gl.contiguous().float()
-        eng.lib.cosine_loss_bwd(p[:Nv], z[:Nv], p[Nv:], z[Nv:], gl, dp[:Nv], dp[Nv:], Nv, p.shape[1], c['T'],
-                                c['K'], c['neg'], c['weight'], s)
+        self.img_head.loss_bwd_nhwc(eng, p, z, gl, dp, Nv, c['T'], c['K'], c['weight'])
         # split-K partials of the weight gradients are reduced by one table-driven launch per stage (data parallel: the
         # stage's gradients must be final before their all-reduce) or one for the whole step (single process)
         eng.defer_wgrad = os.environ.get('VFS_WGRAD_BATCH', '0') == '1'
