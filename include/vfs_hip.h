@@ -378,6 +378,31 @@ int vfs_p2p_allreduce_f64(double* buf, int n, const void* peers, int rank, int w
 int vfs_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float lr,
                  float momentum, float weight_decay, const void* skip_flag, vfs_stream_t stream);
 int vfs_scale(float* x, long long n, float scale, vfs_stream_t stream);
+/* ---- gradient clipping: optimizer_config = dict(grad_clip=dict(max_norm=..., norm_type=2)) (configs/r*_*.py:136), which
+ * apis/train.py:85-93 hands to mmcv's OptimizerHook; OptimizerHook.clip_grads calls torch.nn.utils.clip_grad_norm_ on the trainable
+ * parameters between loss.backward() and optimizer.step().  Here: one streaming reduction over the flat gradient arena, a finish
+ * that leaves norm and coefficient in device memory, and an update that reads the coefficient there - no host read in the step.
+ * norm_type: 2 or +infinity (anything else: VFS_ERR_ARG).
+ *
+ * vfs_grad_norm_rows: number of doubles in the partials buffer (host only; replaces nothing, it sizes the workspace).
+ * vfs_grad_norm_partial (clip_grad_norm_'s per-tensor torch.norm calls, OptimizerHook.clip_grads): every one of the
+ *   vfs_grad_norm_rows workgroups reduces its share of grads[0..n) (16-byte aligned; squares summed in double, or max |g|) and
+ *   writes partials[workgroup] (accumulate == 0) or combines with the value there (accumulate != 0: the further contiguous ranges
+ *   of trainable parameters).  One pass of the grid covers rows * 1024 floats.  No floating-point atomics: same bits on every run.
+ * vfs_grad_norm_finish (clip_grad_norm_'s norm of norms and clip_coef_clamped): one workgroup combines the rows in a fixed
+ *   order; out[0] = (float)total_norm, out[1] = (float)min(1, max_norm / (total_norm + 1e-6)); a NaN norm gives a NaN coefficient
+ *   (torch with error_if_nonfinite=False).  max_norm > 0. */
+int vfs_grad_norm_rows(int* rows);
+int vfs_grad_norm_partial(const float* grads, long long n, float norm_type, double* partials, int accumulate, vfs_stream_t stream);
+int vfs_grad_norm_finish(const double* partials, float norm_type, double max_norm, float* out, vfs_stream_t stream);
+/* vfs_sgd_step with the gradient taken as grads[i] * (*clip) (clip_grad_norm_'s in-place g.mul_(clip_coef_clamped) of
+ * OptimizerHook.clip_grads, folded into torch.optim.SGD.step; grads is NOT modified).  clip: device float, read when the kernel
+ * runs (vfs_grad_norm_finish's out + 1).  *clip == 1.0 gives exactly vfs_sgd_step's bits.  skip_flag as above. */
+int vfs_sgd_step_clip(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
+                      float weight_decay, const float* clip, const void* skip_flag, vfs_stream_t stream);
+/* x[0..n) *= *coef, coef a device float read when the kernel runs (clip_grad_norm_'s g.mul_(clip_coef_clamped) for a caller that
+ * drives the loop itself, OptimizerHook.clip_grads); x 16-byte aligned */
+int vfs_scale_by(float* x, long long n, const float* coef, vfs_stream_t stream);
 /* bf16 gradient buckets for the data-parallel all-reduce (opt-in, VFS_GRAD_BF16=1; the reference's DDP - apis/train.py:62-66 -
  * reduces fp32): dst = bf16(src * scale) before the collective, dst = float(src) after it; buffers 16-byte aligned */
 int vfs_f32_to_bf16(const float* src, vfs_bf16* dst, long long n, float scale, vfs_stream_t stream);

@@ -715,9 +715,49 @@ int vfs_simloss_norm_bwd(const float* x, const float* inv, const float* d, float
 
 int vfs_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
                  float weight_decay, const void* skip_flag, vfs_stream_t stream) {
-  return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
+  return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, nullptr, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
 }
 int vfs_scale(float* x, long long n, float scale, vfs_stream_t stream) { return vfs_scale_launch(x, n, scale, stream_of(stream)); }
+
+// gradient clipping: norm_type is 2 or +infinity, as a float (what torch's clip_grad_norm_ takes)
+static int grad_norm_type(const char* who, float norm_type, int* inf_norm) {
+  if (norm_type == 2.0f) *inf_norm = 0;
+  else if (norm_type == __builtin_inff()) *inf_norm = 1;
+  else return fail(VFS_ERR_ARG, who, "norm_type must be 2 or infinity");
+  return VFS_OK;
+}
+int vfs_grad_norm_rows(int* rows) {
+  if (!rows) return vfs_set_error(VFS_ERR_ARG, "grad_norm_rows: bad argument");
+  *rows = VFS_GRAD_NORM_ROWS;
+  return VFS_OK;
+}
+int vfs_grad_norm_partial(const float* grads, long long n, float norm_type, double* partials, int accumulate, vfs_stream_t stream) {
+  int inf_norm;
+  if (!grads || !partials) return vfs_set_error(VFS_ERR_ARG, "grad_norm_partial: null buffer");
+  if (n < 0) return vfs_set_error(VFS_ERR_ARG, "grad_norm_partial: n < 0");
+  if ((size_t)grads & 15) return vfs_set_error(VFS_ERR_ARG, "grad_norm_partial: 16-byte aligned gradients");
+  if (int rc = grad_norm_type("grad_norm_partial", norm_type, &inf_norm)) return rc;
+  return vfs_grad_norm_partial_launch(grads, n, inf_norm, partials, accumulate, stream_of(stream));
+}
+int vfs_grad_norm_finish(const double* partials, float norm_type, double max_norm, float* out, vfs_stream_t stream) {
+  int inf_norm;
+  if (!partials || !out) return vfs_set_error(VFS_ERR_ARG, "grad_norm_finish: null buffer");
+  if (int rc = grad_norm_type("grad_norm_finish", norm_type, &inf_norm)) return rc;
+  if (!(max_norm > 0.0)) return vfs_set_error(VFS_ERR_ARG, "grad_norm_finish: max_norm <= 0");
+  return vfs_grad_norm_finish_launch(partials, inf_norm, max_norm, out, stream_of(stream));
+}
+int vfs_sgd_step_clip(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
+                      float weight_decay, const float* clip, const void* skip_flag, vfs_stream_t stream) {
+  if (!params || !grads || !momentum_buf || !clip) return vfs_set_error(VFS_ERR_ARG, "sgd_step_clip: null buffer");
+  if (n < 0) return vfs_set_error(VFS_ERR_ARG, "sgd_step_clip: n < 0");
+  return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, clip, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
+}
+int vfs_scale_by(float* x, long long n, const float* coef, vfs_stream_t stream) {
+  if (!x || !coef) return vfs_set_error(VFS_ERR_ARG, "scale_by: null buffer");
+  if (n < 0) return vfs_set_error(VFS_ERR_ARG, "scale_by: n < 0");
+  if ((size_t)x & 15) return vfs_set_error(VFS_ERR_ARG, "scale_by: 16-byte aligned buffer");
+  return vfs_scale_by_launch(x, n, coef, stream_of(stream));
+}
 int vfs_f32_to_bf16(const float* src, vfs_bf16* dst, long long n, float scale, vfs_stream_t stream) {
   return vfs_f32_to_bf16_launch(src, dst, n, scale, stream_of(stream));
 }

@@ -388,10 +388,25 @@ int vfs_cosine_loss_bwd_launch(const LossArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------ SGD
 // torch.optim.SGD (configs/*:134): g += wd*p ; buf = momentum*buf + g ; p -= lr*buf
 // (a zero-initialised buf reproduces torch's "buf = g" on the first step)
+// CLIP: the gradient is g * (*clip) first - torch.nn.utils.clip_grad_norm_'s in-place scaling (mmcv OptimizerHook.clip_grads,
+// apis/train.py:85-93) folded into the update; the stored gradients stay as they are.  The product is handed on through an empty
+// asm: it is rounded on its own, and the compiler sees the rest of the update exactly as it sees the unclipped one (a value it knows
+// nothing about in place of a loaded one), so its contraction choices are the same and a coefficient of 1.0 gives the unclipped bits.
+template <bool CLIP>
+__device__ __forceinline__ float sgd_grad(float g, float c) {
+  if (!CLIP) return g;
+  float gs = g * c;
+#ifndef VFS_EMU
+  asm("" : "+v"(gs));
+#endif
+  return gs;
+}
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  long long n, float lr, float momentum, float wd,
+                                                  long long n, float lr, float momentum, float wd, const float* __restrict__ clip,
                                                   const unsigned long long* __restrict__ skip) {
   if (skip && *skip) return;      // a poisoned step (failed SyncBN exchange, vfs_p2p.h) leaves weights and momentum alone
+  const float c = CLIP ? *clip : 1.0f;
   const long long n4 = n >> 2;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
@@ -399,7 +414,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     f32x4 bv = reinterpret_cast<f32x4*>(buf)[i];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float gg = gv[q] + wd * pv[q];
+      const float gg = sgd_grad<CLIP>(gv[q], c) + wd * pv[q];
       bv[q] = momentum * bv[q] + gg;
       pv[q] -= lr * bv[q];
     }
@@ -408,15 +423,17 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long long i = (n4 << 2) + threadIdx.x;
-    const float gg = g[i] + wd * p[i];
+    const float gg = sgd_grad<CLIP>(g[i], c) + wd * p[i];
     buf[i] = momentum * buf[i] + gg;
     p[i] -= lr * buf[i];
   }
 }
-int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const unsigned long long* skip,
-                   hipStream_t s) {
+int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const float* clip,
+                   const unsigned long long* skip, hipStream_t s) {
   long long b = ((n >> 2) + 255) / 256;
-  hipLaunchKernelGGL(sgd_kernel, dim3((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b))), dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, skip);
+  const dim3 grid((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)));
+  if (clip) hipLaunchKernelGGL(sgd_kernel<true>, grid, dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, clip, skip);
+  else hipLaunchKernelGGL(sgd_kernel<false>, grid, dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, clip, skip);
   return vfs_check_launch("sgd");
 }
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ p, long long n, float scale) {
@@ -426,6 +443,93 @@ int vfs_scale_launch(float* p, long long n, float scale, hipStream_t s) {
   long long b = (n + 255) / 256;
   hipLaunchKernelGGL(scale_kernel, dim3((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b))), dim3(256), 0, s, p, n, scale);
   return vfs_check_launch("scale");
+}
+// x *= *coef, the scalar read from device memory when the kernel runs (vfs_amd.clip_grad_norm_: the coefficient never visits the host)
+__global__ __launch_bounds__(256) void scale_by_kernel(float* __restrict__ p, long long n, const float* __restrict__ coef) {
+  const float c = *coef;
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 v = reinterpret_cast<f32x4*>(p)[i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] *= c;
+    reinterpret_cast<f32x4*>(p)[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) p[(n4 << 2) + threadIdx.x] *= c;
+}
+int vfs_scale_by_launch(float* p, long long n, const float* coef, hipStream_t s) {
+  long long b = ((n >> 2) + 255) / 256;
+  hipLaunchKernelGGL(scale_by_kernel, dim3((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b))), dim3(256), 0, s, p, n, coef);
+  return vfs_check_launch("scale_by");
+}
+
+// ------------------------------------------------------------------ gradient norm (torch.nn.utils.clip_grad_norm_)
+// One streaming pass over a contiguous fp32 range: VFS_GRAD_NORM_ROWS workgroups (four per CU, every lane with up to four 16-byte
+// loads in flight - the grid is sized to the chip, a range of any length is swept by its stride loop), squares accumulated in
+// double, one double per workgroup written to ITS row of `rows`.  No floating-point atomics anywhere: a row's value depends on
+// the range alone, so the norm is the same bits on every run.  accumulate != 0 combines with what the row holds (the trainable
+// ranges of a model with frozen parameters in the middle are several segments: first launch overwrites, the others add).
+// INF: maximum of |g| instead; nan_max hands a NaN on from either side, as torch's max does.
+__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+template <bool INF>
+__device__ __forceinline__ double norm_combine(double a, double b) { return INF ? nan_max(a, b) : a + b; }
+// workgroup total of 256 threads, fixed order (xor butterfly per wave, then the four waves in index order); valid in thread 0
+template <bool INF>
+__device__ __forceinline__ double norm_block_total(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = norm_combine<INF>(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return norm_combine<INF>(norm_combine<INF>(norm_combine<INF>(sh[0], sh[1]), sh[2]), sh[3]);
+}
+template <bool INF>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, long long n, double* __restrict__ rows,
+                                                                int accumulate) {
+  __shared__ double sh[4];
+  const long long n4 = n >> 2;
+  double acc = 0.0;
+#pragma unroll 4
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc = INF ? nan_max(acc, (double)fabsf(v[q])) : acc + (double)v[q] * (double)v[q];
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const float v = g[(n4 << 2) + threadIdx.x];
+    acc = INF ? nan_max(acc, (double)fabsf(v)) : acc + (double)v * (double)v;
+  }
+  const double total = norm_block_total<INF>(acc, sh);
+  if (threadIdx.x == 0) rows[blockIdx.x] = accumulate ? norm_combine<INF>(rows[blockIdx.x], total) : total;
+}
+int vfs_grad_norm_partial_launch(const float* g, long long n, int inf_norm, double* rows, int accumulate, hipStream_t s) {
+  if (inf_norm) hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3(VFS_GRAD_NORM_ROWS), dim3(256), 0, s, g, n, rows, accumulate);
+  else hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3(VFS_GRAD_NORM_ROWS), dim3(256), 0, s, g, n, rows, accumulate);
+  return vfs_check_launch("grad_norm_partial");
+}
+// One workgroup: thread t combines rows 4t .. 4t+3 in index order, then the fixed tree above.  out[0] = the norm,
+// out[1] = torch's clip_coef_clamped = min(1, max_norm / (norm + 1e-6)); a NaN norm gives a NaN coefficient (NaN > 1 is false).
+// A launch of its own rather than the last-arriving workgroup of the reduction: with several segments only the last launch
+// could finish, and the second launch (a dependent boundary, under 2 us) needs no ticket word and no agent-scope hand-off.
+template <bool INF>
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ rows, double max_norm, float* __restrict__ out) {
+  static_assert(VFS_GRAD_NORM_ROWS == 4 * 256, "four rows per thread");
+  __shared__ double sh[4];
+  const int t = threadIdx.x;
+  double acc = rows[4 * t];
+#pragma unroll
+  for (int q = 1; q < 4; ++q) acc = norm_combine<INF>(acc, rows[4 * t + q]);
+  const double total = norm_block_total<INF>(acc, sh);
+  if (t == 0) {
+    const double norm = INF ? total : sqrt(total);
+    double c = max_norm / (norm + 1e-6);
+    if (c > 1.0) c = 1.0;
+    out[0] = (float)norm;
+    out[1] = (float)c;
+  }
+}
+int vfs_grad_norm_finish_launch(const double* rows, int inf_norm, double max_norm, float* out, hipStream_t s) {
+  if (inf_norm) hipLaunchKernelGGL(grad_norm_finish_kernel<true>, dim3(1), dim3(256), 0, s, rows, max_norm, out);
+  else hipLaunchKernelGGL(grad_norm_finish_kernel<false>, dim3(1), dim3(256), 0, s, rows, max_norm, out);
+  return vfs_check_launch("grad_norm_finish");
 }
 
 // bf16 gradient buckets for the data-parallel all-reduce (opt-in: halves the xGMI traffic of the 152.8 MB ResNet-50 gradient;

@@ -194,9 +194,15 @@ __device__ __forceinline__ int roll_src(int i, int T, int k) {  // index of roll
 }
 
 // fused SGD over the flat parameter arena (torch.optim.SGD, dampening 0, no nesterov)
-int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const unsigned long long* skip,
-                   hipStream_t s);
+// clip: nullptr, or the device coefficient the gradient is multiplied by (vfs_grad_norm_finish's out[1])
+int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const float* clip,
+                   const unsigned long long* skip, hipStream_t s);
 int vfs_scale_launch(float* p, long long n, float scale, hipStream_t s);
+int vfs_scale_by_launch(float* p, long long n, const float* coef, hipStream_t s);
+// gradient norm for clipping: per-workgroup partials of a range into rows[VFS_GRAD_NORM_ROWS], then norm and coefficient
+#define VFS_GRAD_NORM_ROWS 1024
+int vfs_grad_norm_partial_launch(const float* g, long long n, int inf_norm, double* rows, int accumulate, hipStream_t s);
+int vfs_grad_norm_finish_launch(const double* rows, int inf_norm, double max_norm, float* out, hipStream_t s);
 int vfs_f32_to_bf16_launch(const float* src, bf16_t* dst, long long n, float scale, hipStream_t s);
 int vfs_bf16_to_f32_launch(const bf16_t* src, float* dst, long long n, hipStream_t s);
 

@@ -86,6 +86,7 @@ class Engine:
         self.prof = None     # list collecting (kind, flops, start_event, end_event) when profiling
         self.prof_pool = None     # optional pre-created timing events for it
         self.tape = None
+        self.grad_norm_rows = None     # vfs_grad_norm_rows of the library, asked once (optim._grad_norm)
         # weight-gradient split-K partials: reduced per layer right after the kernel (default), or - inside the trackers'
         # backward chain (defer_wgrad) - kept in per-layer buffers and reduced by ONE table-driven launch per flush
         self.defer_wgrad = False
