@@ -49,8 +49,9 @@ int vfs_pack_weights(const void* desc, int ntensors, long long total_tiles, vfs_
 /* ---- convolution / linear: torch conv2d & linear call sites ---------------------------------
  * forward  (resnet.py:51-73,163-191,267-277 via mmcv ConvModule; sim_siam_head.py:78-111):
  *   y[N,Ho,Wo,Cout] = conv(x[N,H,W,Cin], wf) (+ bias)          Cin % 64 == 0, Cout % 64 == 0
- *   stats (optional): float[ceil(N*Ho*Wo/128)][2][Cout] per-128-pixel-block (sum, sumsq) of the
- *   stored bf16 outputs -- the BatchNorm batch statistics, free in the GEMM epilogue */
+ *   stats (optional): float[rows][2][Cout] per-128-pixel-block (sum, sumsq) of the
+ *   stored bf16 outputs -- the BatchNorm batch statistics, free in the GEMM epilogue; rows = ceil(N*Ho*Wo/128) linear blocks, or
+ *   the spatial tiles of the 3x3 halo kernel: vfs_conv_plan says which and how many */
 int vfs_conv_fwd(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats,
                  int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
                  int pad, vfs_stream_t stream);
@@ -65,7 +66,8 @@ int vfs_conv_fwd_coarse(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, cons
                         uint32_t* tickets, int coarse_log2, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
                         int stride, int pad, vfs_stream_t stream);
 /* 7x7/2 stem conv (resnet.py:422-434) on NHWC4 input, wf = [64][8][8][4].  stats rows: one per
- * spatial tile of 8x16 output pixels, N*ceil(Ho/8)*ceil(Wo/16) rows of [2][64] (image-major) */
+ * spatial tile of 8x16 output pixels, N*ceil(Ho/8)*ceil(Wo/16) rows of [2][64] (image-major); ceil(N*Ho*Wo/128) linear rows on
+ * the implicit-GEMM fallback (vfs_stem_plan reports the count in force) */
 int vfs_stem_fwd(const vfs_bf16* x4, const vfs_bf16* wf, vfs_bf16* y, float* stats, int N, int H,
                  int Wp, int Ho, int Wo, vfs_stream_t stream);
 /* dgrad (autograd of the above): dx[N,H,W,Cin] = conv_transpose(dy[N,Ho,Wo,Cout], wd) (+ add) */
@@ -150,6 +152,34 @@ int vfs_conv_wgrad_inl(const vfs_bf16* dy, const vfs_bf16* x, const float* in_bn
                        int pad, int nsplit, int pix_per_split, vfs_stream_t stream);
 /* db[Cout] += column sums of dy[M][Cout] (linear bias gradient) */
 int vfs_bias_grad(const vfs_bf16* dy, float* db, int M, int C, vfs_stream_t stream);
+
+/* ---- tiling plan queries (host only: nothing is launched) -----------------------------------------------------------------
+ * The library alone decides which kernel family a convolution launch lands in and how its statistics rows are laid out; a host
+ * that sizes the row buffers, tells the BatchNorm passes how many rows to sum, or splits a weight gradient asks here.  The
+ * answers hold for the options in force (include/vfs_hip_tuning.h) at the time of the call and are what the entry points above do
+ * with the same geometry: each query builds the launch's arguments and asks the dispatcher's own predicate.  All geometry
+ * arguments are those of the FORWARD convolution, as in the entry points.  VFS_ERR_ARG on a null out-pointer, G < 1 or
+ * dilation < 1.
+ *
+ * vfs_conv_plan: dgrad = 0 - vfs_conv_fwd / _coarse / _dilated / _bnin writing `stats` rows [2][Cout] for y[N,Ho,Wo,Cout];
+ *                dgrad = 1 - vfs_conv_dgrad* (stride 1 or 2), vfs_conv_dgrad_bn* writing `bn_partial` rows [2][Cin] for dx[N,H,W,Cin].
+ *   halo : 1 when the 3x3 halo-tile kernel takes the launch (rows are spatial tiles, image-major), 0: implicit-GEMM family
+ *          (rows are linear 128-pixel blocks of the output)
+ *   rows : statistics rows PER GROUP that ONE launch over all N images writes, when the N images form G BatchNorm groups of
+ *          N / G consecutive images (the buffer holds G * rows rows, group after group); 0: a group does not own whole rows -
+ *          launch once per group (N / G images, G = 1).  Always 0 for a stride-2 dgrad, which writes no rows.
+ *   pairs: 1 when the halo kernels of this layer tile whole images of at most 8x8 pixels in PAIRS: vfs_conv_fwd_bnin /
+ *          vfs_conv_wgrad_bnin then need an even in_npg.
+ * vfs_stem_plan: rows per group (as above) that vfs_stem_fwd writes - one per 8x16 output tile with the direct kernel, one per
+ *   128 output pixels when it falls back to the implicit-GEMM kernel (option stem_direct = 0, inputs of 4 GiB and more).
+ * vfs_conv_wgrad_plan: halo = 1 when vfs_conv_wgrad / _bnin / _inl run the 3x3 halo kernel; ntiles = the spatial tiles that
+ *   kernel splits over (it takes min(nsplit, ntiles) splits of ceil(ntiles / nsplit) tiles), 0 when halo = 0 (the generic kernel
+ *   splits over linear pixel ranges of pix_per_split pixels). */
+int vfs_conv_plan(int dgrad, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                  int dilation, int G, int* halo, int* rows, int* pairs);
+int vfs_stem_plan(int N, int H, int Wp, int Ho, int Wo, int G, int* rows);
+int vfs_conv_wgrad_plan(int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int* halo,
+                        int* ntiles);
 
 /* ---- BatchNorm / SyncBN + activation (torch batch_norm in ConvModule; configs/r*_*.py:9,15) ------
  * G = number of independent BN batches inside the tensor (the two views), bpg partial blocks

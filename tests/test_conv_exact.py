@@ -186,9 +186,9 @@ def run_fwd(be, regime, N, H, W, Cin, Cout, k, stride, pad):
     exact_ok(k * k * Cin, x, w)
     wf, _ = pack(be, w)
     xh = d(nhwc(x))
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo)
-    linear = not conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad)
-    halves = 2 if (N % 2 == 0 and conv_stats_rows(N, 2, H, W, Cin, Cout, k, stride, pad, Ho, Wo) is not None) else 1
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib)
+    linear = not conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=lib)
+    halves = 2 if (N % 2 == 0 and conv_stats_rows(N, 2, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib) is not None) else 1
     ref0 = nhwc64(F.conv2d(x.double(), w.double(), None, stride, pad))
     for b, flags in ((bias, (1,)), (None, (1, 0))):       # bias-free: statistics rows on the matrix cores (1) / per element (0)
         ref = ref0 + b.double() if b is not None else ref0
@@ -298,8 +298,8 @@ def test_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout,
     scale = 2.0 ** ints(g, (Cin,), -1, 1)
     shift, mean = ints(g, (Cin,), -4, 4) / 2, ints(g, (Cin,), -4, 4) / 2
     bnp = torch.stack([scale, shift, mean, torch.ones(Cin)], 0).reshape(1, 4, Cin).contiguous()
-    nblk = conv_stats_rows(N, 1, H, W, Cout, Cin, k, 1, pad, H, W)       # the dgrad as a conv producing [N,H,W,Cin]
-    linear = not conv_halo_eligible(N, H, W, Cout, Cin, k, 1, pad)
+    nblk = conv_stats_rows(N, 1, H, W, Cout, Cin, k, 1, pad, H, W, lib=lib)       # the dgrad as a conv producing [N,H,W,Cin]
+    linear = not conv_halo_eligible(N, H, W, Cout, Cin, k, 1, pad, lib=lib)
     xq, gq = x.double().reshape(M, Cin), want.double().reshape(M, Cin)
     ym = ints(g, (N, H, W, Cin), -2, 2)                     # activation of the unit the gradient belongs to (mask operand)
     pa, pb = nan_like((nblk, 2, Cin), dev, torch.float32), nan_like((nblk, 2, Cin), dev, torch.float32)
@@ -368,8 +368,8 @@ def test_wgrad(backend, regime, N, H, W, Cin, Cout, k, stride, pad):
     g = torch.Generator().manual_seed(N * 100 + H + Cout + 2)
     Ho, Wo = out_size(H, W, k, stride, pad)
     x, _, _, dy, _ = operands(regime, g, N, H, W, Cin, Cout, k, Ho, Wo)
-    is_halo = wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad)
-    nsplit, pps = wgrad_splits(N * Ho * Wo, Cout, k * k * Cin, target_blocks=12, halo_geom=(N, H, W, Cin) if is_halo else None)
+    is_halo = wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=backend.lib)
+    nsplit, pps = wgrad_splits(N * Ho * Wo, Cout, k * k * Cin, target_blocks=12, halo_geom=(N, H, W, Cin) if is_halo else None, lib=backend.lib)
     run_wgrad(backend, regime, x, dy, k, stride, pad, nsplit, pps, is_halo)
 
 
@@ -551,7 +551,7 @@ def test_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
     small_ok(regime, ref)
     want = expect_bf16(ref)
     rawd, bnpd = d(raw.to(BF16)), d(bnp)
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, 1, pad, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, 1, pad, H, W, lib=lib)
     y, st = nan_like((N, H, W, Cout), dev), nan_like((nblk, 2, Cout), dev, torch.float32)
     lib.conv_fwd_bnin(rawd, bnpd, npg, wf, y, None, st, N, H, W, Cin, H, W, Cout, k, k, 1, pad, None)
     assert_bits(y, want, 'conv_fwd_bnin')
@@ -560,7 +560,7 @@ def test_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
     exact_ok(M, act, dy)
     grad0 = ints(g, (Cout, Cin, k, k), -5, 5)
     wantg = (grad0.double() + torch.nn.grad.conv2d_weight(act_nchw, (Cout, Cin, k, k), dy.double(), 1, pad)).float()
-    nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, target_blocks=12, halo_geom=(N, H, W, Cin) if k == 3 else None)
+    nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, target_blocks=12, halo_geom=(N, H, W, Cin) if k == 3 else None, lib=lib)
     # 1x1: the generic kernel, linear pixel ranges - every slice is compared; 3x3: the halo kernel's own split count
     partial = nan_like((nsplit, Cout, Cin), dev, torch.float32) if k == 1 else torch.zeros(nsplit, Cout, 9 * Cin, device=dev)
     grad = d(grad0.clone())

@@ -37,7 +37,7 @@ def run_conv_case(be, N, H, W, Cin, Cout, k, stride, pad, wgrad_blocks=12):
     xh = d(nhwc(x))
     M = N * Ho * Wo
     y = torch.full((N, Ho, Wo, Cout), float('nan'), dtype=torch.bfloat16, device=be.dev)
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo)     # spatial tiles (halo kernels) or linear blocks
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib)     # spatial tiles (halo kernels) or linear blocks
     stats = torch.full((nblk, 2, Cout), float('nan'), device=be.dev)
     bias = torch.randn(Cout, generator=g)
     lib.conv_fwd(xh, wf, y, d(bias), stats, N, H, W, Cin, Ho, Wo, Cout, k, k, stride, pad, None)
@@ -49,7 +49,7 @@ def run_conv_case(be, N, H, W, Cin, Cout, k, stride, pad, wgrad_blocks=12):
     # kernel, spatial tiles in the halo kernel); what the consumers rely on is that the blocks of
     # the first / second half of the batch (the two views) are the first / second half of the rows
     st = stats.cpu()
-    halves = 2 if (N % 2 == 0 and conv_stats_rows(N, 2, H, W, Cin, Cout, k, stride, pad, Ho, Wo) is not None) else 1
+    halves = 2 if (N % 2 == 0 and conv_stats_rows(N, 2, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib) is not None) else 1
     for h in range(halves):
         rows = slice(h * nblk // halves, (h + 1) * nblk // halves)
         pix = yf[h * M // halves:(h + 1) * M // halves].double()
@@ -65,8 +65,8 @@ def run_conv_case(be, N, H, W, Cin, Cout, k, stride, pad, wgrad_blocks=12):
     dx = torch.full((N, H, W, Cin), float('nan'), dtype=torch.bfloat16, device=be.dev)
     lib.conv_dgrad(d(nhwc(dy)), wd, dx, d(nhwc(add)), N, H, W, Cin, Ho, Wo, Cout, k, k, stride, pad, None)
     assert relerr(nchw(dx.cpu()), xr.grad + add) < 6e-3
-    halo = (N, H, W, Cin) if wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad) else None
-    nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, target_blocks=wgrad_blocks, halo_geom=halo)
+    halo = (N, H, W, Cin) if wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=lib) else None
+    nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, target_blocks=wgrad_blocks, halo_geom=halo, lib=lib)
     partial = torch.full((nsplit, Cout, k * k * Cin), float('nan'), device=be.dev)
     grad = torch.ones(Cout, Cin, k, k, device=be.dev)
     lib.conv_wgrad(d(nhwc(dy)), xh, partial, grad, N, H, W, Cin, Ho, Wo, Cout, k, k, stride, pad, nsplit, pps, None)
@@ -128,7 +128,7 @@ def test_forward_statistics_rows_without_bias(backend, N, H, W, Cin, Cout, k, st
     wf, _ = pack(backend, w)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     M = N * Ho * Wo
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib)
     outs = []
     for flag in (1, 0):
         lib.set_option(b'igemm_mfma_stats', flag)
@@ -278,7 +278,7 @@ def test_dgrad_fused_bn_backward_statistics(backend, N, H, W, Cin, Cout, k, G, m
                       + 0.5 * torch.randn(N, H, W, Cin, generator=g)))
     dx0 = torch.full((N, H, W, Cin), float('nan'), dtype=torch.bfloat16, device=dev)
     lib.conv_dgrad(dy, wd, dx0, add, N, H, W, Cin, H, W, Cout, k, k, 1, pad, None)
-    nblk = conv_stats_rows(N, G, H, W, Cout, Cin, k, 1, pad, H, W) * G     # the dgrad as a conv producing [N,H,W,Cin]
+    nblk = conv_stats_rows(N, G, H, W, Cout, Cin, k, 1, pad, H, W, lib=lib) * G     # the dgrad as a conv producing [N,H,W,Cin]
     partial = torch.full((nblk, 2, Cin), float('nan'), device=dev)
     dx1 = torch.full((N, H, W, Cin), float('nan'), dtype=torch.bfloat16, device=dev)
     ymask = d(y.to(torch.bfloat16)) if mask == 'y' else None
@@ -333,7 +333,7 @@ def test_dgrad_add_gated_by_bit_packed_mask(backend, N, H, W, Cin, Cout, k):
     assert torch.equal(dx0.cpu(), dx1.cpu())
     # with fused BatchNorm-backward statistics
     M = N * H * W
-    nblk = conv_stats_rows(N, 1, H, W, Cout, Cin, k, 1, pad, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cout, Cin, k, 1, pad, H, W, lib=lib)
     x = rb(torch.randn(N, H, W, Cin, generator=gen))
     bnp = torch.stack([torch.rand(Cin, generator=gen) + 0.5, torch.randn(Cin, generator=gen), torch.randn(Cin, generator=gen) * 0.1,
                        torch.rand(Cin, generator=gen) + 0.5], 0).reshape(1, 4, Cin).contiguous()
@@ -370,7 +370,7 @@ def test_conv_with_folded_input_batchnorm(backend, N, H, W, Cin, Cout, G):
     rawd, bnpd = d(raw), d(bnp)
     act = torch.empty(N, H, W, Cin, dtype=torch.bfloat16, device=dev)
     lib.bn_act(rawd, bnpd, None, None, None, act, M, Cin, M // G, 1, None)
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 3, 1, 1, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 3, 1, 1, H, W, lib=lib)
     y0 = torch.full((N, H, W, Cout), float('nan'), dtype=torch.bfloat16, device=dev)
     y1 = torch.full_like(y0, float('nan'))
     st0 = torch.full((nblk, 2, Cout), float('nan'), device=dev)
@@ -379,7 +379,7 @@ def test_conv_with_folded_input_batchnorm(backend, N, H, W, Cin, Cout, G):
     lib.conv_fwd_bnin(rawd, bnpd, npg, wf, y1, None, st1, N, H, W, Cin, H, W, Cout, 3, 3, 1, 1, None)
     assert torch.equal(y1.cpu(), y0.cpu()) and torch.equal(st1.cpu(), st0.cpu())
     dy = d(rb(torch.randn(N, H, W, Cout, generator=g)).to(torch.bfloat16))
-    nsplit, pps = wgrad_splits(M, Cout, 9 * Cin, target_blocks=12, halo_geom=(N, H, W, Cin))
+    nsplit, pps = wgrad_splits(M, Cout, 9 * Cin, target_blocks=12, halo_geom=(N, H, W, Cin), lib=lib)
     partial = torch.zeros(nsplit, Cout, 9 * Cin, device=dev)
     g0, g1 = torch.zeros(Cout, Cin, 3, 3, device=dev), torch.zeros(Cout, Cin, 3, 3, device=dev)
     lib.conv_wgrad(dy, act, partial, g0, N, H, W, Cin, H, W, Cout, 3, 3, 1, 1, nsplit, pps, None)
@@ -414,7 +414,7 @@ def test_conv1x1_with_folded_input_batchnorm(backend, N, H, W, Cin, Cout, G):
     rawd, bnpd = d(raw), d(bnp)
     act = torch.empty(N, H, W, Cin, dtype=torch.bfloat16, device=dev)
     lib.bn_act(rawd, bnpd, None, None, None, act, M, Cin, M // G, 1, None)
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 1, 1, 0, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 1, 1, 0, H, W, lib=lib)
     y0 = torch.full((N, H, W, Cout), float('nan'), dtype=torch.bfloat16, device=dev)
     y1 = torch.full_like(y0, float('nan'))
     st0 = torch.full((nblk, 2, Cout), float('nan'), device=dev)
@@ -578,7 +578,7 @@ def _sweep_shapes(n, seed):
 @pytest.mark.parametrize('N,H,W,Cin,Cout,k,stride,pad', _sweep_shapes(28, 20260927))
 def test_conv_shape_sweep(backend, N, H, W, Cin, Cout, k, stride, pad):
     """forward (+ statistics rows), dgrad (+ residual add) and wgrad of every sampled problem vs torch: exercises the
-    host mirrors of the tiling rules (conv_halo_eligible / conv_stats_rows / wgrad_splits) together with the kernels"""
+    library's tiling plan as the host asks for it (conv_halo_eligible / conv_stats_rows / wgrad_splits) together with the kernels"""
     run_conv_case(backend, N, H, W, Cin, Cout, k, stride, pad)
 
 
@@ -625,7 +625,7 @@ def test_halo_deep_schedule_matches_two_stage(backend, N, H, W, Cin, Cout):
     wf, wd = pack(backend, w)
     dy = rb(torch.randn(N, Cout, H, W, generator=g))
     add = rb(torch.randn(N, Cin, H, W, generator=g))
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 3, 1, 1, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, 3, 1, 1, H, W, lib=lib)
     outs = []
     for deep in (256, 0):
         lib.set_option(b'halo_deep_max', deep)
@@ -672,7 +672,7 @@ def test_conv_forward_coarse_statistics_rows(backend, N, H, W, Cin, Cout, k, L):
     x = rb(torch.randn(N, Cin, H, W, generator=g))
     w = rb(torch.randn(Cout, Cin, k, k, generator=g) * (2.0 / (Cin * k * k)) ** 0.5)
     wf, _ = pack(backend, w)
-    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, 1, pad, H, W)
+    nblk = conv_stats_rows(N, 1, H, W, Cin, Cout, k, 1, pad, H, W, lib=lib)
     ng = (nblk + (1 << L) - 1) >> L
     y0 = torch.full((N, H, W, Cout), float('nan'), dtype=torch.bfloat16, device=dev)
     s0 = torch.full((nblk, 2, Cout), float('nan'), device=dev)

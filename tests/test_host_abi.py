@@ -37,6 +37,39 @@ def test_labelprop_workspace_query_is_host_only():
         lib.labelprop_workspace_bytes(60, 107, None)
 
 
+def test_plan_queries_are_host_only():
+    """vfs_conv_plan / vfs_conv_wgrad_plan / vfs_stem_plan of the product library answer without a GPU, follow the options in force,
+    and refuse a null out-pointer.  3 images of 14 x 14: 3 x 2 x 1 tiles of 8x16 pixels, ceil(588 / 128) = 5 linear blocks"""
+    from vfs_amd.packing import conv_plan, stem_stats_rows, wgrad_halo_tiles
+    lib = _lib.VfsLib(build.build_hip())
+    geom = (3, 14, 14, 64, 128, 3, 1, 1)
+    assert conv_plan(3, 1, 14, 14, 64, 128, 3, 1, 1, 14, 14, lib=lib) == (True, 6, False)
+    assert conv_plan(3, 1, 14, 14, 64, 128, 3, 1, 1, 14, 14, dgrad=True, lib=lib) == (True, 3 * 1 * 1 * 2, False)      # dx has 64 channels: 16x16 tiles, two rows each
+    assert conv_plan(3, 3, 14, 14, 64, 128, 3, 1, 1, 14, 14, lib=lib).rows == 2 and conv_plan(3, 2, 14, 14, 64, 128, 3, 1, 1, 14, 14, lib=lib).rows is None
+    assert conv_plan(4, 2, 8, 8, 64, 128, 3, 1, 1, 8, 8, lib=lib) == (True, 1, True) and conv_plan(4, 4, 8, 8, 64, 128, 3, 1, 1, 8, 8, lib=lib).rows is None
+    assert conv_plan(2, 1, 16, 16, 64, 128, 3, 2, 1, 8, 8, lib=lib) == (False, 1, False)
+    assert conv_plan(2, 1, 16, 16, 64, 128, 3, 2, 1, 8, 8, dgrad=True, lib=lib) == (False, None, False)      # a strided dgrad writes no rows
+    assert conv_plan(2, 1, 16, 16, 64, 128, 3, 1, 2, 16, 16, dil=2, lib=lib).halo is False
+    assert wgrad_halo_tiles(*geom, lib=lib) == 6 and wgrad_halo_tiles(5, 8, 8, 64, 64, 3, 1, 1, lib=lib) == 3 and wgrad_halo_tiles(2, 16, 16, 64, 128, 3, 2, 1, lib=lib) == 0
+    assert stem_stats_rows(4, 2, 64, 64, 32, 32, lib=lib) == 2 * 4 * 2
+    for name, value, fwd, tiles, stem in ((b'halo', 0, (False, 5, False), 0, 16), (b'halo_min_fill', 100, (False, 5, False), 0, 16),
+                                          (b'stem_direct', 0, (True, 6, False), 6, 2 * 32 * 32 // 128)):
+        lib.set_option(name, value)
+        try:
+            assert conv_plan(3, 1, 14, 14, 64, 128, 3, 1, 1, 14, 14, lib=lib) == fwd, name
+            assert wgrad_halo_tiles(*geom, lib=lib) == tiles, name
+            assert stem_stats_rows(4, 2, 64, 64, 32, 32, lib=lib) == stem, name
+        finally:
+            lib.set_option(name, OPTION_DEFAULTS[name.decode()])
+    out = torch.zeros(3, dtype=torch.int32)
+    with pytest.raises(_lib.VfsError, match='conv_plan: bad argument'):
+        lib.conv_plan(0, 3, 14, 14, 64, 14, 14, 128, 3, 3, 1, 1, 1, 1, out, out[1:], None)
+    with pytest.raises(_lib.VfsError, match='conv_wgrad_plan: bad argument'):
+        lib.conv_wgrad_plan(3, 14, 14, 64, 14, 14, 128, 3, 3, 1, 1, None, out)
+    with pytest.raises(_lib.VfsError, match='stem_plan: bad argument'):
+        lib.stem_plan(4, 64, 64, 32, 32, 2, None)
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(_lib.VfsError):
         _lib.VfsLib(str(tmp_path / 'libvfs_hip.so'))
@@ -342,6 +375,16 @@ def _argument_error_cases():
     case('conv_fwd_dilated-size', 'conv_fwd_dilated', (P, P, P, None, None) + g3 + (2, None), SHAPE,
          'conv_fwd_dilated: output size does not match (H + 2 pad - dilation (K - 1) - 1) / stride + 1')
     case('stem_fwd-odd-width', 'stem_fwd', (P, P, P, None, 1, 32, 33, 16, 16, None), SHAPE, 'stem_fwd: padded width must be even')
+    # ---- plan queries: (dgrad, geometry, dilation, G, halo, rows, pairs) / (N, H, Wp, Ho, Wo, G, rows) / (geometry, halo, ntiles)
+    for i in range(3):
+        outs = tuple(None if j == i else P for j in range(3))
+        case(f'conv_plan-null-out{i}', 'conv_plan', (0,) + g3 + (1, 1) + outs, ARG, 'conv_plan: bad argument')
+    case('conv_plan-G0', 'conv_plan', (0,) + g3 + (1, 0, P, P, P), ARG, 'conv_plan: bad argument')
+    case('conv_plan-dilation0', 'conv_plan', (0,) + g3 + (0, 1, P, P, P), ARG, 'conv_plan: bad argument')
+    case('stem_plan-null-out', 'stem_plan', (2, 32, 32, 16, 16, 1, None), ARG, 'stem_plan: bad argument')
+    case('stem_plan-G0', 'stem_plan', (2, 32, 32, 16, 16, 0, P), ARG, 'stem_plan: bad argument')
+    case('conv_wgrad_plan-null-halo', 'conv_wgrad_plan', g3 + (None, P), ARG, 'conv_wgrad_plan: bad argument')
+    case('conv_wgrad_plan-null-ntiles', 'conv_wgrad_plan', g3 + (P, None), ARG, 'conv_wgrad_plan: bad argument')
 
     # ---- input pipeline: (.., imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean x 3, std x 3)
     norm = (123.675, 116.28, 103.53, 58.395, 57.12, 57.375, None)

@@ -54,8 +54,8 @@ def main():
         dy = torch.randn(N, Ho, Wo, Cout, device=dev).to(torch.bfloat16)
         dx = torch.empty(N, H, W, Cin, device=dev, dtype=torch.bfloat16)
         stats = torch.empty((M + 127) // 128 * 2 * Cout, device=dev)
-        halo = (N, H, W, Cin) if wgrad_halo_eligible(N, H, W, Cin, Cout, k, st, pad) else None
-        nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, halo_geom=halo)
+        halo = (N, H, W, Cin) if wgrad_halo_eligible(N, H, W, Cin, Cout, k, st, pad, lib=lib) else None
+        nsplit, pps = wgrad_splits(M, Cout, k * k * Cin, halo_geom=halo, lib=lib)
         nsplit0, pps0 = wgrad_splits(M, Cout, k * k * Cin)
         partial0 = torch.empty(nsplit0 * Cout * k * k * Cin, device=dev)
         partial = torch.empty(nsplit * Cout * k * k * Cin, device=dev)

@@ -35,7 +35,7 @@ def main():
         wf = torch.randn(C, 3, 3, C, device=dev).to(torch.bfloat16)
         y = torch.empty(N, H, W, C, device=dev, dtype=torch.bfloat16)
         stats = torch.empty((M + 127) // 128 * 2 * C, device=dev)
-        nsplit, pps = wgrad_splits(M, C, 9 * C, halo_geom=(N, H, W, C))
+        nsplit, pps = wgrad_splits(M, C, 9 * C, halo_geom=(N, H, W, C), lib=lib)
         partial = torch.empty(nsplit * C * 9 * C, device=dev)
         grad = torch.zeros(C, C, 3, 3, device=dev)
         fl = 2.0 * M * C * 9 * C

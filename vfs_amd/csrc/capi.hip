@@ -70,6 +70,13 @@ static ConvArgs conv_dgrad_args(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16
   a.src = dy; a.wgt = wd; a.out = dx; a.add = add; a.Cout = Cin;
   return a;
 }
+// the 7x7 / stride-2 stem on NHWC4 input, and which of its two kernels takes it: the direct kernel (stem.hip), else GATHER_STEM
+static ConvArgs stem_fwd_args(const vfs_bf16* x4, const vfs_bf16* wf, vfs_bf16* y, float* stats, int N, int H, int Wp, int Ho, int Wo) {
+  ConvArgs a = conv_fwd_args(x4, wf, y, nullptr, stats, N, H, Wp, 4, Ho, Wo, 64, 7, 7, 2, 3);
+  a.g.Ktot = 256;      // 8 x 8 x 4: the taps and channels as the stem gather pads them (vfs_conv.h, GATHER_STEM)
+  return a;
+}
+static bool stem_takes_direct(const ConvArgs& a) { return vfs_option_stem_direct && (size_t)a.g.N * a.g.H * a.g.W * 8 < 0xFFFFFFF0ull; }
 static int set_add_mask(ConvArgs& a, const vfs_bf16* add, const uint8_t* add_mask, int N, int H, int W, int Cin) {
   if (!add_mask) return VFS_OK;
   if (!add || Cin % 64) return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad: add_mask needs an add operand and Cin % 64 == 0");
@@ -278,8 +285,7 @@ int vfs_conv_fwd_bnin(const vfs_bf16* x_raw, const float* in_bnp, int in_npg, co
   // round 6: also the 1x1 / stride-1 forward of the implicit-GEMM kernel (the conv2 -> conv3 edge), groups of whole 128-pixel tiles
   const bool pw = KH * KW == 1 && stride == 1 && pad == 0 && H == Ho && W == Wo && Cin % 64 == 0 && ((long long)in_npg * H * W) % 128 == 0;
   if (pw) return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
-  if (!vfs_option_halo || Cin % 64 || (size_t)N * H * W * Cin * 2 >= 0xFFFFFFF0ull || !vfs_conv_halo_eligible(a, GATHER_FWD) ||
-      (smallw && in_npg % 2))
+  if (!vfs_takes_halo(a, GATHER_FWD) || (smallw && in_npg % 2))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_fwd_bnin: the 3x3/stride-1 halo-tile kernel and the 1x1/stride-1 kernel fold the input BatchNorm");
   return vfs_conv_igemm_dispatch(a, GATHER_FWD, stream_of(stream));
 }
@@ -287,9 +293,8 @@ int vfs_conv_fwd_bnin(const vfs_bf16* x_raw, const float* in_bnp, int in_npg, co
 int vfs_stem_fwd(const vfs_bf16* x4, const vfs_bf16* wf, vfs_bf16* y, float* stats, int N, int H, int Wp, int Ho, int Wo,
                  vfs_stream_t stream) {
   if (Wp & 1) return vfs_set_error(VFS_ERR_SHAPE, "stem_fwd: padded width must be even");
-  ConvArgs a = conv_fwd_args(x4, wf, y, nullptr, stats, N, H, Wp, 4, Ho, Wo, 64, 7, 7, 2, 3);
-  a.g.Ktot = 256;      // 8 x 8 x 4: the taps and channels as the stem gather pads them (vfs_conv.h, GATHER_STEM)
-  if (vfs_option_stem_direct && (size_t)N * H * Wp * 8 < 0xFFFFFFF0ull) return vfs_stem_fwd_direct_launch(a, stream_of(stream));
+  const ConvArgs a = stem_fwd_args(x4, wf, y, stats, N, H, Wp, Ho, Wo);
+  if (stem_takes_direct(a)) return vfs_stem_fwd_direct_launch(a, stream_of(stream));
   return vfs_conv_igemm_dispatch(a, GATHER_STEM, stream_of(stream));
 }
 
@@ -315,7 +320,7 @@ int vfs_conv_dgrad_bn_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* 
   a.bn.x = bn_x; a.bn.y = bn_y; a.bn.bnp = bnp; a.bn.partial = bn_partial; a.bn.mpg = bn_mpg; a.bn.relu = bn_relu;
   // a statistics row must belong to ONE group: spatial tiles never straddle images (halo kernels: groups of whole
   // images), linear blocks are 128 pixels
-  const bool tiles = vfs_option_halo && Cout % 64 == 0 && vfs_conv_halo_eligible(a, GATHER_DGRAD);
+  const bool tiles = vfs_takes_halo(a, GATHER_DGRAD);
   if (bn_mpg < M && (tiles ? bn_mpg % ((long long)H * W) != 0 : bn_mpg % 128 != 0))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad_bn: groups must be whole images (tile kernels) / multiples of 128 pixels");
   return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
@@ -331,7 +336,7 @@ int vfs_conv_wgrad(const vfs_bf16* dy, const vfs_bf16* x, float* partial, float*
                    int Wo, int Cout, int KH, int KW, int stride, int pad, int nsplit, int pix_per_split, vfs_stream_t stream) {
   const WgradArgs a = wgrad_args(dy, x, nullptr, 0, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, nsplit, pix_per_split);
   int rc;
-  if (vfs_option_halo && vfs_wgrad_halo_eligible(a, GATHER_FWD)) {
+  if (vfs_takes_halo(a)) {
     rc = vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);   // may use fewer splits than offered
   } else {
     rc = vfs_conv_wgrad_dispatch(a, GATHER_FWD, stream_of(stream));
@@ -349,7 +354,7 @@ int vfs_conv_wgrad_bnin(const vfs_bf16* dy, const vfs_bf16* x_raw, const float* 
     if (rc1) return rc1;
     return finish_wgrad(a, grad, nsplit, Cin, 0, nullptr, stream_of(stream));      // (this kernel takes every plan as offered)
   }
-  if (!vfs_option_halo || !vfs_wgrad_halo_eligible(a, GATHER_FWD) || (vfs_small_map(H, W) && in_npg % 2))
+  if (!vfs_takes_halo(a) || (vfs_small_map(H, W) && in_npg % 2))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad_bnin: the 3x3/stride-1 halo-tile kernel and the 1x1/stride-1 kernel fold the input BatchNorm");
   int rc = vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);
   if (rc) return rc;
@@ -364,7 +369,7 @@ int vfs_conv_wgrad_inl(const vfs_bf16* dy, const vfs_bf16* x, const float* in_bn
   if (in_bnp && in_npg <= 0) return vfs_set_error(VFS_ERR_ARG, "conv_wgrad_inl: images per BatchNorm group of the input");
   WgradArgs a = wgrad_args(dy, x, in_bnp, in_bnp ? in_npg : 0, partial, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, nsplit, pix_per_split);
   a.grad = grad; a.tickets = tickets;
-  if (vfs_option_halo && vfs_wgrad_halo_eligible(a, GATHER_FWD) && !(in_bnp && vfs_small_map(H, W) && in_npg % 2))
+  if (vfs_takes_halo(a) && !(in_bnp && vfs_small_map(H, W) && in_npg % 2))
     return vfs_wgrad_halo_dispatch(a, stream_of(stream), &nsplit);
   if (in_bnp) return vfs_set_error(VFS_ERR_SHAPE, "conv_wgrad_inl: only the 3x3/stride-1 halo-tile kernel folds the input BatchNorm");
   return vfs_conv_wgrad_dispatch(a, GATHER_FWD, stream_of(stream));
@@ -377,6 +382,42 @@ int vfs_stem_wgrad(const vfs_bf16* dy, const vfs_bf16* x4, float* partial, float
   int rc = vfs_conv_wgrad_dispatch(a, GATHER_STEM, stream_of(stream));
   if (rc) return rc;
   return finish_wgrad(a, grad, nsplit, 3, 1, nullptr, stream_of(stream));      // (this kernel takes every plan as offered)
+}
+
+// ---- the tiling plan behind the launches above (host only: nothing is launched).  Each query builds the argument struct with the
+// entry point's own builder and asks the predicate its dispatcher asks.
+// rows of ONE launch over all G groups, per group - or 0: a group does not own whole rows
+static int rows_per_group(bool tiles, int total, int N, int G, long long pixels_per_image) {
+  if (N % G) return 0;
+  if (tiles) return total % G == 0 ? total / G : 0;      // (spatial tiles never straddle images; whole image PAIRS: total = N / 2)
+  return G == 1 || ((N / G) * pixels_per_image) % 128 == 0 ? (total + G - 1) / G : 0;
+}
+int vfs_conv_plan(int dgrad, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int dilation,
+                  int G, int* halo, int* rows, int* pairs) {
+  if (!halo || !rows || !pairs || G < 1 || dilation < 1) return vfs_set_error(VFS_ERR_ARG, "conv_plan: bad argument");
+  ConvArgs a = dgrad ? conv_dgrad_args(nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)
+                     : conv_fwd_args(nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
+  a.g.dil = dilation;
+  *halo = vfs_takes_halo(a, dgrad ? GATHER_DGRAD : GATHER_FWD);
+  *pairs = *halo && vfs_small_map(a.g.H, a.g.W);
+  if (dgrad && stride != 1) *rows = 0;      // (strided dgrads run per parity class and write no statistics rows)
+  else *rows = rows_per_group(*halo, *halo ? vfs_conv_halo_stats_rows(a) : vfs_conv_igemm_stats_rows(a), N, G, (long long)a.g.Ho * a.g.Wo);
+  return VFS_OK;
+}
+int vfs_stem_plan(int N, int H, int Wp, int Ho, int Wo, int G, int* rows) {
+  if (!rows || G < 1) return vfs_set_error(VFS_ERR_ARG, "stem_plan: bad argument");
+  const ConvArgs a = stem_fwd_args(nullptr, nullptr, nullptr, nullptr, N, H, Wp, Ho, Wo);
+  const bool direct = stem_takes_direct(a);
+  *rows = rows_per_group(direct, direct ? vfs_stem_tiles(N, Ho, Wo) : vfs_conv_igemm_stats_rows(a), N, G, (long long)Ho * Wo);
+  return VFS_OK;
+}
+int vfs_conv_wgrad_plan(int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int* halo,
+                        int* ntiles) {
+  if (!halo || !ntiles) return vfs_set_error(VFS_ERR_ARG, "conv_wgrad_plan: bad argument");
+  const WgradArgs a = wgrad_args(nullptr, nullptr, nullptr, 0, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, 1, 64);
+  *halo = vfs_takes_halo(a);
+  *ntiles = *halo ? vfs_wgrad_halo_tiles(a) : 0;
+  return VFS_OK;
 }
 
 int vfs_wgrad_reduce_table(const void* desc, int nrecords, int total_blocks, vfs_stream_t stream) {

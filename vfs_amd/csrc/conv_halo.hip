@@ -655,13 +655,30 @@ __global__ __launch_bounds__(256, NW > 2 ? 1 : 2) void conv3x3_halo_kernel(ConvA
   halo_epilogue_dispatch<BC, SMALLW, RAGGED>(a, acc, &sRed[0][0][0], smem, tile, tn0, y0, x0, c0, wc, wp, lr, lq, t);
 }
 
+// workgroups (spatial tiles) of a launch with bc-channel tiles: WAVES_P pixel waves of 64 pixels each - 8x16 (bc = 128) or
+// 16x16 (bc = 64) pixels of one image, or (smallw) WAVES_P whole images of at most 8x8 pixels
+static int halo_tiles(const ConvGeom& g, int bc, bool smallw) {
+  const int WAVES_P = 4 / (bc / 64);
+  const int TW = smallw ? 8 : 16, TH = smallw ? 8 : 4 * WAVES_P, TI = smallw ? WAVES_P : 1;
+  return ((g.N + TI - 1) / TI) * ((g.H + TH - 1) / TH) * ((g.W + TW - 1) / TW);
+}
+// which of the launch_halo instances vfs_conv_halo_dispatch picks
+static int halo_bc(const ConvArgs& a) { return a.Cout % 128 == 0 ? 128 : 64; }
+static bool halo_smallw(const ConvArgs& a) { return a.Cout % 128 == 0 && vfs_small_map(a.g.H, a.g.W); }
+// statistics rows of a launch: one per pair of pixel waves (128 tile pixels, ragged edge tiles included), tile-major - tiles
+// are enumerated image-major, so a group of whole images (whole image pairs: smallw) owns a contiguous block of rows
+int vfs_conv_halo_stats_rows(const ConvArgs& a) {
+  const int bc = halo_bc(a);
+  return halo_tiles(a.g, bc, halo_smallw(a)) * (4 / (bc / 64) / 2);
+}
+
 template <int BC, bool DGRAD, bool SMALLW>
 static int launch_halo(const ConvArgs& a0, hipStream_t stream) {
   ConvArgs a = a0;
   a.xcd_swizzle = vfs_option_halo_xcd;
   const int WAVES_P = 4 / (BC / 64);
-  const int TW = SMALLW ? 8 : 16, TH = SMALLW ? 8 : 4 * WAVES_P, TI = SMALLW ? WAVES_P : 1;
-  const int tiles = ((a.g.N + TI - 1) / TI) * ((a.g.H + TH - 1) / TH) * ((a.g.W + TW - 1) / TW);
+  const int TW = SMALLW ? 8 : 16, TH = SMALLW ? 8 : 4 * WAVES_P;
+  const int tiles = halo_tiles(a.g, BC, SMALLW);
   const int ncb = a.Cout / BC;
   const bool ragged = a.g.H % TH != 0 || a.g.W % TW != 0;
   if (BC == 128 && !a.in_bnp && tiles * ncb <= vfs_option_halo_deep_max) {
@@ -694,7 +711,7 @@ bool vfs_conv_halo_eligible(const ConvArgs& a, int mode) {
 }
 
 int vfs_conv_halo_dispatch(const ConvArgs& a, int mode, hipStream_t stream) {
-  const bool wide = (a.Cout % 128 == 0), smallw = vfs_small_map(a.g.H, a.g.W), dg = mode == GATHER_DGRAD;
+  const bool wide = halo_bc(a) == 128, smallw = halo_smallw(a), dg = mode == GATHER_DGRAD;
   if (wide) {
     if (dg) return smallw ? launch_halo<128, true, true>(a, stream) : launch_halo<128, true, false>(a, stream);
     return smallw ? launch_halo<128, false, true>(a, stream) : launch_halo<128, false, false>(a, stream);

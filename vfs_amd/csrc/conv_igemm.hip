@@ -436,14 +436,16 @@ static int launch_igemm(const ConvArgs& a, hipStream_t stream) {
   return vfs_check_launch("conv_igemm");
 }
 
+// statistics rows of a launch of this kernel family (conv_pw.hip shares the epilogue): one per 128-pixel block `pb` of the
+// destination grid, in pixel order (vfs_igemm_epi.h)
+int vfs_conv_igemm_stats_rows(const ConvArgs& a) { return (a.g.M + 127) / 128; }
+
 int vfs_conv_igemm_dispatch(const ConvArgs& a_in, int mode, hipStream_t stream) {
   ConvArgs a = a_in;
   a.xcd_swizzle = vfs_option_igemm_xcd;
   a.mfma_stats = vfs_option_igemm_mfma_stats;
   if (a.g.Ktot % 64 != 0 || a.Cout % 8 != 0) return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: K%64 or Cout%8");
-  if (vfs_option_halo && a.g.C % 64 == 0 && (size_t)a.g.N * a.g.H * a.g.W * a.g.C * 2 < 0xFFFFFFF0ull &&
-      vfs_conv_halo_eligible(a, mode))
-    return vfs_conv_halo_dispatch(a, mode, stream);
+  if (vfs_takes_halo(a, mode)) return vfs_conv_halo_dispatch(a, mode, stream);
   if (mode != GATHER_STEM && a.g.C % 64 != 0) return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: C%64");
   if (mode != GATHER_STEM && a.g.KH * a.g.KW > 32) return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: more than 32 taps");
   if ((size_t)a.g.N * a.g.H * a.g.W * a.g.C * 2 >= 0xFFFFFFF0ull || (size_t)a.Cout * a.g.Ktot * 2 >= 0xFFFFFFF0ull)

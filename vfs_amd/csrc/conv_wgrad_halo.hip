@@ -251,10 +251,16 @@ bool vfs_wgrad_halo_eligible(const WgradArgs& a, int mode) {
   return (long long)g.H * g.W * 100 >= cover * vfs_option_halo_min_fill;
 }
 
-int vfs_wgrad_halo_dispatch(const WgradArgs& a, hipStream_t stream, int* eff_nsplit) {
+// spatial tiles the kernel splits over: 8x16 pixels of one image, or (small maps) two whole images
+int vfs_wgrad_halo_tiles(const WgradArgs& a) {
   const bool smallw = vfs_small_map(a.g.H, a.g.W);
   const int TW = smallw ? 8 : 16, TI = smallw ? 2 : 1;
-  const int ntiles = ((a.g.N + TI - 1) / TI) * ((a.g.H + 7) / 8) * ((a.g.W + TW - 1) / TW);
+  return ((a.g.N + TI - 1) / TI) * ((a.g.H + 7) / 8) * ((a.g.W + TW - 1) / TW);
+}
+
+int vfs_wgrad_halo_dispatch(const WgradArgs& a, hipStream_t stream, int* eff_nsplit) {
+  const bool smallw = vfs_small_map(a.g.H, a.g.W);
+  const int ntiles = vfs_wgrad_halo_tiles(a);
   const int nsplit = a.nsplit < ntiles ? a.nsplit : ntiles;
   const int tps = (ntiles + nsplit - 1) / nsplit;
   WgradArgs b = a;

@@ -152,6 +152,18 @@ static inline bool vfs_small_map(int H, int W) { return H <= 8 && W <= 8 && H * 
 int vfs_conv_halo_dispatch(const ConvArgs& a, int mode, hipStream_t stream);
 bool vfs_wgrad_halo_eligible(const WgradArgs& a, int mode);
 int vfs_wgrad_halo_dispatch(const WgradArgs& a, hipStream_t stream, int* eff_nsplit);
+// THE decision "this launch runs on the halo-tile kernels": the dispatchers, the entry points that need the answer before they
+// dispatch and the host's plan queries (capi.hip: vfs_conv_plan, vfs_conv_wgrad_plan) all ask here
+static inline bool vfs_takes_halo(const ConvArgs& a, int mode) {
+  return vfs_option_halo && a.g.C % 64 == 0 && (size_t)a.g.N * a.g.H * a.g.W * a.g.C * 2 < 0xFFFFFFF0ull && vfs_conv_halo_eligible(a, mode);
+}
+static inline bool vfs_takes_halo(const WgradArgs& a) { return vfs_option_halo && vfs_wgrad_halo_eligible(a, GATHER_FWD); }
+// the plan behind a launch (host only): statistics rows (forward: a.stats, stride-1 dgrad: a.bn.partial) that ONE launch
+// writes, next to the kernels that define them - spatial tiles (conv_halo.hip), linear 128-pixel blocks (conv_igemm.hip) -
+// and the spatial tiles the halo weight gradient splits over
+int vfs_conv_halo_stats_rows(const ConvArgs& a);
+int vfs_conv_igemm_stats_rows(const ConvArgs& a);
+int vfs_wgrad_halo_tiles(const WgradArgs& a);
 int vfs_stem_tiles(int N, int Ho, int Wo);
 int vfs_stem_fwd_direct_launch(const ConvArgs& a, hipStream_t stream);
 int vfs_conv_wgrad_dispatch(const WgradArgs& a, int mode, hipStream_t stream);

@@ -6,7 +6,7 @@
 #define VFS_OPTIONS(X)                                                                                                              \
   /* ---- 3x3 halo-tile kernels (conv_halo.hip, conv_wgrad_halo.hip) */                                                             \
   X(halo, 1)                  /* 1: 3x3 / stride-1 convs use the halo-tile kernels */                                               \
-  X(halo_min_fill, 70)        /* percent of a ragged tiling that must be real pixels (100: exact tilings only); vfs_amd/packing.py HALO_MIN_FILL mirrors it */ \
+  X(halo_min_fill, 70)        /* percent of a ragged tiling that must be real pixels (100: exact tilings only) */ \
   X(halo_deep_max, 256)       /* the four-stage weight ring (one workgroup per CU) for launches of at most this many workgroups (0: never) */ \
   X(halo_xcd, 1)              /* XCD-aware tile order of the halo kernels (A/B knob) */                                             \
   /* ---- stem (stem.hip) */                                                                                                        \

@@ -16,8 +16,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import Tape, TapeLib, get_lib
-from .packing import (bn_fold_eligible, build_pack_table, build_reduce_table, conv_halo_eligible, conv_stats_rows, wgrad_halo_eligible,
-                      wgrad_splits, small_map)
+from .packing import bn_fold_eligible, build_pack_table, build_reduce_table, conv_plan, stem_stats_rows, wgrad_halo_eligible, wgrad_splits
 
 BF16 = torch.bfloat16
 
@@ -98,9 +97,6 @@ class Engine:
         for kv in filter(None, os.environ.get('VFS_OPTS', '').split(',')):      # kernel A/B knobs: "name=value,..."
             name, value = kv.split('=')
             self.lib.set_option(name.strip().encode(), int(value))
-            if name.strip() == 'halo_min_fill':      # the host mirrors of the tiling rules must agree with the library
-                from . import packing
-                packing.HALO_MIN_FILL = int(value)
 
     # ------------------------------------------------------------------ command tape (see _lib.Tape)
     def begin_tape(self):
@@ -162,14 +158,17 @@ class Engine:
         """grow-only flat buffer that starts zero-filled and that every user leaves zero (ticket counters, constant zero operands)"""
         return self.ws(key, numel, dtype, dev, alloc=torch.zeros)
 
-    @staticmethod
-    def conv_kind(u, N, H, W, dgrad=False):
-        """kernel family a forward / dgrad launch of unit u lands in (bench.py's per-kernel roofline classes; mirrors the
-        dispatch of csrc/conv_igemm.hip): stem_fwd | conv3x3_halo | conv_igemm"""
+    def conv_plan(self, u, N, G, H, W, dgrad=False):
+        """the library's plan (packing.ConvPlan) for unit u's forward / dgrad launch over N images of H x W INPUT pixels"""
+        Ho, Wo = u.out_hw(H, W)
+        return conv_plan(N, G, H, W, u.cin, u.cout, u.k, u.stride, u.pad, Ho, Wo, dil=u.dil, dgrad=dgrad, lib=self.host_lib)
+
+    def conv_kind(self, u, N, H, W, dgrad=False):
+        """kernel family a forward / dgrad launch of unit u (input H x W) lands in, as the library dispatches it (bench.py's
+        per-kernel roofline classes): stem_fwd | conv3x3_halo | conv_igemm"""
         if u.kind == 'stem':
             return 'stem_fwd'
-        cin, cout = (u.cout, u.cin) if dgrad else (u.cin, u.cout)
-        return 'conv3x3_halo' if (u.dil == 1 and conv_halo_eligible(N, H, W, cin, cout, u.k, u.stride, u.pad)) else 'conv_igemm'
+        return 'conv3x3_halo' if self.conv_plan(u, N, 1, H, W, dgrad).halo else 'conv_igemm'
 
     def timed(self, kind, work, dev, fn, *args):
         """launch through `fn`; with profiling on, bracket it with events on the launch stream.
@@ -313,13 +312,11 @@ class Engine:
         mpg = Ng * Ho * Wo
         # statistics rows per group when ONE launch covers all groups (spatial tiles of the halo kernels, ragged
         # edges included, or linear 128-pixel blocks), else one launch per group
-        rows = None if u.kind == 'stem' else conv_stats_rows(N, G, H, W, u.cin, u.cout, u.k, u.stride, u.pad, Ho, Wo,
-                                                             halo=u.dil == 1)
+        def rows_of(n, g):
+            return stem_stats_rows(n, g, H, W, Ho, Wo, lib=self.host_lib) if u.kind == 'stem' else self.conv_plan(u, n, g, H, W).rows
+        rows = rows_of(N, G)
         fused = rows is not None
-        nblk_g = rows if fused else (mpg + 127) // 128
-        if u.kind == 'stem':      # the stem kernel emits one statistics row per 8x16 spatial tile
-            fused = True
-            nblk_g = Ng * ((Ho + 7) // 8) * ((Wo + 15) // 16)
+        nblk_g = rows if fused else rows_of(Ng, 1)
         # small groups that are not multiples of the 128-pixel statistics rows (the head's Linear layers on the ResNet-50
         # config: 32 rows per view): ONE launch without statistics rows, the sums come from the stored output
         raw_stats = (want_stats and not fused and not self.collectives_on and mpg <= 2048
@@ -430,7 +427,7 @@ class Engine:
         # ResNet-50 9.36 / 9.30 / 9.24 ms, ResNet-18 unchanged - its folded tensors are all >= 48 MB)
         # whole-image tiles (maps of at most 8x8): the fold is a loss (ResNet-18 layer4 at 256^2, 17 MB: step 6.90 with, 6.82 without -
         # profiles/r06_fold3x3_threshold_step_ab.txt); VFS_BNACT_FUSE_SMALL=1 keeps it (tests exercise the kernels through the engine)
-        if u.k == 3 and small_map(H, W) and os.environ.get('VFS_BNACT_FUSE_SMALL', '0') != '1':
+        if u.k == 3 and self.conv_plan(u, N, G, H, W).pairs and os.environ.get('VFS_BNACT_FUSE_SMALL', '0') != '1':
             return False
         mb = os.environ.get('VFS_BNACT_FUSE_1X1_MB', '16') if u.k == 1 else os.environ.get('VFS_BNACT_FUSE_MB', '16')
         if N * H * W * u.cin * 2 < float(mb) * (1 << 20):
@@ -439,7 +436,7 @@ class Engine:
         mpg = Ng * H * W
         if not (G == 1 or mpg % 128 == 0):      # the consumer must take the single-launch statistics path
             return False
-        return bn_fold_eligible(N, G if train else 1, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
+        return bn_fold_eligible(N, G if train else 1, H, W, u.cin, u.cout, u.k, u.stride, u.pad, lib=self.host_lib)
 
     def bn_scratch(self, G, C, dev):
         """scratch of the chunked BatchNorm reductions: 64 ticket counters (must start at zero; every
@@ -698,8 +695,8 @@ class Engine:
                            self.stream(dev))
             return None, None
         ktot = u.k * u.k * u.cin
-        halo = (N, H, W, u.cin) if wgrad_halo_eligible(N, H, W, u.cin, u.cout, u.k, u.stride, u.pad) else None
-        nsplit, pps = wgrad_splits(M, u.cout, ktot, halo_geom=halo)
+        halo = (N, H, W, u.cin) if wgrad_halo_eligible(N, H, W, u.cin, u.cout, u.k, u.stride, u.pad, lib=self.host_lib) else None
+        nsplit, pps = wgrad_splits(M, u.cout, ktot, halo_geom=halo, lib=self.host_lib)
         partial = self.wgrad_partial(u, nsplit, u.cout, ktot, dev) if u.weight.requires_grad else None
         flops = 2.0 * M * u.cout * ktot
         # ALGORITHMIC bytes: dY + x once, the fp32 gradient read-modify-write.  (The fp32 split-K partials - written by the
@@ -734,19 +731,19 @@ class Engine:
             Min = N * H * W
             mpg = Min // G
             # the dgrad as a conv [N,Ho,Wo,cout] -> [N,H,W,cin]: its statistics rows (tiles or linear blocks)
-            rows = conv_stats_rows(N, G, Ho, Wo, u.cout, u.cin, u.k, u.stride, u.pad, H, W)
+            rows = self.conv_plan(u, N, G, H, W, dgrad=True).rows
             if rows is not None:
                 nblk = rows * G
                 partial = self.ws('ws.bnbwd_fused', nblk * 2 * u.cin, torch.float32, dev)
                 pbits = pymask is not None and pymask.dtype == torch.uint8
                 mask_units = 0.0 if pymask is None else (1.0 / 16 if pbits else 1.0)
-                self.timed(self.conv_kind(u, N, Ho, Wo, dgrad=True), (flops, dbytes + 2.0 * N * H * W * u.cin * ((1 if add is not None else 0) + 1 + mask_units)),
+                self.timed(self.conv_kind(u, N, H, W, dgrad=True), (flops, dbytes + 2.0 * N * H * W * u.cin * ((1 if add is not None else 0) + 1 + mask_units)),
                            dev, lib.conv_dgrad_bn_maskadd, dx, u.wd, gin, add, add_mask, praw, pymask, pu.bnp, partial,
                            mpg, 2 if pbits else (1 if (prelu and pymask is None) else 0), N, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k,
                            u.stride, u.pad, s)
                 return gin, BwdRows(pu, partial, nblk)
         work = (flops, dbytes + (2.0 * N * H * W * u.cin if add is not None else 0.0))
-        self.timed(self.conv_kind(u, N, Ho, Wo, dgrad=True), work, dev, lib.conv_dgrad_maskadd, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo, u.cout,
+        self.timed(self.conv_kind(u, N, H, W, dgrad=True), work, dev, lib.conv_dgrad_maskadd, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo, u.cout,
                    u.k, u.k, u.stride, u.pad, s)
         return gin, None
 

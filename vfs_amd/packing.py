@@ -1,5 +1,6 @@
-"""Host helpers shared by the engine and the tests: pack-table construction, wgrad split choice."""
+"""Host helpers shared by the engine and the tests: pack-table construction, the library's tiling plan, wgrad split choice."""
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -53,59 +54,66 @@ def build_reduce_table(entries, device, max_blocks_per_record=2048):
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device), len(entries), start
 
 
-def small_map(H, W):
-    """mirror of vfs_small_map (csrc/vfs_conv.h): whole images of <= 8x8 pixels, two per halo tile"""
-    return H <= 8 and W <= 8 and H * W * 100 >= 64 * HALO_MIN_FILL
+class ConvPlan(NamedTuple):
+    """vfs_conv_plan's answer for one forward / dgrad launch (include/vfs_hip.h): the library owns the tiling rules"""
+    halo: bool                # the 3x3 halo-tile kernel takes it (else the implicit-GEMM family)
+    rows: Optional[int]       # statistics rows per group that ONE launch over all groups writes; None: launch per group
+    pairs: bool               # whole images of at most 8x8 pixels tiled in pairs (a folded input BatchNorm needs an even group)
 
 
-def wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad):
-    """mirror of vfs_wgrad_halo_eligible (csrc/conv_wgrad_halo.hip)"""
-    if k != 3 or stride != 1 or pad != 1 or Cin % 64 or Cout % 64:
-        return False
-    if small_map(H, W):
-        return True
-    cover = ((H + 7) // 8 * 8) * ((W + 15) // 16 * 16)
-    return H * W * 100 >= cover * HALO_MIN_FILL
+def _host_lib(lib):
+    """the library a plan is asked from: the one given (Engine.host_lib, a test's backend.lib - the queries are no part of a
+    recorded chain), else the one the process's shared engine launches through"""
+    if lib is not None:
+        return lib
+    from .engine import shared_engine
+    return shared_engine().host_lib
 
 
-HALO_MIN_FILL = 70      # mirror of vfs_option_halo_min_fill (VFS_OPTS=halo_min_fill=.. sets both, see Engine)
+def conv_plan(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, dil=1, dgrad=False, lib=None):
+    """the plan of conv(k, stride, pad, dil): [N,H,W,Cin] -> [N,Ho,Wo,Cout] with G statistics groups (dgrad: of its input
+    gradient, rows and groups over [N,H,W,Cin])"""
+    out = torch.zeros(3, dtype=torch.int32)
+    _host_lib(lib).conv_plan(int(dgrad), N, H, W, Cin, Ho, Wo, Cout, k, k, stride, pad, dil, G, out[0:], out[1:], out[2:])
+    halo, rows, pairs = out.tolist()
+    return ConvPlan(bool(halo), rows or None, bool(pairs))
 
 
-def conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad):
-    """mirror of vfs_conv_halo_eligible (csrc/conv_halo.hip), forward / stride-1 dgrad"""
-    if k != 3 or stride != 1 or pad != 1 or Cin % 64 or Cout % 64:
-        return False
-    if small_map(H, W) and Cout % 128 == 0:
-        return N % 2 == 0
-    th, tw = (8 if Cout % 128 == 0 else 16), 16
-    cover = ((H + th - 1) // th * th) * ((W + tw - 1) // tw * tw)
-    return H * W * 100 >= cover * HALO_MIN_FILL
+def conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=None):
+    """does the halo-tile kernel take this forward conv (statistics rows are then spatial tiles, not linear 128-pixel blocks)?"""
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    return conv_plan(N, 1, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib).halo
 
 
-def halo_stats_rows(N, H, W, Cout):
-    """statistics rows the halo kernels emit for an [N,H,W,Cout] output: one per 128 tile pixels (ragged edge tiles
-    included), tiles enumerated image-major - so a group of whole images owns a contiguous block of rows"""
-    if small_map(H, W) and Cout % 128 == 0:
-        return N // 2
-    if Cout % 128 == 0:
-        return N * ((H + 7) // 8) * ((W + 15) // 16)
-    return N * ((H + 15) // 16) * ((W + 15) // 16) * 2
-
-
-def conv_stats_rows(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, halo=True):
+def conv_stats_rows(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=None):
     """rows per statistics group of the per-block (sum, sum of squares) rows a forward conv - or a stride-1 dgrad seen
     as a conv producing [N,Ho,Wo,Cout] - writes in ONE launch, or None when the groups do not own whole rows (the
-    caller then launches per group): spatial tiles for the halo kernels, linear 128-pixel blocks otherwise."""
-    if halo and conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad):
-        total = halo_stats_rows(N, Ho, Wo, Cout)
-        return total // G if (N % G == 0 and total % G == 0) else None
-    mpg = (N // G) * Ho * Wo
-    if G == 1 or mpg % 128 == 0:
-        return (mpg + 127) // 128
-    return None
+    caller then launches per group)"""
+    return conv_plan(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib).rows
 
 
-def bn_fold_eligible(N, G, H, W, Cin, Cout, k, stride, pad):
+def stem_stats_rows(N, G, H, Wp, Ho, Wo, lib=None):
+    """conv_stats_rows for vfs_stem_fwd"""
+    out = torch.zeros(1, dtype=torch.int32)
+    _host_lib(lib).stem_plan(N, H, Wp, Ho, Wo, G, out)
+    return int(out) or None
+
+
+def wgrad_halo_tiles(N, H, W, Cin, Cout, k, stride, pad, lib=None):
+    """spatial tiles the 3x3 halo weight-gradient kernel splits over when vfs_conv_wgrad takes it for this layer, else 0"""
+    out = torch.zeros(2, dtype=torch.int32)
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    _host_lib(lib).conv_wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, k, k, stride, pad, out[0:], out[1:])
+    halo, ntiles = out.tolist()
+    return ntiles if halo else 0
+
+
+def wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=None):
+    """does vfs_conv_wgrad run the 3x3 halo kernel for this layer?"""
+    return wgrad_halo_tiles(N, H, W, Cin, Cout, k, stride, pad, lib=lib) > 0
+
+
+def bn_fold_eligible(N, G, H, W, Cin, Cout, k, stride, pad, lib=None):
     """can conv(k, stride, pad) read the RAW output of its producer unit and apply BatchNorm + ReLU while
     staging (vfs_conv_fwd_bnin / vfs_conv_wgrad_bnin)?  Both halo kernels must take the shape and a tile
     must not straddle two statistics groups (8x8 images are tiled in pairs)."""
@@ -114,9 +122,11 @@ def bn_fold_eligible(N, G, H, W, Cin, Cout, k, stride, pad):
         # weight-gradient kernels: groups of whole 128-pixel tiles
         return (os.environ.get('VFS_BNACT_FUSE_1X1', '1') == '1' and Cin % 64 == 0 and Cout % 64 == 0 and N % G == 0 and G <= 8
                 and ((N // G) * H * W) % 128 == 0)
-    if not (conv_halo_eligible(N, H, W, Cin, Cout, k, stride, pad) and wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad)):
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    plan = conv_plan(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib)
+    if not (plan.halo and wgrad_halo_eligible(N, H, W, Cin, Cout, k, stride, pad, lib=lib)):
         return False
-    if small_map(H, W) and (N // G) % 2:
+    if plan.pairs and (N // G) % 2:
         return False
     return N % G == 0 and G <= 8
 
@@ -144,13 +154,13 @@ def wgrad_inl_floats(nsplit, Cout, Ktot):
     return nsplit * Cout * ((Ktot + 127) // 128 * 128)
 
 
-def wgrad_splits(M, Cout, Ktot, target_blocks=192, halo_geom=None):
-    """Split-K plan for the wgrad kernels: (nsplit, pix_per_split).  halo_geom = (N, H, W, Cin)
-    selects the plan of the 3x3 halo kernel (workgroup = 64 cin x 64 cout x 9 taps, split over
-    128-pixel spatial tiles)."""
-    if halo_geom is not None:
-        N, H, W, Cin = halo_geom
-        ntiles = ((N + 1) // 2) if small_map(H, W) else N * ((H + 7) // 8) * ((W + 15) // 16)
+def wgrad_splits(M, Cout, Ktot, target_blocks=192, halo_geom=None, lib=None):
+    """Split-K plan the host OFFERS the wgrad kernels: (nsplit, pix_per_split).  halo_geom = (N, H, W, Cin) of a 3x3 /
+    stride-1 / pad-1 layer selects the plan of the halo kernel (workgroup = 64 cin x 64 cout x 9 taps, split over the
+    128-pixel spatial tiles the library reports) - where the library runs that kernel; else the generic kernel's plan."""
+    ntiles = wgrad_halo_tiles(*halo_geom, Cout, 3, 1, 1, lib=lib) if halo_geom is not None else 0
+    if ntiles:
+        Cin = halo_geom[3]
         colblocks = (Cin // 64) * (Cout // 64)
         # every workgroup writes a 9x64x64 fp32 partial (147 KB): keep ~2 workgroups per CU so
         # the split-K traffic (blocks x 147 KB, written then re-read) stays well below the MFMA time
