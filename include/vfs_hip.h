@@ -430,6 +430,32 @@ int vfs_grad_norm_finish(const double* partials, float norm_type, double max_nor
  * runs (vfs_grad_norm_finish's out + 1).  *clip == 1.0 gives exactly vfs_sgd_step's bits.  skip_flag as above. */
 int vfs_sgd_step_clip(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
                       float weight_decay, const float* clip, const void* skip_flag, vfs_stream_t stream);
+/* ---- optimizers with param groups: optimizer = dict(type='SGD' | 'Adam' | 'AdamW', ..., paramwise_cfg=...) (configs/r*_*.py:134-136),
+ * which apis/train.py:72 hands to mmcv's build_optimizer: DefaultOptimizerConstructor makes one param group per parameter, torch's
+ * optimizer then steps tensor by tensor.  Here one update launch covers every trainable range of the flat arena and every param group.
+ *
+ * vfs_opt_segment_map_words / vfs_opt_segment_map (host only, once per arena layout): `segments` is HOST memory, nseg x
+ *   {begin, end, group} in words - the trainable parameters [begin, end) of the arena, sorted, inside [0, n), each beginning on a
+ *   multiple of 4 words and none sharing a 16-byte vector with the one before (parameters are padded to 4 words), group in
+ *   [0, ngroups).  The map (`words` ints, host memory) is what vfs_opt_step_table reads on the DEVICE: copy it there once.
+ * vfs_opt_step_table (torch.optim.SGD.step / Adam.step / AdamW.step over all param groups): kind 0 SGD, 1 Adam, 2 AdamW, fp32.
+ *   state1: momentum_buffer / exp_avg, state2: exp_avg_sq (NULL for SGD); params, grads and the states are arenas of n words with
+ *   the same layout, 16-byte aligned.  map: the DEVICE copy of vfs_opt_segment_map's output for this (n, nseg).  hyper: HOST
+ *   memory, ngroups x 8 floats, read before the call returns: {lr, weight_decay, momentum} for SGD, {lr, weight_decay, beta1, beta2,
+ *   eps} for Adam / AdamW (the other slots are ignored; the bias corrections of `step` are worked out inside).  Up to 224
+ *   groups the rows are kernel arguments of the update launch itself; more go through `table` (device workspace of ngroups x 8
+ *   floats, 16-byte aligned, always required), written on `stream` by two small launches in front of the update with the
+ *   values of THIS call.  Nothing waits for a copy, a changed lr holds from this step on.  At most 448 param groups.
+ *   SGD: g' = clip g + wd p; buf = momentum buf + g'; p -= lr (nesterov ? g' + momentum buf : buf)   (dampening 0; a zero buffer
+ *   gives torch's first step).  Adam (amsgrad off): the wd p term joins the gradient.  AdamW: p *= 1 - lr wd before the moments.
+ *   step: torch's state['step'] AFTER this update (>= 1; ignored by SGD).  clip: NULL or the device coefficient of
+ *   vfs_grad_norm_finish, skip_flag: NULL or the device word, both as in vfs_sgd_step_clip.  Words outside every segment are
+ *   neither read nor written.  One group without nesterov gives vfs_sgd_step's / vfs_sgd_step_clip's bits. */
+int vfs_opt_segment_map_words(long long n, int nseg, long long* words);
+int vfs_opt_segment_map(const long long* segments, int nseg, long long n, int ngroups, int* map, long long words);
+int vfs_opt_step_table(int kind, float* params, const float* grads, float* state1, float* state2, long long n, const int* map, int nseg,
+                       const float* hyper, int ngroups, float* table, int nesterov, int step, const float* clip, const void* skip_flag,
+                       vfs_stream_t stream);
 /* x[0..n) *= *coef, coef a device float read when the kernel runs (clip_grad_norm_'s g.mul_(clip_coef_clamped) for a caller that
  * drives the loop itself, OptimizerHook.clip_grads); x 16-byte aligned */
 int vfs_scale_by(float* x, long long n, const float* coef, vfs_stream_t stream);

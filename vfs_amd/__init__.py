@@ -11,7 +11,7 @@ from .resnet import ResNet  # noqa: F401
 from .sim_loss import CosineSimLoss  # noqa: F401
 from .sim_siam_head import DenseSimSiamHead, SimSiamHead  # noqa: F401
 from .trackers import BaseTracker, SimSiamBaseTracker, VanillaTracker  # noqa: F401
-from .optim import SGD, build_optimizer, clip_grad_norm_  # noqa: F401
+from .optim import SGD, Adam, AdamW, LrUpdater, build_lr_updater, build_optimizer, clip_grad_norm_  # noqa: F401
 from .davis_eval import DavisEvaluator, evaluate_sequences  # noqa: F401
 from .prop_eval import JHMDBEvaluator, VIPEvaluator, heatmap_coords, pose_heatmaps  # noqa: F401
 from .checkpoint import from_pretrained_keys, to_pretrained_keys  # noqa: F401

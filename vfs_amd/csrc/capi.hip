@@ -793,6 +793,24 @@ int vfs_sgd_step_clip(float* params, const float* grads, float* momentum_buf, lo
   if (n < 0) return vfs_set_error(VFS_ERR_ARG, "sgd_step_clip: n < 0");
   return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, clip, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
 }
+// table-driven optimizer step: the map is built and checked on the host (opt_table.h), the step checks what it can see
+int vfs_opt_segment_map_words(long long n, int nseg, long long* words) {
+  if (!words || n < 0 || nseg < 0) return vfs_set_error(VFS_ERR_ARG, "opt_segment_map_words: bad argument");
+  *words = vfs_opt_map_words_of(n, nseg);
+  return VFS_OK;
+}
+int vfs_opt_segment_map(const long long* segments, int nseg, long long n, int ngroups, int* map, long long words) {
+  if (const char* what = vfs_opt_map_build(segments, nseg, n, ngroups, map, words)) return fail(VFS_ERR_ARG, "opt_segment_map", what);
+  return VFS_OK;
+}
+int vfs_opt_step_table(int kind, float* params, const float* grads, float* state1, float* state2, long long n, const int* map, int nseg,
+                       const float* hyper, int ngroups, float* table, int nesterov, int step, const float* clip, const void* skip_flag,
+                       vfs_stream_t stream) {
+  if (const char* what = vfs_opt_step_check(kind, params, grads, state1, state2, n, map, nseg, hyper, ngroups, table, nesterov, step))
+    return fail(VFS_ERR_ARG, "opt_step_table", what);
+  return vfs_opt_table_launch(kind, params, grads, state1, state2, n, map, nseg, hyper, ngroups, table, nesterov, step, clip,
+                              static_cast<const unsigned long long*>(skip_flag), stream_of(stream));
+}
 int vfs_scale_by(float* x, long long n, const float* coef, vfs_stream_t stream) {
   if (!x || !coef) return vfs_set_error(VFS_ERR_ARG, "scale_by: null buffer");
   if (n < 0) return vfs_set_error(VFS_ERR_ARG, "scale_by: n < 0");

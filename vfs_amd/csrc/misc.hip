@@ -436,6 +436,146 @@ int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, 
   else hipLaunchKernelGGL(sgd_kernel<false>, grid, dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, clip, skip);
   return vfs_check_launch("sgd");
 }
+
+// ------------------------------------------------------------------ table-driven optimizer step (vfs_opt_step_table)
+// mmcv's build_optimizer with paramwise_cfg (configs/r*_*.py:134-136, apis/train.py:72) gives every parameter a param group of its
+// own; torch then updates tensor by tensor.  Here one update launch sweeps the whole arena: the segment map (opt_table.h) says
+// which 16-byte vectors are trainable and which group they belong to.  The groups' hyperparameter rows are kernel arguments of the
+// update itself while they fit (VFS_OPT_WRITE_GROUPS groups); more groups go through a small device table that
+// opt_table_write_kernel fills on the launch stream right before, again from kernel arguments.  Either way there is no host copy to
+// wait for, and a changed lr is in force at the next step.  Words outside every segment - frozen parameters, the padding between
+// parameters - are neither read nor written.
+// A workgroup pass covers one VFS_OPT_CHUNK_WORDS chunk.  The chunk's entry index and the segment it names are uniform loads; when
+// that segment holds the whole chunk (all but the chunks with a parameter edge in them: ~350 of the 37 315 of a ResNet-50), the
+// group and its row are uniform too and the lanes go straight to their streaming loads.  Only a chunk with an edge in it walks
+// the map per lane - from the entry index past the segments of this chunk at the most.
+// SGD:   g' = clip g + wd p;  buf = momentum buf + g';  p -= lr (nesterov ? g' + momentum buf : buf)      (sgd_kernel's expressions)
+// Adam:  g' = clip g + wd p;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// AdamW: p *= 1 - lr wd first, g' = clip g                                                                  (adam_kernel's expressions)
+struct OptHyperChunk { float v[VFS_OPT_WRITE_GROUPS * VFS_OPT_HYPER]; };
+__global__ __launch_bounds__(256) void opt_table_write_kernel(OptHyperChunk c, float* __restrict__ table, int count) {
+  for (int i = threadIdx.x; i < count; i += 256) table[i] = c.v[i];
+}
+template <int KIND, bool NEST, bool CLIP>
+__device__ __forceinline__ void opt_update(float& p, float g, float& a, float& b, const float* h, float c) {
+  const float lr = h[0], wd = h[1];
+  if (KIND == VFS_OPT_SGD) {
+    const float momentum = h[2];
+    const float gg = sgd_grad<CLIP>(g, c) + wd * p;
+    a = momentum * a + gg;
+    if (NEST) p -= lr * (gg + momentum * a);
+    else p -= lr * a;
+  } else {
+    const float b1 = h[2], b2 = h[3], eps = h[4], bc1 = h[5], bc2s = h[6];
+    float gi = sgd_grad<CLIP>(g, c);
+    if (KIND == VFS_OPT_ADAMW) p *= 1.f - lr * wd;
+    else if (wd != 0.f) gi += wd * p;
+    a = b1 * a + (1.f - b1) * gi;
+    b = b2 * b + (1.f - b2) * gi * gi;
+    p -= (lr / bc1) * (a / (sqrtf(b) / bc2s + eps));
+  }
+}
+// vector i of a segment {.., end4, group, tail}: a whole vector, or the segment's last, partial one (its `tail` words one by one)
+template <int KIND, bool NEST, bool CLIP>
+__device__ __forceinline__ void opt_vector(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1, float* __restrict__ s2,
+                                           long long i, int end4, int tail, const float* __restrict__ row, float c) {
+  float h[7];
+#pragma unroll
+  for (int q = 0; q < (KIND == VFS_OPT_SGD ? 3 : 7); ++q) h[q] = row[q];
+  if (i < end4) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 av = reinterpret_cast<f32x4*>(s1)[i];
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (KIND != VFS_OPT_SGD) bv = reinterpret_cast<f32x4*>(s2)[i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float pq = pv[q], aq = av[q], bq = bv[q];
+      opt_update<KIND, NEST, CLIP>(pq, gv[q], aq, bq, h, c);
+      pv[q] = pq; av[q] = aq; bv[q] = bq;
+    }
+    reinterpret_cast<f32x4*>(s1)[i] = av;
+    if (KIND != VFS_OPT_SGD) reinterpret_cast<f32x4*>(s2)[i] = bv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+  } else {
+    for (int q = 0; q < tail; ++q) {
+      const long long w = (i << 2) + q;
+      float bw = KIND != VFS_OPT_SGD ? s2[w] : 0.f;
+      opt_update<KIND, NEST, CLIP>(p[w], g[w], s1[w], bw, h, c);
+      if (KIND != VFS_OPT_SGD) s2[w] = bw;
+    }
+  }
+}
+// table: the device table, or nullptr when the rows are `rows` itself (ngroups <= VFS_OPT_WRITE_GROUPS).  With a table `rows` is
+// dead: it still travels (one instantiation per kind, and only the rows that are indexed are ever loaded from the argument block).
+template <int KIND, bool NEST, bool CLIP>
+__global__ __launch_bounds__(256) void opt_table_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                                        float* __restrict__ s2, long long nvec, const int* __restrict__ map, int nseg,
+                                                        const float* __restrict__ table, const float* __restrict__ clip,
+                                                        const unsigned long long* __restrict__ skip, OptHyperChunk rows) {
+  if (skip && *skip) return;      // as sgd_kernel: a poisoned step leaves weights and state alone
+  const float c = CLIP ? *clip : 1.0f;
+  const float* hyper = table ? table : rows.v;
+  const int* first = map + 4 * (long long)nseg;
+  for (long long base = (long long)blockIdx.x * 256; base < nvec; base += (long long)gridDim.x * 256) {
+    const long long i = base + threadIdx.x;
+    const int s0 = first[base >> 8];
+    if (s0 == nseg) continue;                   // nothing trainable from here to the end of the arena
+    int begin4 = map[4 * s0], end4 = map[4 * s0 + 1], group = map[4 * s0 + 2], tail = map[4 * s0 + 3];
+    if (begin4 <= base && base + 256 <= end4) {      // the whole chunk inside one segment: everything above is uniform
+      opt_vector<KIND, NEST, CLIP>(p, g, s1, s2, i, end4, 0, hyper + group * VFS_OPT_HYPER, c);
+      continue;
+    }
+    if (i >= nvec) continue;
+    int s = s0;
+    while ((long long)end4 + (tail != 0) <= i) {      // a chunk with a parameter edge in it: the lane's own walk
+      if (++s == nseg) break;
+      begin4 = map[4 * s]; end4 = map[4 * s + 1]; group = map[4 * s + 2]; tail = map[4 * s + 3];
+    }
+    if (s == nseg || begin4 > i) continue;      // frozen or padding
+    opt_vector<KIND, NEST, CLIP>(p, g, s1, s2, i, end4, tail, hyper + group * VFS_OPT_HYPER, c);
+  }
+}
+template <int KIND, bool NEST>
+static void opt_table_launch_kind(dim3 grid, hipStream_t s, float* p, const float* g, float* s1, float* s2, long long nvec, const int* map,
+                                  int nseg, const float* table, const float* clip, const unsigned long long* skip, const OptHyperChunk& rows) {
+  if (clip) hipLaunchKernelGGL((opt_table_kernel<KIND, NEST, true>), grid, dim3(256), 0, s, p, g, s1, s2, nvec, map, nseg, table, clip, skip, rows);
+  else hipLaunchKernelGGL((opt_table_kernel<KIND, NEST, false>), grid, dim3(256), 0, s, p, g, s1, s2, nvec, map, nseg, table, clip, skip, rows);
+}
+// hyper: HOST memory, ngroups x VFS_OPT_HYPER floats {lr, wd, momentum} or {lr, wd, beta1, beta2, eps}; the bias corrections of
+// `step` are worked out here (as vfs_adam_launch does) and travel in slots 5 and 6
+int vfs_opt_table_launch(int kind, float* p, const float* g, float* s1, float* s2, long long n, const int* map, int nseg,
+                         const float* hyper, int ngroups, float* table, int nesterov, int step, const float* clip,
+                         const unsigned long long* skip, hipStream_t s) {
+  const bool by_value = ngroups <= VFS_OPT_WRITE_GROUPS;      // the rows ride with the update launch: nothing in front of it
+  OptHyperChunk ch;
+  for (int g0 = 0; g0 < ngroups; g0 += VFS_OPT_WRITE_GROUPS) {
+    const int ng = ngroups - g0 < VFS_OPT_WRITE_GROUPS ? ngroups - g0 : VFS_OPT_WRITE_GROUPS;
+    for (int k = 0; k < ng; ++k) {
+      const float* src = hyper + (size_t)(g0 + k) * VFS_OPT_HYPER;
+      float* dst = ch.v + k * VFS_OPT_HYPER;
+      for (int q = 0; q < VFS_OPT_HYPER; ++q) dst[q] = q < 5 ? src[q] : 0.f;
+      if (kind != VFS_OPT_SGD) {
+        dst[5] = 1.f - powf(src[2], (float)step);
+        dst[6] = sqrtf(1.f - powf(src[3], (float)step));
+      }
+    }
+    for (int k = ng * VFS_OPT_HYPER; k < VFS_OPT_WRITE_GROUPS * VFS_OPT_HYPER; ++k) ch.v[k] = 0.f;
+    if (!by_value)
+      hipLaunchKernelGGL(opt_table_write_kernel, dim3(1), dim3(256), 0, s, ch, table + (size_t)g0 * VFS_OPT_HYPER, ng * VFS_OPT_HYPER);
+  }
+  if (int rc = vfs_check_launch("opt_step_table")) return rc;
+  const float* dev_rows = by_value ? nullptr : table;
+  const long long nvec = (n + 3) >> 2;
+  long long b = (nvec + 255) / 256;
+  const dim3 grid((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)));
+  if (kind == VFS_OPT_SGD) {
+    if (nesterov) opt_table_launch_kind<VFS_OPT_SGD, true>(grid, s, p, g, s1, s2, nvec, map, nseg, dev_rows, clip, skip, ch);
+    else opt_table_launch_kind<VFS_OPT_SGD, false>(grid, s, p, g, s1, s2, nvec, map, nseg, dev_rows, clip, skip, ch);
+  } else if (kind == VFS_OPT_ADAM) opt_table_launch_kind<VFS_OPT_ADAM, false>(grid, s, p, g, s1, s2, nvec, map, nseg, dev_rows, clip, skip, ch);
+  else opt_table_launch_kind<VFS_OPT_ADAMW, false>(grid, s, p, g, s1, s2, nvec, map, nseg, dev_rows, clip, skip, ch);
+  return vfs_check_launch("opt_step_table");
+}
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ p, long long n, float scale) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] *= scale;
 }

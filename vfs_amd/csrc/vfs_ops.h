@@ -197,6 +197,12 @@ __device__ __forceinline__ int roll_src(int i, int T, int k) {  // index of roll
 // clip: nullptr, or the device coefficient the gradient is multiplied by (vfs_grad_norm_finish's out[1])
 int vfs_sgd_launch(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, const float* clip,
                    const unsigned long long* skip, hipStream_t s);
+// SGD (nesterov too) / Adam / AdamW over the whole arena in one launch, param groups looked up per 16-byte vector in the segment
+// map of opt_table.h; hyper is HOST memory (ngroups x VFS_OPT_HYPER floats), table its device copy written on the stream
+#include "opt_table.h"
+int vfs_opt_table_launch(int kind, float* p, const float* g, float* s1, float* s2, long long n, const int* map, int nseg,
+                         const float* hyper, int ngroups, float* table, int nesterov, int step, const float* clip,
+                         const unsigned long long* skip, hipStream_t s);
 int vfs_scale_launch(float* p, long long n, float scale, hipStream_t s);
 int vfs_scale_by_launch(float* p, long long n, const float* coef, hipStream_t s);
 // gradient norm for clipping: per-workgroup partials of a range into rows[VFS_GRAD_NORM_ROWS], then norm and coefficient

@@ -11,7 +11,16 @@ the update kernel multiplies the gradient by the coefficient it reads there.  No
 stays free of synchronisation and of values baked into a recorded chain; `last_grad_norm()` (what OptimizerHook logs as
 `grad_norm`) reads a pinned copy queued behind the step.  The padding words between parameters in the gradient arena are zero
 (allocated zeroed; gradients are written through the per-parameter views, the bucket scaling and all-reduce keep zeros zero),
-so the reduction may sweep them."""
+so the reduction may sweep them.
+
+Param groups (mmcv's build_optimizer with `paramwise_cfg`, configs/r*_*.py:134, apis/train.py:72: one group per parameter with its
+own lr and weight decay), nesterov momentum, Adam and AdamW take a second path: one call of vfs_opt_step_table - ONE update launch
+over the whole arena, behind two small table-write launches when there are more than 224 groups.  A segment map on the
+device (built once per arena layout) tells the kernel which 16-byte vectors are trainable and which group they belong to; the
+groups' hyperparameters travel with every step as launch arguments, so `param_groups[i]['lr'] = ...` (an LR schedule,
+`build_lr_updater`) holds from the next step on and nothing waits for a copy.  One group of plain SGD - every
+shipped config - keeps the launches above."""
+import inspect
 import math
 import os
 
@@ -78,13 +87,34 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0):
     return out[0]
 
 
-class SGD(torch.optim.Optimizer):
-    def __init__(self, model, lr=0.05, momentum=0.9, weight_decay=1e-4, grad_clip=None):
+_KINDS = dict(SGD=0, Adam=1, AdamW=2)      # vfs_opt_step_table's `kind`
+_MAX_GROUPS = 448                          # VFS_OPT_MAX_GROUPS (csrc/opt_table.h)
+
+
+def _torch_defaults(name, **kw):
+    """the `defaults` of the same-named torch.optim class for these options: the param groups then carry every key torch's own
+    step() reads, so a state_dict() loads into torch.optim.<name> and runs there; torch's argument checks (negative lr, nesterov
+    without momentum, ...) come along"""
+    return dict(getattr(torch.optim, name)([torch.zeros(1)], **kw).defaults)
+
+
+class _ArenaOptimizer(torch.optim.Optimizer):
+    """What SGD, Adam and AdamW on the flat arena share: the state arenas with their per-parameter views, the choice between the
+    single-group launches and the table-driven one, gradient clipping, the SyncBN skip word."""
+    _kind = 'SGD'
+    _state_names = ('momentum_buffer',)
+
+    def __init__(self, model, defaults, grad_clip=None, param_groups=None):
         self.model = model
-        params = [p for p in model.parameters() if p.requires_grad]
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
-        self._buf = None
+        params = param_groups if param_groups is not None else [p for p in model.parameters() if p.requires_grad]
+        super().__init__(params, defaults)
+        if len(self.param_groups) > _MAX_GROUPS:
+            raise ValueError(f'{len(self.param_groups)} param groups: the table-driven step holds at most {_MAX_GROUPS}')
+        self._arenas = None        # state name -> arena with the layout of the parameter arena
         self._segments = None
+        self._table = None         # (key, per-parameter segments, device map, device hyperparameter table, host hyperparameters)
+        self._step = 0             # torch's state['step'] (Adam / AdamW), the same for every parameter
+        self._steps = None
         self.grad_clip = None      # (max_norm, norm_type) or None
         if grad_clip is not None:
             gc = dict(grad_clip)
@@ -99,36 +129,83 @@ class SGD(torch.optim.Optimizer):
         self._norm_out = None
         self._norm_pending = None
 
+    @property
+    def _buf(self):
+        """the first state arena (SGD: the momentum arena)"""
+        return None if self._arenas is None else self._arenas[self._state_names[0]]
+
     def zero_grad(self, set_to_none=False):
         f = self.model._ensure_arena()
         f['grads'].zero_()
 
     def _arena(self):
-        """momentum arena + the contiguous arena ranges that hold trainable parameters"""
+        """state arenas + the contiguous arena ranges that hold trainable parameters"""
         f = self.model._ensure_arena()
         flat = f['params']
-        if self._buf is None or self._buf.shape != flat.shape or self._buf.device != flat.device:
-            old = {id(p): st.get('momentum_buffer') for p, st in self.state.items()}
-            self._buf = torch.zeros_like(flat)
-            self._segments = None
-            for p, o in zip(f['plist'], f['offsets']):
-                if not p.requires_grad:
-                    continue
-                view = self._buf[o:o + p.numel()].view(p.shape)
-                prev = old.get(id(p))
-                if prev is not None:              # a state restored before the arena existed
-                    view.copy_(prev)
-                self.state[p]['momentum_buffer'] = view
+        if self._arenas is None or self._buf.shape != flat.shape or self._buf.device != flat.device:
+            old = {id(p): dict(st) for p, st in self.state.items()}
+            self._arenas = {name: torch.zeros_like(flat) for name in self._state_names}
+            self._segments = self._table = None
+            trainable = [(p, o) for p, o in zip(f['plist'], f['offsets']) if p.requires_grad]
+            if self._kind != 'SGD':      # torch keeps `step` as a float32 scalar per parameter: views of one host vector
+                self._steps = torch.full((len(trainable),), float(self._step))
+            for i, (p, o) in enumerate(trainable):
+                for name, arena in self._arenas.items():
+                    view = arena[o:o + p.numel()].view(p.shape)
+                    prev = old.get(id(p), {}).get(name)
+                    if prev is not None:              # a state restored before the arena existed
+                        view.copy_(prev)
+                    self.state[p][name] = view
+                if self._steps is not None:
+                    self.state[p]['step'] = self._steps[i]
         key = tuple(p.requires_grad for p in f['plist'])
         if self._segments is None or self._segments[0] != key:
             self._segments = (key, _trainable_segments(f))
         return f, self._segments[1]
 
+    def _group_values(self, grp):
+        """one param group's row of the hyperparameter table (vfs_opt_step_table's `hyper`)"""
+        if self._kind == 'SGD':
+            return (float(grp['lr']), float(grp['weight_decay']), float(grp['momentum']))
+        return (float(grp['lr']), float(grp['weight_decay']), float(grp['betas'][0]), float(grp['betas'][1]), float(grp['eps']))
+
+    def _group_rows(self):
+        """one pass over the param groups -> (their rows, nesterov); refuses the options the kernels do not take per group, or at all"""
+        nesterov = self.param_groups[0].get('nesterov', False)
+        values, rows = self._group_values, []
+        for grp in self.param_groups:
+            if grp.get('dampening', 0) != 0 or grp.get('maximize', False) or grp.get('amsgrad', False) or grp.get('nesterov', False) != nesterov:
+                k = next(k for k, want in (('dampening', 0), ('maximize', False), ('amsgrad', False), ('nesterov', nesterov)) if grp.get(k, want) != want)
+                raise NotImplementedError(f'param group option {k}={grp[k]!r} is not on the VFS path')
+            rows.append(values(grp))
+        return rows, bool(nesterov)
+
+    def _device_table(self, eng, f):
+        """segment map of the arena (one segment per trainable parameter, with its param group) on the device, the table workspace
+        and the host rows; rebuilt when the requires_grad flags (the key _arena() keeps), the arena, the number of groups or the
+        identity or length of a group's `params` list change - a fingerprint of one entry per group, not per parameter"""
+        key = (self._segments[0], f['params'].data_ptr(), tuple([(id(grp['params']), len(grp['params'])) for grp in self.param_groups]))
+        if self._table is None or self._table[0] != key:
+            if len(self.param_groups) > _MAX_GROUPS:
+                raise ValueError(f'{len(self.param_groups)} param groups: the table-driven step holds at most {_MAX_GROUPS}')
+            # a trainable parameter that no group holds follows group 0, as it does on the single-group path
+            owner = {id(p): gi for gi, grp in enumerate(self.param_groups) for p in grp['params']}
+            segs = [(o, o + p.numel(), owner.get(id(p), 0)) for p, o in zip(f['plist'], f['offsets']) if p.requires_grad]
+            n, dev = f['params'].numel(), f['params'].device
+            words = torch.zeros(1, dtype=torch.int64)
+            eng.host_lib.opt_segment_map_words(n, len(segs), words)
+            host_map = torch.zeros(max(int(words), 4), dtype=torch.int32)
+            seg_t = torch.tensor(segs, dtype=torch.int64).reshape(-1, 3) if segs else torch.zeros(1, 3, dtype=torch.int64)
+            eng.host_lib.opt_segment_map(seg_t, len(segs), n, len(self.param_groups), host_map, host_map.numel())
+            table = torch.zeros(len(self.param_groups) * 8, dtype=torch.float32, device=dev)
+            self._table = (key, len(segs), host_map.to(dev), table, torch.zeros(len(self.param_groups), 8), sum(e - b for b, e, _ in segs))
+        return self._table[1:]
+
     @torch.no_grad()
     def step(self, closure=None):
         f, segs = self._arena()
         flat, g = f['params'], f['grads']
-        grp = self.param_groups[0]
+        rows, nesterov = self._group_rows()
         eng = shared_engine()
         bump_params_epoch()      # raw-pointer update: caches derived from the parameters (vfs_amd/exact.py) must refresh
         # data parallel with the SyncBN window exchange: its error word gates the update on the device (a peer that never arrived
@@ -136,13 +213,30 @@ class SGD(torch.optim.Optimizer):
         x = eng._p2p
         skip = x.state[1:2] if x is not None and x.state.device == flat.device else None
         clip = self._clip_coefficient(eng, g, segs) if self.grad_clip is not None and segs else None
-        for lo, hi in segs:
-            if clip is None:
-                eng.timed('sgd', (0.0, 20.0 * (hi - lo)), flat.device, eng.lib.sgd_step, flat[lo:hi], g[lo:hi], self._buf[lo:hi], hi - lo,
-                          float(grp['lr']), float(grp['momentum']), float(grp['weight_decay']), skip, eng.stream(flat.device))
-            else:
-                eng.timed('sgd', (0.0, 20.0 * (hi - lo)), flat.device, eng.lib.sgd_step_clip, flat[lo:hi], g[lo:hi], self._buf[lo:hi], hi - lo,
-                          float(grp['lr']), float(grp['momentum']), float(grp['weight_decay']), clip, skip, eng.stream(flat.device))
+        st = eng.stream(flat.device)
+        if self._kind == 'SGD' and not nesterov and all(r == rows[0] for r in rows):
+            # every shipped config: one group of plain SGD, one launch per contiguous trainable range
+            lr, wd, momentum = rows[0]
+            for lo, hi in segs:
+                if clip is None:
+                    eng.timed('sgd', (0.0, 20.0 * (hi - lo)), flat.device, eng.lib.sgd_step, flat[lo:hi], g[lo:hi], self._buf[lo:hi], hi - lo,
+                              lr, momentum, wd, skip, st)
+                else:
+                    eng.timed('sgd', (0.0, 20.0 * (hi - lo)), flat.device, eng.lib.sgd_step_clip, flat[lo:hi], g[lo:hi], self._buf[lo:hi], hi - lo,
+                              lr, momentum, wd, clip, skip, st)
+        elif segs:
+            # param groups that differ, nesterov, Adam, AdamW: one update launch over the whole arena, the groups looked up in the kernel.
+            # The step count is the host's: a step the device skips (the SyncBN error word) still counts, as it would in torch,
+            # which knows nothing of the word - and the word is sticky, _watch_exchange ends such a run.
+            nseg, dev_map, table, hyper, ntrain = self._device_table(eng, f)
+            hyper.numpy()[:, :len(rows[0])] = rows      # in place: the slots behind stay zero
+            self._step += 1
+            if self._steps is not None:
+                self._steps += 1
+            s1 = self._arenas[self._state_names[0]]
+            s2 = self._arenas[self._state_names[1]] if len(self._state_names) > 1 else None
+            eng.timed('sgd', (0.0, (20.0 if s2 is None else 28.0) * ntrain), flat.device, eng.lib.opt_step_table, _KINDS[self._kind], flat, g, s1, s2,
+                      flat.numel(), dev_map, nseg, hyper.data_ptr(), len(rows), table, int(nesterov), max(self._step, 1), clip, skip, st)
         if skip is not None:
             self._watch_exchange(x)
 
@@ -195,27 +289,190 @@ class SGD(torch.optim.Optimizer):
         self._xpending = (host, ev)
 
     def load_state_dict(self, state_dict):
-        """torch's loader replaces the state tensors by copies: put them back into the momentum arena"""
+        """torch's loader replaces the state tensors by copies: put them back into the state arenas.  Adam / AdamW keep one step
+        count for the whole arena (the bias corrections are per launch): a state whose parameters disagree on it is refused."""
         super().load_state_dict(state_dict)
-        loaded = {id(p): st.get('momentum_buffer') for p, st in self.state.items()}
-        self._buf = None
+        loaded = {id(p): dict(st) for p, st in self.state.items()}
+        if self._kind != 'SGD':
+            steps = {int(st['step']) for st in loaded.values() if 'step' in st}
+            if len(steps) > 1:
+                raise ValueError(f'the loaded state holds different step counts ({sorted(steps)[:4]} ...): one count per arena on the VFS path')
+            self._step = steps.pop() if steps else 0
+        self._arenas = None
         f, _ = self._arena()
         for p in f['plist']:
-            buf = loaded.get(id(p))
-            if buf is not None and p.requires_grad:
-                self.state[p]['momentum_buffer'].copy_(buf)
+            st = loaded.get(id(p))
+            if st is None or not p.requires_grad:
+                continue
+            for name in self._state_names:
+                if st.get(name) is not None:
+                    self.state[p][name].copy_(st[name])
+
+
+class SGD(_ArenaOptimizer):
+    """torch.optim.SGD (dampening 0) on the arena; `param_groups`: torch's list of group dicts instead of one group of every
+    trainable parameter"""
+
+    def __init__(self, model, lr=0.05, momentum=0.9, weight_decay=1e-4, grad_clip=None, nesterov=False, dampening=0, param_groups=None):
+        if dampening != 0:
+            raise NotImplementedError(f'dampening={dampening!r} is not on the VFS path (0)')
+        super().__init__(model, _torch_defaults('SGD', lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov),
+                         grad_clip=grad_clip, param_groups=param_groups)
+
+
+class Adam(_ArenaOptimizer):
+    """torch.optim.Adam (amsgrad off) on the arena: exp_avg and exp_avg_sq are arenas, one update launch per step"""
+    _kind = 'Adam'
+    _state_names = ('exp_avg', 'exp_avg_sq')
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, grad_clip=None, param_groups=None):
+        if amsgrad:
+            raise NotImplementedError('amsgrad=True is not on the VFS path')
+        super().__init__(model, _torch_defaults(self._kind, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         grad_clip=grad_clip, param_groups=param_groups)
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: the weight decay scales the parameter (p *= 1 - lr wd) instead of joining the gradient"""
+    _kind = 'AdamW'
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, grad_clip=None, param_groups=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, grad_clip=grad_clip,
+                         param_groups=param_groups)
+
+
+_OPTIMIZERS = dict(SGD=(SGD, ('lr', 'momentum', 'weight_decay', 'nesterov', 'dampening')),
+                   Adam=(Adam, ('lr', 'betas', 'eps', 'weight_decay', 'amsgrad')),
+                   AdamW=(AdamW, ('lr', 'betas', 'eps', 'weight_decay', 'amsgrad')))
+_PARAMWISE_KEYS = ('custom_keys', 'bias_lr_mult', 'bias_decay_mult', 'norm_decay_mult', 'dwconv_decay_mult', 'bypass_duplicate')
+
+
+def _paramwise_groups(model, base_lr, base_wd, paramwise_cfg):
+    """mmcv's DefaultOptimizerConstructor.add_params: one param group {params, lr, weight_decay} per trainable parameter, in
+    model.named_parameters() order.  The first custom key (longest first) that is a substring of the parameter's full name decides
+    alone; otherwise bias_lr_mult for the bias of a module that is no norm layer, and norm_decay_mult (BatchNorm modules) or
+    bias_decay_mult (biases) on the weight decay.  dwconv_decay_mult and bypass_duplicate are accepted: no depth-wise convolutions
+    and no shared parameters here."""
+    cfg = dict(paramwise_cfg)
+    for k in cfg:
+        if k not in _PARAMWISE_KEYS:
+            raise NotImplementedError(f'paramwise_cfg option {k!r} is not on the VFS path ({", ".join(_PARAMWISE_KEYS)})')
+    custom = dict(cfg.get('custom_keys') or {})
+    for k, v in custom.items():
+        extra = sorted(set(v) - {'lr_mult', 'decay_mult'})
+        if extra:
+            raise NotImplementedError(f'custom_keys[{k!r}] option {extra[0]!r} is not on the VFS path (lr_mult, decay_mult)')
+    keys = sorted(custom, key=lambda k: (len(k), k), reverse=True)
+    bias_lr, bias_wd, norm_wd = (float(cfg.get(k, 1.)) for k in ('bias_lr_mult', 'bias_decay_mult', 'norm_decay_mult'))
+    owner = {}
+    for m in model.modules():
+        for pname, p in m.named_parameters(recurse=False):
+            owner.setdefault(id(p), (m, pname))
+    groups = []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        lr, wd = base_lr, base_wd
+        hit = next((k for k in keys if k in name), None)
+        if hit is not None:
+            lr, wd = base_lr * custom[hit].get('lr_mult', 1.), base_wd * custom[hit].get('decay_mult', 1.)
+        else:
+            m, pname = owner[id(p)]
+            is_norm = isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+            if pname == 'bias' and not is_norm:
+                lr = base_lr * bias_lr
+            if is_norm:
+                wd = base_wd * norm_wd
+            elif pname == 'bias':
+                wd = base_wd * bias_wd
+        groups.append(dict(params=[p], lr=lr, weight_decay=wd))
+    return groups
 
 
 def build_optimizer(model, cfg, optimizer_config=None):
-    """mmcv build_optimizer for the shipped `optimizer = dict(type='SGD', ...)`; `optimizer_config` is the config's dict of that
-    name (configs/r*_*.py:136; apis/train.py:85-93 makes mmcv's OptimizerHook of it): `grad_clip=None` or absent leaves the
-    optimizer as it is, `grad_clip=dict(max_norm=..., norm_type=2 | 'inf')` clips inside step()."""
+    """mmcv build_optimizer (apis/train.py:72) for `optimizer = dict(type='SGD' | 'Adam' | 'AdamW', ..., paramwise_cfg=...)`
+    (configs/r*_*.py:134); `optimizer_config` is the config's dict of that name (configs/r*_*.py:136; apis/train.py:85-93 makes
+    mmcv's OptimizerHook of it): `grad_clip=None` or absent leaves the optimizer as it is, `grad_clip=dict(max_norm=...,
+    norm_type=2 | 'inf')` clips inside step()."""
     cfg = dict(cfg)
     t = cfg.pop('type')
-    if t != 'SGD':
+    if t not in _OPTIMIZERS:
         raise KeyError(f'optimizer type {t} is not on the VFS path')
+    cls, known = _OPTIMIZERS[t]
+    paramwise_cfg = cfg.pop('paramwise_cfg', None)
+    for k in cfg:
+        if k not in known:
+            raise NotImplementedError(f'optimizer option {k!r} is not on the VFS path ({t}: {", ".join(known)})')
     oc = dict(optimizer_config or {})
     grad_clip = oc.pop('grad_clip', None)
     if oc:
         raise NotImplementedError(f'optimizer_config option {sorted(oc)[0]!r} is not on the VFS path (grad_clip)')
-    return SGD(model, grad_clip=grad_clip, **cfg)
+    groups = None
+    if paramwise_cfg is not None:
+        sig = inspect.signature(cls.__init__).parameters      # lr / weight_decay the config leaves out: the class's defaults
+        groups = _paramwise_groups(model, cfg.get('lr', sig['lr'].default), cfg.get('weight_decay', sig['weight_decay'].default), paramwise_cfg)
+        if len(groups) > _MAX_GROUPS:
+            raise ValueError(f'paramwise_cfg gives {len(groups)} param groups: the table-driven step holds at most {_MAX_GROUPS}')
+    return cls(model, grad_clip=grad_clip, param_groups=groups, **cfg)
+
+
+class LrUpdater:
+    """mmcv's LrUpdaterHook for `lr_config` (configs/r*_*.py:135): before_iter(it) sets every param group's lr from its
+    `initial_lr`.  Host code only - the new values reach the device with the next step's launch arguments."""
+
+    def __init__(self, optimizer, policy, max_iters, iters_per_epoch=None, by_epoch=True, warmup=None, warmup_iters=0, warmup_ratio=0.1,
+                 min_lr=None, min_lr_ratio=None):
+        if policy not in ('fixed', 'CosineAnnealing'):
+            raise NotImplementedError(f'lr_config policy {policy!r} is not on the VFS path (fixed, CosineAnnealing)')
+        if warmup not in (None, 'linear', 'constant', 'exp'):
+            raise ValueError(f'warmup {warmup!r}: None, linear, constant or exp')
+        if warmup is not None and not (warmup_iters > 0 and 0 < warmup_ratio <= 1.0):
+            raise ValueError('warmup needs warmup_iters > 0 and 0 < warmup_ratio <= 1')
+        if policy == 'CosineAnnealing' and (min_lr is None) == (min_lr_ratio is None):
+            raise ValueError('CosineAnnealing takes exactly one of min_lr and min_lr_ratio')
+        if by_epoch and policy != 'fixed' and not iters_per_epoch:
+            raise ValueError('by_epoch=True needs iters_per_epoch')
+        if not max_iters > 0:
+            raise ValueError('max_iters must be positive')
+        self.optimizer, self.policy, self.by_epoch = optimizer, policy, bool(by_epoch)
+        self.max_iters, self.iters_per_epoch = int(max_iters), iters_per_epoch
+        self.warmup, self.warmup_iters, self.warmup_ratio = warmup, int(warmup_iters), float(warmup_ratio)
+        self.min_lr, self.min_lr_ratio = min_lr, min_lr_ratio
+        for grp in optimizer.param_groups:      # a resumed state_dict brings its own initial_lr
+            grp.setdefault('initial_lr', grp['lr'])
+
+    def _regular(self, base, it):
+        if self.policy == 'fixed':
+            return base
+        if self.by_epoch:
+            progress, total = it // self.iters_per_epoch, -(-self.max_iters // self.iters_per_epoch)
+        else:
+            progress, total = it, self.max_iters
+        target = self.min_lr if self.min_lr is not None else base * self.min_lr_ratio
+        return target + 0.5 * (base - target) * (math.cos(math.pi * progress / total) + 1)
+
+    def get_lr(self, base, it):
+        lr = self._regular(base, it)
+        if self.warmup is None or it >= self.warmup_iters:
+            return lr
+        if self.warmup == 'constant':
+            return lr * self.warmup_ratio
+        if self.warmup == 'linear':
+            return lr * (1 - (1 - it / self.warmup_iters) * (1 - self.warmup_ratio))
+        return lr * self.warmup_ratio ** (1 - it / self.warmup_iters)
+
+    def before_iter(self, it):
+        for grp in self.optimizer.param_groups:
+            grp['lr'] = self.get_lr(grp.setdefault('initial_lr', grp['lr']), it)
+
+
+def build_lr_updater(optimizer, lr_config, max_iters, iters_per_epoch=None):
+    """the config's `lr_config = dict(policy='CosineAnnealing', min_lr=0, by_epoch=False)` -> LrUpdater"""
+    cfg = dict(lr_config)
+    if 'policy' not in cfg:
+        raise KeyError('lr_config needs policy')
+    known = ('policy', 'by_epoch', 'warmup', 'warmup_iters', 'warmup_ratio', 'min_lr', 'min_lr_ratio')
+    for k in cfg:
+        if k not in known:
+            raise NotImplementedError(f'lr_config option {k!r} is not on the VFS path ({", ".join(known)})')
+    return LrUpdater(optimizer, cfg.pop('policy'), max_iters, iters_per_epoch=iters_per_epoch, **cfg)
