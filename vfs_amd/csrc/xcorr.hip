@@ -149,6 +149,14 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 __device__ __forceinline__ float log_sigmoid_f(float x) {      // losses.py:8-13
   return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
 }
@@ -174,16 +182,19 @@ __global__ __launch_bounds__(256) void siamfc_loss_kernel(const float* __restric
     if (t == 0) loss_out[0] = l;
     return;
   }
-  float ls = 0.f, as = 0.f;
+  // mean(l / mean(a)) = sum l / sum a.  The two sums are kept in double and the quotient is rounded once: in fp32 the dozen
+  // roundings of the two reductions, of a / n and of n * mean(a) put the loss up to 2 ulp from the float64 value.
+  __shared__ double redd[4];
+  double ls = 0., as = 0.;
   for (int i = t; i < n; i += 256) {
     const float xi = x[i], ti = tgt[i];
     const float p = 1.f / (1.f + expf(-xi));
     const float pw = powf(1.f - p, param), nw = powf(p, param);
-    ls += -(ti * pw * log_sigmoid_f(xi) + (1.f - ti) * nw * log_sigmoid_f(-xi));
-    as += ti * pw + (1.f - ti) * nw;
+    ls += (double)(-(ti * pw * log_sigmoid_f(xi) + (1.f - ti) * nw * log_sigmoid_f(-xi)));
+    as += (double)(ti * pw + (1.f - ti) * nw);
   }
-  const float S = block_sum(ls, red), A = block_sum(as, red) / (float)n;
-  const float L = S / ((float)n * A);
+  const double S = block_sum_d(ls, redd), As = block_sum_d(as, redd);
+  const float L = (float)(S / As), nA = (float)As;      // nA = n mean(a)
   if (t == 0) loss_out[0] = L;
   if (!grad) return;
   for (int i = t; i < n; i += 256) {
@@ -194,7 +205,7 @@ __global__ __launch_bounds__(256) void siamfc_loss_kernel(const float* __restric
     // d/dx[(1-p)^g log p] = (1-p)^g ((1-p) - g p log p);  d/dx[p^g log(1-p)] = p^g (g (1-p) log(1-p) - p)
     const float dl = -(ti * pw * (q - param * p * lp) + (1.f - ti) * nw * (param * q * ln - p));
     const float da = param * p * q * (-(ti) * powf(q, param - 1.f) + (1.f - ti) * powf(p, param - 1.f));
-    grad[i] = scale * (dl - L * da) / ((float)n * A);
+    grad[i] = scale * (dl - L * da) / nA;
   }
 }
 int vfs_siamfc_loss_launch(const float* x, const float* tgt, float* loss_out, float* grad, int n, int mode, float param, float scale,

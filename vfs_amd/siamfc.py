@@ -89,6 +89,9 @@ def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=
     eng = shared_engine(xf.device)
     dev = xf.device
     s = eng.stream(dev)
+    n_resp = xf.shape[0] * (xf.shape[2] - zf.shape[2] + 1) * (xf.shape[3] - zf.shape[3] + 1)      # the 1x1 convs keep the size
+    if labels.numel() != n_resp:      # the loss kernel reads n_resp labels: a map built for another response size would be read past its end
+        raise ValueError(f'head_loss_backward: {labels.numel()} labels {tuple(labels.shape)} for {n_resp} responses')
     z, x = _nhwc_bf16(zf), _nhwc_bf16(xf)
     convs = isinstance(head, SiamConvFC)
     if convs and (len(head.z_convs) != 1):
