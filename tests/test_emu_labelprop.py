@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import vfs_oracle as O
-from tests.emu_util import rb
+from tests.test_labelprop_exact import l2norm_rule, post_explained
 
 
 def _bank(T, H, W, C, CO, seed):
@@ -24,10 +24,10 @@ def run_labelprop_case(be, T, H, W, C, CO, radius, slots, qframe, topk=10, seed=
     lib = be.hostlib
     feats, seg = _bank(T, H, W, C, CO, seed)
     fb = torch.empty(T, H * W, C, dtype=torch.bfloat16)
-    lib.l2norm_rows(feats.to(torch.bfloat16), fb, T * H * W, C, None)
-    xin = rb(feats)
-    want_n = rb(F.normalize(xin, p=2, dim=2))
-    assert (fb.float() - want_n).abs().max() <= 2 ** -8 * want_n.abs().max() * 1.01
+    xin = feats.to(torch.bfloat16)
+    lib.l2norm_rows(xin, fb, T * H * W, C, None)
+    # every element: a bf16 neighbour of the float64 quotient, and the nearest one outside the kernel's fp32 error band
+    l2norm_rule(xin.reshape(T * H * W, C), fb.reshape(T * H * W, C), f'l2norm {T}x{H}x{W}x{C}')
     out = torch.full((H * W, CO), float('nan'))
     ks = (ctypes.c_int * len(slots))(*slots)
     ws = torch.zeros(96 * H * W * 10 * 2)       # vfs_labelprop_workspace_bytes
@@ -86,8 +86,12 @@ def test_seg_postprocess_and_onehot(backend):
     lab = torch.zeros(Ho, Wo, dtype=torch.uint8)
     lib.seg_postprocess(seg, partial, lab, H, W, CO, Ho, Wo, None)
     want = O.seg_postprocess(seg.t().reshape(1, CO, H, W), (Ho, Wo))[0]
-    mism = (lab != want).float().mean()
-    assert mism < 1e-3, mism          # fp32 rounding can flip exact near-ties between channels
+    # fp32 rounding can flip near-ties between channels and nothing else: every label that is not the float64 argmax must be such
+    # a near-tie (tests/test_labelprop_exact.py, 3.), and the labels differ from the fp32 oracle's no more often than those occur
+    off64, near = post_explained(seg.numpy(), H, W, Ho, Wo, lab.numpy(), 'seg_postprocess 12x16 -> 96x128')
+    post_explained(seg.numpy(), H, W, Ho, Wo, want.numpy(), 'the fp32 oracle, 12x16 -> 96x128')
+    mism = float((lab != want).float().mean())
+    assert mism <= min(near, 1e-3), (mism, off64, near)
     labels = torch.randint(0, CO, (H * W,), generator=g).to(torch.uint8)
     oh = torch.zeros(H * W, CO)
     lib.onehot(labels, oh, H * W, CO, None)

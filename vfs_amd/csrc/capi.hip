@@ -823,6 +823,8 @@ int vfs_f32_to_bf16(const float* src, vfs_bf16* dst, long long n, float scale, v
 int vfs_bf16_to_f32(const vfs_bf16* src, float* dst, long long n, vfs_stream_t stream) { return vfs_bf16_to_f32_launch(src, dst, n, stream_of(stream)); }
 
 int vfs_l2norm_rows(const vfs_bf16* x, vfs_bf16* y, long long P, int C, vfs_stream_t stream) {
+  if (P < 1 || P > 4LL * 0x7fffffff || C < 1) return vfs_set_error(VFS_ERR_SHAPE, "l2norm_rows: P >= 1 (four rows per workgroup), C >= 1");
+  if (!x || !y) return vfs_set_error(VFS_ERR_ARG, "l2norm_rows: null buffer");
   return vfs_l2norm_rows_launch(x, y, P, C, stream_of(stream));
 }
 int vfs_labelprop_workspace_bytes(int H, int W, long long* bytes) {
@@ -833,7 +835,16 @@ int vfs_labelprop_workspace_bytes(int H, int W, long long* bytes) {
 int vfs_labelprop(const vfs_bf16* fbank, const float* sbank, float* out, void* workspace, long long workspace_bytes, int qframe,
                   const int* kslot, int nkeys, int H, int W, int C, int CO, int radius, int non_mask_len, int topk, float temperature,
                   vfs_stream_t stream) {
+  // the cheap refusals come before the workspace is looked at: nothing below may index with these
+  if (H < 1 || W < 1 || C < 1 || CO < 1) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: H, W, C, CO >= 1");
+  if (topk < 1 || topk > 10) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: 1 <= topk <= 10");
+  if ((long long)H * W > 0x7fffffff / LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: nkeys * H * W must fit the int candidate ids");
   if (int rc = lp_check("labelprop", nkeys, radius, non_mask_len, true, workspace, workspace_bytes, H, W)) return rc;
+  if (!fbank || !sbank || !out || !kslot) return vfs_set_error(VFS_ERR_ARG, "labelprop: null buffer");
+  if (qframe < 0) return vfs_set_error(VFS_ERR_ARG, "labelprop: qframe >= 0");
+  for (int i = 0; i < nkeys; ++i)
+    if (kslot[i] < 0) return vfs_set_error(VFS_ERR_ARG, "labelprop: kslot entries >= 0");
+  if (!(temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop: temperature > 0");
   LabelPropArgs a{};
   a.fbank = fbank; a.sbank = sbank; a.out = out; a.qframe = qframe; a.nkeys = nkeys;
   a.pval = (float*)workspace; a.pidx = lp_pidx(workspace, H, W);
@@ -843,9 +854,17 @@ int vfs_labelprop(const vfs_bf16* fbank, const float* sbank, float* out, void* w
 }
 int vfs_seg_postprocess(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                         vfs_stream_t stream) {
+  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || CO < 1 || CO > LP_MAX_CLASSES)
+    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess: H, W, Ho, Wo >= 1, 1 <= classes <= 256");
+  if ((long long)Ho * Wo > 0x7fffffff - 255 || (long long)H * W * CO > 0x7fffffff)
+    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess: Ho * Wo and H * W * classes must fit an int");
+  if (!seg || !partial || !label) return vfs_set_error(VFS_ERR_ARG, "seg_postprocess: null buffer");
   return vfs_seg_postprocess_launch(seg, partial, label, H, W, CO, Ho, Wo, stream_of(stream));
 }
 int vfs_onehot(const uint8_t* labels, float* out, int P, int CO, vfs_stream_t stream) {
+  if (P < 1 || CO < 1 || CO > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "onehot: P >= 1, 1 <= classes <= 256");
+  if ((long long)P * CO > 0x7fffffff - 255) return vfs_set_error(VFS_ERR_SHAPE, "onehot: P * classes must fit an int");
+  if (!labels || !out) return vfs_set_error(VFS_ERR_ARG, "onehot: null buffer");
   return vfs_onehot_launch(labels, out, P, CO, stream_of(stream));
 }
 

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void labelprop_kernel(LabelPropArgs a) {
         for (int c = 1; c < 4 * LP_TOPK; ++c)
           if (cv[c] > bvv) { bvv = cv[c]; best = c; }
         pv[k] = bvv; pi[k] = ci[best];
-        cv[best] = -INFINITY;
+        cv[best] = -INFINITY; ci[best] = -1;     // an exhausted list ends in (-inf, -1), not in the id of an entry already taken
       }
     }
   }
