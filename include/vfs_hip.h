@@ -662,6 +662,43 @@ int vfs_siamfc_upsample(const float* responses, const int* tap_idx, const float*
 int vfs_siamfc_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
                     float one_minus_wi, double window_influence, vfs_stream_t stream);
 
+
+/* ---- SiamFC probe, tracking loop for a batch of sequences: the tracker state on the device, N <= 64 slots in lock-step (a slot
+ * holds one sequence at a time).  Per slot n:
+ *   state    fp64  [N][8] = {center_y, center_x, target_h, target_w, z_sz, x_sz, 0, 0}.  center and target_sz are the host
+ *            loop's float32 values widened; z_sz / x_sz are float32 values after init and float64 from the first step on.
+ *   meta     int32 [N][8] = {active, H, W, fill_r, fill_g, fill_b, row, status}.  H, W <= 32768: the slot's frame size;
+ *            fill: clip(rint(average colour)); row: the next row of boxes / records this slot writes; status: a bit set that the
+ *            kernels only ever OR into - 1: the state is not finite or not below 2^30 in magnitude (or H / W / frame_off out of
+ *            range), 2: a computed crop rectangle left its array, 4: row outside [0, rows_cap).
+ *   frame_off int64 [N]: byte offset of the slot's current frame, uint8 [H][W][3] RGB, in the one `frames` buffer.
+ * Every buffer is device memory.  The arithmetic is the host loop's (vfs_amd/siamfc.py: crop_params, SiamFCProbe._apply_peak) in
+ * the types numpy uses there, without fused multiply-adds.  Sizes are checked before any launch: 1 <= N <= 64, 1 <= S <= 8,
+ * 1 <= out_size, up <= 4096, r * r <= 1024; non-null buffers; 8-byte aligned fp64 / int64 buffers, 16-byte aligned tap tables
+ * and records.
+ *
+ * vfs_siamfc_batch_crops: for every active slot and scale s the crop of vfs_siamfc_crops with the geometry
+ * crop_params((H, W), center, size, out_size, fill) computed on the device in float64, size = x_sz * factors[s], or z_sz when
+ * use_z (then S = 1).  factors fp64 [S].  out fp32 [S][N][3][out_size][out_size] - scale-major, so that vfs_xcorr_fwd's
+ * `m % nz` pairs slot n's S search maps with exemplar n.  The crop is zeros where crop_and_resize returns zeros, for an inactive
+ * slot (nothing else of that slot is read), and for a slot whose state fails the check (status bit 1 or 2; no address is formed
+ * from an unchecked state). */
+int vfs_siamfc_batch_crops(const uint8_t* frames, const long long* frame_off, const double* state, int* meta, const double* factors,
+                           float* out, int N, int S, int out_size, int use_z, vfs_stream_t stream);
+/* vfs_siamfc_batch_upsample: vfs_siamfc_upsample (same kernel, same key format) on responses fp32 [S][N][r][r] -> up_out fp32
+ * [S][N][up][up], penalty fp32 [S]; scale_max uint64 [N][S]. */
+int vfs_siamfc_batch_upsample(const float* responses, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                              unsigned long long* scale_max, int N, int S, int r, int up, vfs_stream_t stream);
+/* vfs_siamfc_batch_peak: one workgroup per slot.  For an active slot: {scale_id, row, col} of vfs_siamfc_peak on the slot's S
+ * maps of up_in [S][N][up][up]; then SiamFCProbe._apply_peak on the slot's state (total_stride, response_up, instance_sz,
+ * scale_lr: the probe's configuration; factors fp64 [S]); boxes[meta.row] (fp64 [rows_cap][4], 1-indexed ltwh computed in float32
+ * and widened), records[meta.row] (int32 [rows_cap][4], 16-byte aligned) = {scale_id, row, col, 0}; meta.row += 1.  With
+ * meta.row outside [0, rows_cap) nothing is written but status bit 4.  An inactive slot is untouched in every word. */
+int vfs_siamfc_batch_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, const double* factors,
+                          double* state, int* meta, double* boxes, int* records, long long rows_cap, int N, int S, int up,
+                          float one_minus_wi, double window_influence, double total_stride, double response_up, double instance_sz,
+                          double scale_lr, vfs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -658,6 +658,27 @@ int vfs_siamfc_peak(const float* up_in, const unsigned long long* scale_max, con
   if (!up_in || !scale_max || !hann || !record) return vfs_set_error(VFS_ERR_ARG, "siamfc_peak: null buffer");
   return vfs_siamfc_peak_launch(up_in, scale_max, hann, record, S, up, one_minus_wi, window_influence, stream_of(stream));
 }
+int vfs_siamfc_batch_crops(const uint8_t* frames, const long long* frame_off, const double* state, int* meta, const double* factors, float* out,
+                           int N, int S, int out_size, int use_z, vfs_stream_t stream) {
+  SiamBatchCropArgs a{};      // every check (null buffers, alignment, sizes) before the launch: vfs_siamfc_batch_crops_check, siamfc_batch.h
+  a.frames = frames; a.frame_off = frame_off; a.state = state; a.meta = meta; a.factors = factors; a.out = out;
+  a.N = N; a.S = S; a.out_size = out_size; a.use_z = use_z;
+  return vfs_siamfc_batch_crops_launch(a, stream_of(stream));
+}
+int vfs_siamfc_batch_upsample(const float* responses, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                              unsigned long long* scale_max, int N, int S, int r, int up, vfs_stream_t stream) {
+  return vfs_siamfc_batch_upsample_launch(responses, tap_idx, tap_w, penalty, up_out, scale_max, N, S, r, up, stream_of(stream));
+}
+int vfs_siamfc_batch_peak(const float* up_in, const unsigned long long* scale_max, const double* hann, const double* factors, double* state,
+                          int* meta, double* boxes, int* records, long long rows_cap, int N, int S, int up, float one_minus_wi,
+                          double window_influence, double total_stride, double response_up, double instance_sz, double scale_lr,
+                          vfs_stream_t stream) {
+  SiamBatchPeakArgs a{};
+  a.up_in = up_in; a.scale_max = scale_max; a.hann = hann; a.factors = factors; a.state = state; a.meta = meta; a.boxes = boxes;
+  a.records = records; a.rows_cap = rows_cap; a.N = N; a.S = S; a.up = up; a.one_minus_wi = one_minus_wi; a.wi = window_influence;
+  a.total_stride = total_stride; a.response_up = response_up; a.instance_sz = instance_sz; a.scale_lr = scale_lr;
+  return vfs_siamfc_batch_peak_launch(a, stream_of(stream));
+}
 int vfs_loss_means(const float* loss, float* means, int K, int N, vfs_stream_t stream) {
   if (!loss || !means) return vfs_set_error(VFS_ERR_ARG, "loss_means: null buffer");
   return vfs_loss_means_launch(loss, means, K, N, stream_of(stream));

@@ -282,17 +282,8 @@ int vfs_adam_launch(float* p, const float* g, float* m, float* v, long long n, f
                     hipStream_t s);
 
 // ---- siamfc_track.hip: SiamFC tracking loop (search crops, response up-sampling, peak search) -------------
-#define VFS_SIAMFC_MAX_SCALES 8
-#define VFS_SIAMFC_MAX_RESP 1024      // r * r floats of one response map in LDS
-struct SiamCropScale {
-  int valid;           // 0: the crop is all zeros (empty in-image patch, negative pad)
-  int px0, py0;        // origin of the in-image patch in the frame
-  int iw, ih;          // its size
-  int ow, oh;          // its size after the resize
-  int padx, pady;      // where it lands in the crop; the rest is `fill`
-  int fill[3];
-  double sx, sy;       // iw / ow, ih / oh (float64 division, as the host's)
-};
+// (the limits, the per-slot state / meta layout, SiamCropScale and the batched entry points' argument checks: siamfc_batch.h, HIP-free)
+#include "siamfc_batch.h"
 struct SiamCropArgs {
   const uint8_t* frame;      // [H][W][3]
   float* out;                // [S][3][out_size][out_size]
@@ -304,6 +295,33 @@ int vfs_siamfc_upsample_launch(const float* resp, const int* tap_idx, const floa
                                unsigned long long* scale_max, int S, int r, int up, hipStream_t s);
 int vfs_siamfc_peak_launch(const float* up_in, const unsigned long long* scale_max, const double* hann, int* record, int S, int up,
                            float one_minus_wi, double wi, hipStream_t s);
+struct SiamBatchCropArgs {
+  const uint8_t* frames;           // every slot's current frame [H][W][3], slot n's at byte frame_off[n]
+  const long long* frame_off;      // [N]
+  const double* state;             // [N][8]
+  int* meta;                       // [N][8]; only the status word is written (OR)
+  const double* factors;           // [S]
+  float* out;                      // [S][N][3][out_size][out_size]
+  int N, S, out_size, use_z;
+};
+struct SiamBatchPeakArgs {
+  const float* up_in;                      // [S][N][up][up]
+  const unsigned long long* scale_max;     // [N][S]
+  const double* hann;                      // [up][up]
+  const double* factors;                   // [S]
+  double* state;                           // [N][8]
+  int* meta;                               // [N][8]
+  double* boxes;                           // [rows_cap][4]
+  int* records;                            // [rows_cap][4]
+  long long rows_cap;
+  int N, S, up;
+  float one_minus_wi;
+  double wi, total_stride, response_up, instance_sz, scale_lr;
+};
+int vfs_siamfc_batch_crops_launch(const SiamBatchCropArgs& a, hipStream_t s);
+int vfs_siamfc_batch_upsample_launch(const float* resp, const int* tap_idx, const float* tap_w, const float* penalty, float* up_out,
+                                     unsigned long long* scale_max, int N, int S, int r, int up, hipStream_t s);
+int vfs_siamfc_batch_peak_launch(const SiamBatchPeakArgs& a, hipStream_t s);
 
 // ---- p2p.hip: SyncBN statistic exchange through IPC-mapped windows ----------------------------------------
 int vfs_p2p_window_bytes_host(long long* bytes, int* max_doubles, int* max_world);

@@ -201,19 +201,29 @@ class SiamFCProbe:
         return float(loss.item())
 
     # ------------------------------------------------------------------ tracking (:199-347)
-    @torch.no_grad()
-    def init(self, img, box):
+    def _start_state(self, img, box):
+        """the tracker state init() derives from the first frame and its 1-indexed ltwh box
+        -> center [2], target_sz [2] (float32 arrays), z_sz, x_sz (float32 scalars), avg_color [3] (float64)"""
         c = self.cfg
         box = np.array([box[1] - 1 + (box[3] - 1) / 2, box[0] - 1 + (box[2] - 1) / 2, box[3], box[2]], dtype=np.float32)
-        self.center, self.target_sz = box[:2], box[2:]
+        center, target_sz = box[:2], box[2:]
+        context = c['context'] * np.sum(target_sz)
+        z_sz = np.sqrt(np.prod(target_sz + context))
+        x_sz = z_sz * c['instance_sz'] / c['exemplar_sz']
+        return center, target_sz, z_sz, x_sz, np.mean(img, axis=(0, 1))
+
+    def _init_windows(self):
+        c = self.cfg
         self.upscale_sz = c['response_up'] * c['response_sz']
         self.hann_window = np.outer(np.hanning(self.upscale_sz), np.hanning(self.upscale_sz))
         self.hann_window /= self.hann_window.sum()
         self.scale_factors = c['scale_step'] ** np.linspace(-(c['scale_num'] // 2), c['scale_num'] // 2, c['scale_num'])
-        context = c['context'] * np.sum(self.target_sz)
-        self.z_sz = np.sqrt(np.prod(self.target_sz + context))
-        self.x_sz = self.z_sz * c['instance_sz'] / c['exemplar_sz']
-        self.avg_color = np.mean(img, axis=(0, 1))
+
+    @torch.no_grad()
+    def init(self, img, box):
+        c = self.cfg
+        self._init_windows()
+        self.center, self.target_sz, self.z_sz, self.x_sz, self.avg_color = self._start_state(img, box)
         if self.device_loop:
             self._init_device_loop(img)
             return
@@ -280,6 +290,17 @@ class SiamFCProbe:
         eng.lib.siamfc_crops(d['frame'], params.ctypes.data, out, d['shape'][0], d['shape'][1], len(sizes), int(out_size),
                              eng.stream(self.device))
 
+    def _device_tables(self, r):
+        """the constant operands of the up-sampling and peak kernels for r x r responses, on the device"""
+        c, dev = self.cfg, self.device
+        S, up = int(c['scale_num']), int(self.upscale_sz)
+        idx, w = _cubic_taps(r, up)
+        pen = np.ones(S, np.float32)
+        pen[:S // 2] = pen[S // 2 + 1:] = np.float32(c['scale_penalty'])
+        return dict(tap_idx=torch.from_numpy(idx.astype(np.int32)).to(dev), tap_w=torch.from_numpy(w).to(dev),
+                    penalty=torch.from_numpy(pen).to(dev), hann=torch.from_numpy(np.ascontiguousarray(self.hann_window)).to(dev),
+                    one_minus_wi=float(np.float32(1 - c['window_influence'])))      # the host multiplies its fp32 map by this scalar
+
     def _init_device_loop(self, img):
         """the exemplar through the crop kernel, then everything update() needs per frame, uploaded / allocated once"""
         c, dev = self.cfg, self.device
@@ -295,14 +316,7 @@ class SiamFCProbe:
         if shape[0] != S or shape[-1] != shape[-2]:
             raise ValueError(f'device_loop: {S} square response maps expected, got {tuple(shape)}')
         d['r'] = r = int(shape[-1])
-        idx, w = _cubic_taps(r, up)
-        d['tap_idx'] = torch.from_numpy(idx.astype(np.int32)).to(dev)
-        d['tap_w'] = torch.from_numpy(w).to(dev)
-        pen = np.ones(S, np.float32)
-        pen[:S // 2] = pen[S // 2 + 1:] = np.float32(c['scale_penalty'])
-        d['penalty'] = torch.from_numpy(pen).to(dev)
-        d['hann'] = torch.from_numpy(np.ascontiguousarray(self.hann_window)).to(dev)
-        d['one_minus_wi'] = float(np.float32(1 - c['window_influence']))      # the host multiplies its fp32 map by this scalar
+        d.update(self._device_tables(r))
         d['up'] = torch.empty(S, up, up, device=dev)
         d['scale_max'] = torch.zeros(S, dtype=torch.int64, device=dev)
         d['record'] = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -324,6 +338,161 @@ class SiamFCProbe:
         scale_id, row, col, _ = d['record'].tolist()      # the frame's only read-back (and its only synchronisation)
         self.last_peak = (scale_id, row, col)
         return self._apply_peak(scale_id, (row, col))
+
+    # ------------------------------------------------------------------ tracking, a batch of sequences (csrc/siamfc_track.hip)
+    @torch.no_grad()
+    def track_batch(self, sequences, boxes, batch=16):
+        """track() for many sequences at once, the tracker state on the device (vfs_siamfc_batch_crops / _upsample / _peak;
+        state layout in include/vfs_hip.h).  sequences: indexable frame sequences with len(), frames RGB uint8 [H,W,3]; boxes:
+        their 1-indexed ltwh boxes; -> a list of float64 [T_i,4] arrays, what track() returns for each sequence.
+
+        At most `batch` (<= 64) slots advance in lock-step: per frame step the slots' frames are packed into one pinned staging
+        buffer and go up in one copy, then crops -> features -> head -> up-sampling -> peak run for all slots, and the peak kernel
+        moves every slot's state and writes its box.  The lengths are known up front, so the schedule is the host's: a slot whose
+        sequence has ended is refilled with the next waiting one (its initial state as init() computes it, uploaded; its exemplar
+        through a one-image feature pass), and goes inactive when none is left.  Nothing is read back before the last step; the
+        host only ever waits for the upload that used the same staging buffer three steps earlier.  Every buffer is allocated
+        once per call, sized by `batch` and the largest frame (the first frame of every sequence is looked at up front).
+        Always the device path, whatever `device_loop` says, with its limitation: one frame size per sequence (sequences may
+        differ).  A slot whose state left the checked range raises RuntimeError naming the sequence."""
+        from collections import deque
+        c, dev = self.cfg, self.device
+        eng = shared_engine(dev)
+        lib = eng.lib
+        nseq = len(sequences)
+        if len(boxes) != nseq:
+            raise ValueError(f'track_batch: {nseq} sequences, {len(boxes)} boxes')
+        if not 1 <= int(batch) <= 64:
+            raise ValueError(f'track_batch: 1 <= batch <= 64, got {batch}')
+        lengths = [len(q) for q in sequences]
+        if min(lengths, default=1) < 1:
+            raise ValueError('track_batch: an empty sequence')
+        if nseq == 0:
+            return []
+        self._init_windows()
+        N, S, up = min(int(batch), nseq), int(c['scale_num']), int(self.upscale_sz)
+        ez, ix = int(c['exemplar_sz']), int(c['instance_sz'])
+        shapes = [tuple(q[0].shape) for q in sequences]
+        if any(len(sh) != 3 or sh[2] != 3 for sh in shapes):
+            raise ValueError('track_batch: frames must be [H,W,3]')
+        nbytes = [sh[0] * sh[1] * 3 for sh in shapes]
+        slot_bytes = (max(nbytes) + 255) // 256 * 256
+        bases = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)      # sequence i owns rows bases[i] .. bases[i + 1] - 1
+        rows_cap = int(bases[-1])
+        cuda = dev.type == 'cuda'
+
+        b = self._bl = dict()
+        b['frames'] = torch.empty(N * slot_bytes, dtype=torch.uint8, device=dev)
+        b['init_frame'] = torch.empty(slot_bytes, dtype=torch.uint8, device=dev)
+        b['state'] = torch.zeros(N, 8, dtype=torch.float64, device=dev)
+        b['meta'] = torch.zeros(N, 8, dtype=torch.int32, device=dev)
+        b['frame_off'] = torch.zeros(N, dtype=torch.int64, device=dev)
+        b['zero_off'] = torch.zeros(1, dtype=torch.int64, device=dev)
+        b['factors'] = torch.from_numpy(np.ascontiguousarray(self.scale_factors, dtype=np.float64)).to(dev)
+        b['one'] = torch.ones(1, dtype=torch.float64, device=dev)
+        b['z'] = torch.zeros(1, 3, ez, ez, device=dev)
+        b['x'] = torch.zeros(S * N, 3, ix, ix, device=dev)
+        b['boxes'] = torch.zeros(rows_cap, 4, dtype=torch.float64, device=dev)
+        b['records'] = torch.zeros(rows_cap, 4, dtype=torch.int32, device=dev)
+        b['seq_status'] = torch.zeros(nseq, dtype=torch.int32, device=dev)
+        one_z = self.features(b['z'])      # a dry pass on blank crops: the exemplar bank's and the responses' sizes
+        b['bank'] = torch.zeros(N, *one_z.shape[1:], device=dev)
+        shape = self.head(b['bank'], self.features(b['x'])).shape
+        if shape[0] != S * N or shape[-1] != shape[-2]:
+            raise ValueError(f'track_batch: {S * N} square response maps expected, got {tuple(shape)}')
+        r = int(shape[-1])
+        b.update(self._device_tables(r))
+        b['up'] = torch.empty(S * N, up, up, device=dev)
+        b['scale_max'] = torch.zeros(N, S, dtype=torch.int64, device=dev)
+        ring = [torch.empty(N * slot_bytes, dtype=torch.uint8, pin_memory=cuda) for _ in range(3)]
+        ring_np = [t.numpy() for t in ring]
+        ring_ev = [torch.cuda.Event() if cuda else None for _ in ring]
+        uploads = 0
+
+        def upload(dst, parts):
+            """parts [(byte offset, frame)] -> dst, through the next staging buffer; the copy is asynchronous"""
+            nonlocal uploads
+            k = uploads % len(ring)
+            if cuda and uploads >= len(ring):
+                ring_ev[k].synchronize()      # the copy that last read this staging buffer, three uploads ago
+            end = 0
+            for off, img in parts:
+                ring_np[k][off:off + img.size].reshape(img.shape)[...] = img
+                end = max(end, off + img.size)
+            dst[:end].copy_(ring[k][:end], non_blocking=True)
+            if cuda:
+                ring_ev[k].record()
+            uploads += 1
+
+        def frame_of(i, t):
+            img = sequences[i][t]
+            if tuple(img.shape) != shapes[i] or img.dtype != np.uint8:
+                raise ValueError(f'track_batch: sequence {i}: frames must be uint8 {shapes[i]} like the first one, got {img.dtype} {tuple(img.shape)}')
+            return img
+
+        def retire(n):
+            b['seq_status'][slot_seq[n]:slot_seq[n] + 1].copy_(b['meta'][n, 7:8])      # device to device: the refill clears the word
+            slot_seq[n] = None
+
+        def refill(n, i):
+            img = frame_of(i, 0)
+            center, target_sz, z_sz, x_sz, avg = self._start_state(img, boxes[i])
+            fill = np.clip(np.rint(avg), 0, 255)
+            b['state'][n].copy_(torch.tensor([center[0], center[1], target_sz[0], target_sz[1], z_sz, x_sz, 0, 0], dtype=torch.float64))
+            b['meta'][n].copy_(torch.tensor([1, shapes[i][0], shapes[i][1], fill[0], fill[1], fill[2], bases[i] + 1, 0], dtype=torch.int32))
+            upload(b['init_frame'], [(0, img)])
+            lib.siamfc_batch_crops(b['init_frame'], b['zero_off'], b['state'][n:n + 1], b['meta'][n:n + 1], b['one'], b['z'], 1, 1, ez, 1,
+                                   eng.stream(dev))
+            b['bank'][n].copy_(self.features(b['z'])[0])
+            slot_seq[n], slot_t[n] = i, 1
+
+        waiting = deque(i for i in range(nseq) if lengths[i] > 1)
+        slot_seq, slot_t = [None] * N, [0] * N
+        while True:
+            moved = False
+            for n in range(N):
+                if slot_seq[n] is not None and slot_t[n] >= lengths[slot_seq[n]]:
+                    retire(n)
+                    if not waiting:
+                        b['meta'][n, 0:1].zero_()      # inactive from here on
+                    moved = True
+                if slot_seq[n] is None and waiting:
+                    refill(n, waiting.popleft())
+                    moved = True
+            live = [n for n in range(N) if slot_seq[n] is not None]
+            if not live:
+                break
+            if moved:      # the frames are packed back to back: the offsets change only when a slot changes hands
+                offs = np.zeros(N, np.int64)
+                offs[live] = np.concatenate([[0], np.cumsum([(nbytes[slot_seq[n]] + 255) // 256 * 256 for n in live])])[:-1]
+                b['frame_off'].copy_(torch.from_numpy(offs))
+            upload(b['frames'], [(int(offs[n]), frame_of(slot_seq[n], slot_t[n])) for n in live])
+            s = eng.stream(dev)
+            lib.siamfc_batch_crops(b['frames'], b['frame_off'], b['state'], b['meta'], b['factors'], b['x'], N, S, ix, 0, s)
+            b['responses'] = resp = self.head(b['bank'], self.features(b['x']))
+            if tuple(resp.shape) != (S * N, 1, r, r):
+                raise ValueError(f'track_batch: response maps {tuple(resp.shape)} differ from those the buffers were sized for')
+            lib.siamfc_batch_upsample(resp, b['tap_idx'], b['tap_w'], b['penalty'], b['up'], b['scale_max'], N, S, r, up, s)
+            lib.siamfc_batch_peak(b['up'], b['scale_max'], b['hann'], b['factors'], b['state'], b['meta'], b['boxes'], b['records'], rows_cap,
+                                  N, S, up, b['one_minus_wi'], float(c['window_influence']), float(c['total_stride']), float(c['response_up']),
+                                  float(c['instance_sz']), float(c['scale_lr']), s)
+            for n in live:
+                slot_t[n] += 1
+
+        out = b['boxes'].cpu().numpy()      # the call's only read-backs (and its only synchronisation with the results)
+        status = b['seq_status'].cpu().numpy()
+        rec = b['records'].cpu().numpy()
+        bad = np.flatnonzero(status)
+        if len(bad):
+            raise RuntimeError('track_batch: ' + ', '.join(f'sequence {i}: status {int(status[i])}' for i in bad) +
+                               ' (1: state not finite or out of range, 2: crop geometry, 4: out of box rows; include/vfs_hip.h)')
+        res = []
+        for i in range(nseq):
+            bx = out[bases[i]:bases[i + 1]].copy()
+            bx[0] = np.asarray(boxes[i], dtype=np.float64)
+            res.append(bx)
+        self.last_batch_records = [rec[bases[i] + 1:bases[i + 1], :3].copy() for i in range(nseq)]      # per frame: scale_id, row, col
+        return res
 
 
 # ---------------------------------------------------------------------------------------------
