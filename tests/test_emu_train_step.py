@@ -679,7 +679,7 @@ def test_rccl_one_rank_group_equals_no_collectives(gpu_backend, monkeypatch):
 
     # the single-process step normally takes shortcuts a SyncBN step cannot (statistics finished in the consumer's prologue,
     # statistics from the stored output for tiny groups): switch them off so that both runs execute the same reduction kernels
-    monkeypatch.setattr(engine, 'FIN_FUSE', False)
+    monkeypatch.setenv('VFS_FIN_FUSE', '0')
     monkeypatch.setenv('VFS_RAW_STATS', '0')
     base_losses, base_sd, _ = run()
     monkeypatch.setenv('MASTER_ADDR', '127.0.0.1')
@@ -804,9 +804,8 @@ def test_sgd_skips_frozen_parameters_and_checkpoints_momentum(backend):
 @pytest.mark.parametrize('depth,shape', [(18, [4, 2, 3, 2, 32, 32]), (50, [4, 2, 3, 1, 32, 32])])
 def test_bit_packed_relu_mask_step_is_bit_identical(backend, depth, shape, monkeypatch):
     """residual joins write a bit-packed ReLU mask and their BatchNorm backward reads it instead of the activation
-    (engine.MASK_BITS, VFS_MASK_BITS): losses and every parameter after two steps equal the run that reads y, bit for bit"""
+    (VFS_MASK_BITS): losses and every parameter after two steps equal the run that reads y, bit for bit"""
     import vfs_amd
-    from vfs_amd import engine as E
     if backend.name == 'emu' and depth == 50:
         pytest.skip('ResNet-50 on the emulator takes half a minute; the GPU runs it (R18 covers the emulator)')
     cfg = vfs_amd.Config.fromfile(os.path.join(REPO, 'configs', f'vfs_r{depth}.py'))
@@ -817,7 +816,7 @@ def test_bit_packed_relu_mask_step_is_bit_identical(backend, depth, shape, monke
     batches = [O.fill_tensor(shape, seed=70 + i, scale=2.0).to(dev) for i in range(2)]
 
     def run(bits):
-        monkeypatch.setattr(E, 'MASK_BITS', bits)
+        monkeypatch.setenv('VFS_MASK_BITS', '1' if bits else '0')
         torch.manual_seed(0)
         model = vfs_amd.build_model(mcfg, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).to(dev).train()
         opt = vfs_amd.build_optimizer(model, cfg.optimizer)

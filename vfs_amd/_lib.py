@@ -6,6 +6,8 @@ import os
 import sys
 import re
 
+from . import knobs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'vfs_hip.h')
 TUNING_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'vfs_hip_tuning.h')      # vfs_set_option: the A/B switchboard, not part of the operator contract
@@ -80,8 +82,7 @@ class VfsLib:
         if fn is None:
             raise AttributeError(name)
 
-        trace = os.environ.get('VFS_TRACE_CALLS') == '1'      # diagnostics: name every entry point before it runs (with
-                                                              # AMD_SERIALIZE_KERNEL=3 the last line names a faulting launch)
+        trace = knobs.flag('VFS_TRACE_CALLS')
 
         def call(*args):
             conv = [a.data_ptr() if hasattr(a, 'data_ptr') else a for a in args]
@@ -102,7 +103,7 @@ def get_lib():
     """The product library (gfx950).  Raises VfsError when it has not been built."""
     global _LIB
     if _LIB is None:
-        _LIB = VfsLib(os.environ.get('VFS_HIP_LIB') or LIB_PATH)     # VFS_HIP_LIB: A/B a variant build of the same ABI
+        _LIB = VfsLib(knobs.text('VFS_HIP_LIB') or LIB_PATH)
     return _LIB
 
 

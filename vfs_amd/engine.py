@@ -9,26 +9,21 @@ Layout of one "unit" (mmcv ConvModule = conv -> BN -> act in the reference):
 Backward of a unit: bn_bwd_reduce -> (all-reduce) -> bn_bwd_apply -> wgrad (+dgrad).
 """
 import math
-import os
 from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
 
+from . import knobs
 from ._lib import Tape, TapeLib, get_lib
 from .packing import bn_fold_eligible, build_pack_table, build_reduce_table, conv_plan, stem_stats_rows, wgrad_halo_eligible, wgrad_splits
 
 BF16 = torch.bfloat16
 
-FIN_FUSE = os.environ.get('VFS_FIN_FUSE', '1') == '1'      # BatchNorm statistics finished in the apply kernels' prologue
-FIN_MAX_ROWS = int(os.environ.get('VFS_FIN_MAX_ROWS', '128'))   # ... for at most this many statistics rows per group
-FIN_XCHG = os.environ.get('VFS_FIN_XCHG', '0') == '1'      # SyncBN (round 6, opt-in): ... and the window exchange folded into the same launch (vfs_bn_act_fin_xchg / vfs_bn_bwd_apply_fin_xchg) - measured LEVEL with the reduction + exchange launch of rounds 3-5 on one GPU (8.92 vs 8.88 ms), and its waiting workgroups hold their CUs, so the default stays 0
-# timing experiments only: kernel families (Engine.timed labels) whose launches are dropped - results are garbage, the step
-# time shows what the family costs on the critical path (no kernel here has data-dependent control flow)
-MASK_ADD = os.environ.get('VFS_MASK_ADD', '1') == '1'     # with MASK_BITS: the identity-branch gradient g * (y > 0) is applied on the fly (vfs_conv_dgrad_maskadd), never written
-MASK_BITS = os.environ.get('VFS_MASK_BITS', '1') == '1'   # residual joins also write a bit-packed ReLU mask; their BatchNorm backward reads it instead of y (R50 -0.3 ms)
-NOMASK = os.environ.get('VFS_DEBUG_NOMASK') == '1'     # what-if timing: BatchNorm backward without reading the activation as ReLU mask
-SKIP = frozenset(filter(None, os.environ.get('VFS_DEBUG_SKIP', '').split(',')))
+
+def side_stream_on(dev):
+    """do the weight gradients (data parallel: and the gradient buckets behind them) get a stream of their own on `dev`?"""
+    return dev.type == 'cuda' and knobs.flag('VFS_SIDE_STREAM')
 
 
 class ConvUnit:
@@ -94,7 +89,7 @@ class Engine:
         self._p2p, self._p2p_tried = None, False      # SyncBN statistic exchange over xGMI (vfs_amd/p2p.py), set up lazily
         self._xseq = 0      # number of the next folded SyncBN exchange of the running launch chain
         self.generation = 0  # bumped whenever a persistent buffer is (re)allocated: recorded launch chains hold raw pointers
-        for kv in filter(None, os.environ.get('VFS_OPTS', '').split(',')):      # kernel A/B knobs: "name=value,..."
+        for kv in knobs.items('VFS_OPTS'):
             name, value = kv.split('=')
             self.lib.set_option(name.strip().encode(), int(value))
 
@@ -174,7 +169,7 @@ class Engine:
         """launch through `fn`; with profiling on, bracket it with events on the launch stream.
         work = algorithmic FLOP of the launch, or (FLOP, algorithmic HBM bytes: every operand once)"""
         flops, nbytes = work if isinstance(work, tuple) else (work, 0.0)
-        if SKIP and kind in SKIP:      # what-if measurement (VFS_DEBUG_SKIP=family,...): the step WITHOUT this family's launches
+        if kind in knobs.items('VFS_DEBUG_SKIP'):      # what-if measurement: the step WITHOUT this family's launches
             return 0
         if self.prof is None or dev.type != 'cuda':
             if self.tape is not None:      # recording: the launch carries its family and algorithmic work onto the tape (_lib.Tape.meta)
@@ -201,7 +196,7 @@ class Engine:
         (exercises the RCCL calls, dtypes and stream ordering on a single-GPU box)"""
         if not (dist.is_available() and dist.is_initialized()):
             return False
-        return self.world > 1 or os.environ.get('VFS_FORCE_COLLECTIVES') == '1'
+        return self.world > 1 or knobs.flag('VFS_FORCE_COLLECTIVES')
 
     def allreduce(self, t):
         """sum a SyncBN statistic buffer over the ranks: the P2P window exchange (vfs_amd/p2p.py; one small kernel, on the launch
@@ -221,7 +216,7 @@ class Engine:
         if self._p2p is not None or self._p2p_tried:
             return self._p2p
         self._p2p_tried = True
-        want = os.environ.get('VFS_SYNCBN_P2P', '1')      # 'force': also in a 1-rank group (measures the exchange kernels' cost on one GPU)
+        want = knobs.text('VFS_SYNCBN_P2P')
         if want not in ('1', 'force') or dev.type != 'cuda' or (self.world < 2 and want != 'force'):
             return None
         from .p2p import P2PExchange
@@ -247,7 +242,7 @@ class Engine:
         """head of a launch chain (forward / backward of a train step): the folded SyncBN exchanges of the chain are numbered from 0
         and the chain counter in device memory moves on (vfs_p2p_chain_start; recorded on the tape like any other call)"""
         self._xseq = 0
-        if not (self.collectives_on and FIN_XCHG and FIN_FUSE):
+        if not (self.collectives_on and knobs.flag('VFS_FIN_XCHG') and knobs.flag('VFS_FIN_FUSE')):
             return
         x = self.p2p_exchange(dev)
         if x is not None:
@@ -320,11 +315,11 @@ class Engine:
         # small groups that are not multiples of the 128-pixel statistics rows (the head's Linear layers on the ResNet-50
         # config: 32 rows per view): ONE launch without statistics rows, the sums come from the stored output
         raw_stats = (want_stats and not fused and not self.collectives_on and mpg <= 2048
-                     and os.environ.get('VFS_RAW_STATS', '1') == '1')
+                     and knobs.flag('VFS_RAW_STATS'))
         # round 6: Linear + BatchNorm1d + ReLU of the head in ONE launch (vfs_linear_bn_act: the workgroup that owns 16 output channels
         # owns all <= 64 rows, so the batch statistics are local to it) instead of conv + statistics + apply
         lin_fused = (raw_stats and u.kind == 'linear' and defer_fin and M <= 256 and G <= 4 and u.cin % 128 == 0 and u.cout % 16 == 0
-                     and os.environ.get('VFS_HEAD_FUSE', '1') == '1')
+                     and knobs.flag('VFS_HEAD_FUSE'))
         if raw_stats:
             fused, want_rows = True, False
         else:
@@ -370,7 +365,8 @@ class Engine:
     def prologue_can_finish(nrows, G, C, xchg=False):
         """may an apply kernel (bn_act / bn_bwd_apply) sum `nrows` statistics rows per group in its prologue - and, with xchg, run the
         SyncBN window exchange of the sums there as well?"""
-        return FIN_FUSE and nrows <= FIN_MAX_ROWS and (not xchg or (FIN_XCHG and G * 2 * min(C, 64) <= 256 and C <= 4096))
+        return (knobs.flag('VFS_FIN_FUSE') and nrows <= knobs.integer('VFS_FIN_MAX_ROWS')
+                and (not xchg or (knobs.flag('VFS_FIN_XCHG') and G * 2 * min(C, 64) <= 256 and C <= 4096)))
 
     def _finish_stats(self, u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer):
         """where the BatchNorm statistics of u's fresh output y get finished: eval parameters, from the stored output (raw_stats),
@@ -413,24 +409,21 @@ class Engine:
             self.timed('bn_stats', (0.0, 8.0 * G * nblk_g * C), dev, lib.bn_reduce_partials, partial, u.sums,
                        self.bn_scratch(G, C, dev), G, nblk_g, C, s)
             self.allreduce(u.sums)
-        if defer and FIN_FUSE:
+        if defer and knobs.flag('VFS_FIN_FUSE'):
             return FinRows(None, 0, count)      # bn_act turns the all-reduced sums into scale / shift itself (any size)
         lib.bn_finalize(u.sums, *params, G, C, count, float(bn.eps), float(bn.momentum), s)
         return None
 
     def can_fold_input_bn(self, u, N, G, H, W, train):
         """may conv unit u read the raw output of its producer (BatchNorm + ReLU folded into the load)?"""
-        if os.environ.get('VFS_BNACT_FUSE', '1') != '1' or u.kind == 'stem' or u.dil != 1:
+        if not knobs.flag('VFS_BNACT_FUSE') or u.kind == 'stem' or u.dil != 1:
             return False
-        # pays only where the saved activation pass is large: the fold costs VALU work in the staging of
-        # the consumer's forward and weight-gradient kernels (round-2 whole-step A/B on MI355X, threshold 48 / 32 / 16 MB:
-        # ResNet-50 9.36 / 9.30 / 9.24 ms, ResNet-18 unchanged - its folded tensors are all >= 48 MB)
-        # whole-image tiles (maps of at most 8x8): the fold is a loss (ResNet-18 layer4 at 256^2, 17 MB: step 6.90 with, 6.82 without -
-        # profiles/r06_fold3x3_threshold_step_ab.txt); VFS_BNACT_FUSE_SMALL=1 keeps it (tests exercise the kernels through the engine)
-        if u.k == 3 and self.conv_plan(u, N, G, H, W).pairs and os.environ.get('VFS_BNACT_FUSE_SMALL', '0') != '1':
+        # whole-image tiles (maps of at most 8x8): the fold is a loss
+        if u.k == 3 and self.conv_plan(u, N, G, H, W).pairs and not knobs.flag('VFS_BNACT_FUSE_SMALL'):
             return False
-        mb = os.environ.get('VFS_BNACT_FUSE_1X1_MB', '16') if u.k == 1 else os.environ.get('VFS_BNACT_FUSE_MB', '16')
-        if N * H * W * u.cin * 2 < float(mb) * (1 << 20):
+        # pays only where the saved activation pass is large: the fold costs VALU work in the staging of the consumer's kernels
+        mb = knobs.number('VFS_BNACT_FUSE_1X1_MB' if u.k == 1 else 'VFS_BNACT_FUSE_MB')
+        if N * H * W * u.cin * 2 < mb * (1 << 20):
             return False
         Ng = N // G
         mpg = Ng * H * W
@@ -452,7 +445,7 @@ class Engine:
             u.mask_bits = None
             return fin.act
         y = self.buf(f'{u.name}{tag}.act', raw.shape, BF16, dev)
-        u.mask_bits = self.buf(f'{u.name}{tag}.mbits', (M * u.cout // 8,), torch.uint8, dev) if (want_mask and MASK_BITS and u.cout % 8 == 0 and (u.cout < 64 or u.cout % 64 == 0)) else None      # slab-major layout (mask8_index): whole 64-channel slabs
+        u.mask_bits = self.buf(f'{u.name}{tag}.mbits', (M * u.cout // 8,), torch.uint8, dev) if (want_mask and knobs.flag('VFS_MASK_BITS') and u.cout % 8 == 0 and (u.cout < 64 or u.cout % 64 == 0)) else None      # slab-major layout (mask8_index): whole 64-channel slabs
         mpg = M // G if train else M
         nbytes = 2.0 * M * u.cout * (2 + (res is not None) + (rres is not None)) + (M * u.cout / 8.0 if u.mask_bits is not None else 0.0)      # raw in, activation out, identity in (+ mask bits out)
         if fin is None:
@@ -480,7 +473,7 @@ class Engine:
         the mask is recomputed from raw inside the kernels.
         rows: the BwdRows the conv_bwd that produced g returned (the reduce pass is skipped), or None."""
         assert rows is None or rows.unit is u, 'backward statistics rows of another unit'
-        if NOMASK:
+        if knobs.flag('VFS_DEBUG_NOMASK'):
             ymask = None       # what-if only (WRONG gradients): the step without the mask operand reads
         if not u.bn.training:
             return self._bn_bwd_eval(u, g, ymask, raw, M, want_gm, relu, rows)
@@ -499,7 +492,7 @@ class Engine:
         raw_row = False
         if rows is not None:     # the producing dgrad already emitted the statistics rows
             partial, nblk = rows.rows, rows.nrows
-        elif (FIN_FUSE and not self.collectives_on and nblk == G and mpg <= 512 and os.environ.get('VFS_HEAD_FUSE', '1') == '1'):
+        elif knobs.flag('VFS_FIN_FUSE') and not self.collectives_on and nblk == G and mpg <= 512 and knobs.flag('VFS_HEAD_FUSE'):
             raw_row = True      # round 6: one statistics row per group (the head's BatchNorm1d layers): the apply pass computes it itself
         else:
             self.timed('bn_bwd_reduce', (0.0, 2.0 * M * C * 2 + mask_bytes), dev, lib.bn_bwd_reduce, g, ymask, raw, u.bnp,
@@ -507,7 +500,7 @@ class Engine:
         dx = self.buf(f'{u.name}.dx', raw.shape, BF16, dev)
         # with the bit-packed mask the masked gradient is not materialised: its consumers take (g, mask) instead (conv_bwd add_mask,
         # the downsample unit's bn_bwd)
-        want_gm = want_gm and not (bits and MASK_ADD and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
+        want_gm = want_gm and not (bits and knobs.flag('VFS_MASK_ADD') and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
         gm = self.buf(f'{u.name}.gm', raw.shape, BF16, dev) if want_gm else None
         abytes = 2.0 * M * C * (3 + want_gm) + mask_bytes      # g, raw in; dx out; activation (or its bit mask) in; masked gradient out
         if raw_row:
@@ -559,7 +552,7 @@ class Engine:
             self.timed('bn_stats', (0.0, 8.0 * nblk * C), dev, lib.bn_bwd_sums_paramgrad, partial, scratch, self.bn_scratch(1, C, dev),
                        u.bn.weight.grad, u.bn.bias.grad, 1, nblk, C, s)
         dx = self.buf(f'{u.name}.dx', raw.shape, BF16, dev)
-        want_gm = want_gm and not (bits and MASK_ADD and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
+        want_gm = want_gm and not (bits and knobs.flag('VFS_MASK_ADD') and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
         gm = self.buf(f'{u.name}.gm', raw.shape, BF16, dev) if want_gm else None
         self.timed('bn_bwd_apply', (0.0, 2.0 * M * C * (3 + want_gm)), dev, lib.bn_bwd_apply, g, ymask, raw, u.bnp, self.zero_sums(C, dev), dx, gm,
                    M, C, M, 1.0, rl, s)
@@ -613,7 +606,7 @@ class Engine:
         """context: subsequent launches go to the side stream, ordered after everything already
         enqueued on the current stream (no-op on the CPU / when VFS_SIDE_STREAM=0)"""
         import contextlib
-        if dev.type != 'cuda' or os.environ.get('VFS_SIDE_STREAM', '1') != '1':
+        if not side_stream_on(dev):
             return contextlib.nullcontext()
         side = self._side.get(dev)
         if side is None:
@@ -634,7 +627,7 @@ class Engine:
         """stem weight gradient; the BN-backward apply pass is folded into its operand load"""
         dev = raw.device
         ntiles = N * ((H + 7) // 8) * ((W + 15) // 16)
-        nb = int(os.environ.get('VFS_STEM_WGRAD_BLOCKS', '1536'))
+        nb = knobs.integer('VFS_STEM_WGRAD_BLOCKS')
         tpb = (ntiles + nb - 1) // nb        # ~6 workgroups per CU: the operand gather is latency-bound
         nblocks = (ntiles + tpb - 1) // tpb
         partial = self.wgrad_partial(u, nblocks, 64, 224, dev)
@@ -724,9 +717,9 @@ class Engine:
         if not need_dgrad:
             return None, None
         gin = g_out if g_out is not None else self.buf(f'{u.name}.gin', (N, H, W, u.cin), BF16, dev)
-        if bn_next is not None and u.stride == 1 and os.environ.get('VFS_BN_FUSE', '1') == '1':
+        if bn_next is not None and u.stride == 1 and knobs.flag('VFS_BN_FUSE'):
             pu, praw, pymask, prelu, G = bn_next
-            if NOMASK:
+            if knobs.flag('VFS_DEBUG_NOMASK'):
                 pymask = None
             Min = N * H * W
             mpg = Min // G

@@ -20,14 +20,14 @@ import tempfile
 import numpy as np
 import torch
 
+from . import knobs, resnet
 from .engine import BF16, shared_engine
 
 F32 = torch.float32
 
 
 def eval_precision(test_cfg):
-    p = None if test_cfg is None else test_cfg.get('precision', None)
-    p = p or os.environ.get('VFS_EVAL_PRECISION', 'fp32')
+    p = resnet.eval_precision(None if test_cfg is None else test_cfg.get('precision', None))
     if p not in ('fp32', 'bf16'):
         raise ValueError(f"test_cfg.precision must be 'fp32' or 'bf16', got {p!r}")
     return p
@@ -80,7 +80,7 @@ def two_pass_ok(precision, with_norm, C):
     """the two-pass exact label propagation (csrc/labelprop2.hip: bf16 hi/lo prefilter + exact rescoring, same bits as the dense
     kernel) needs the fp32 path, unit rows and a channel count its register-resident query tile covers; VFS_LP_TWO_PASS=0 keeps
     the dense kernel (A/B)"""
-    return precision == 'fp32' and with_norm and C in (256, 512, 1024) and os.environ.get('VFS_LP_TWO_PASS', '1') == '1'
+    return precision == 'fp32' and with_norm and C in (256, 512, 1024) and knobs.flag('VFS_LP_TWO_PASS')
 
 
 def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, split_banks=None):
@@ -202,7 +202,7 @@ def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
         pairs = mask_pairs(h, w, radius)
         partial = eng.ws('ws.segpost', 64 * CO * 2, F32, dev)
         nbytes = torch.zeros(1, dtype=torch.int64)
-        entries = int(tc.get('lp2_entries', os.environ.get('VFS_LP2_ENTRIES', 0)))      # list entries per query of the two-pass kernels (0: full capacity, 237 MB at 60 x 107)
+        entries = int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES')      # list entries per query of the two-pass kernels
         if hl is None:
             eng.lib.labelprop_workspace_bytes(h, w, nbytes)
         elif entries > 0:

@@ -22,10 +22,10 @@ groups' hyperparameters travel with every step as launch arguments, so `param_gr
 shipped config - keeps the launches above."""
 import inspect
 import math
-import os
 
 import torch
 
+from . import knobs
 from .engine import bump_params_epoch, shared_engine
 
 
@@ -268,11 +268,12 @@ class _ArenaOptimizer(torch.optim.Optimizer):
             ev.synchronize()
         return float(host[0])
 
-    def _watch_exchange(self, x, every=int(os.environ.get('VFS_P2P_CHECK_EVERY', '50'))):
+    def _watch_exchange(self, x):
         """the error word of the SyncBN window exchange is sticky: once set, every later update is skipped on every rank (the word is
         MAX-reduced over the ranks, trackers.py).  A consumer that never reads the log values would then train as a silent no-op
         (advisor r05): every `every` steps a copy of the word is queued to pinned memory and the copy queued `every` steps earlier -
         long complete, no stall - is looked at; a set word raises here, at most 2 x `every` steps after the failed exchange."""
+        every = knobs.integer('VFS_P2P_CHECK_EVERY')
         self._xsteps = getattr(self, '_xsteps', 0) + 1
         if self._xsteps % every:
             return

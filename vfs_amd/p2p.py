@@ -13,6 +13,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import knobs
+
 
 class P2PExchange:
     def __init__(self, lib, dev, group=None, spin_limit=None):
@@ -20,7 +22,7 @@ class P2PExchange:
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         # polls (each followed by s_sleep 8, ~0.3 us) before a waiting kernel gives up: ~10 minutes by default - a rank whose host
         # stalls (checkpoint, data loader) must not turn into silently wrong statistics; tests use a short limit
-        self.spin_limit = int(spin_limit if spin_limit is not None else os.environ.get('VFS_P2P_SPIN', str(1 << 31)))
+        self.spin_limit = int(spin_limit) if spin_limit is not None else knobs.integer('VFS_P2P_SPIN')
         meta = torch.zeros(3, dtype=torch.int64)
         i32 = torch.zeros(2, dtype=torch.int32)
         lib.p2p_window_bytes(meta, i32[0:1], i32[1:2])

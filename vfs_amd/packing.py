@@ -1,14 +1,14 @@
 """Host helpers shared by the engine and the tests: pack-table construction, the library's tiling plan, wgrad split choice."""
-import os
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
+from . import knobs
+
 PACK_DTYPE = np.dtype([('w', '<u8'), ('wf', '<u8'), ('wd', '<u8'), ('start', '<i8'), ('Cout', '<i4'),
                        ('Cin', '<i4'), ('KH', '<i4'), ('KW', '<i4'), ('kind', '<i4'), ('tile_start', '<i4')])
 assert PACK_DTYPE.itemsize == 56
-FAST_PACK = os.environ.get('VFS_FAST_PACK', '1') == '1'      # 16-byte tile variants of the weight packing (A/B switch)
 
 
 def build_pack_table(entries, device):
@@ -19,12 +19,13 @@ def build_pack_table(entries, device):
     arr = np.zeros(len(entries), PACK_DTYPE)
     start = 0
     tiles = 0
+    fast = knobs.flag('VFS_FAST_PACK')
     for i, (w, wf, wd, kind) in enumerate(entries):
         shp = list(w.shape) + [1, 1]
         assert kind == 1 or shp[2] * shp[3] <= 25
         aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (w, wf, wd))
         ntiles = (w.numel() + 255) // 256 if kind == 1 else ((shp[0] + 31) // 32) * ((shp[1] + 31) // 32)
-        if kind == 0 and aligned and FAST_PACK:      # the two shapes that hold a ResNet's weights: 16-byte accesses (csrc/misc.hip)
+        if kind == 0 and aligned and fast:      # the two shapes that hold a ResNet's weights: 16-byte accesses (csrc/misc.hip)
             if shp[2] * shp[3] == 1 and shp[0] % 64 == 0 and shp[1] % 64 == 0:
                 kind, ntiles = 2, (shp[0] // 64) * (shp[1] // 64)
             elif shp[2] == 3 and shp[3] == 3 and shp[0] % 32 == 0 and shp[1] % 64 == 0:
@@ -120,7 +121,7 @@ def bn_fold_eligible(N, G, H, W, Cin, Cout, k, stride, pad, lib=None):
     if k == 1 and stride == 1 and pad == 0:
         # round 6: the 1x1 / stride-1 consumer (conv2 -> conv3 of a bottleneck block) on the register-staged implicit-GEMM forward and
         # weight-gradient kernels: groups of whole 128-pixel tiles
-        return (os.environ.get('VFS_BNACT_FUSE_1X1', '1') == '1' and Cin % 64 == 0 and Cout % 64 == 0 and N % G == 0 and G <= 8
+        return (knobs.flag('VFS_BNACT_FUSE_1X1') and Cin % 64 == 0 and Cout % 64 == 0 and N % G == 0 and G <= 8
                 and ((N // G) * H * W) % 128 == 0)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     plan = conv_plan(N, G, H, W, Cin, Cout, k, stride, pad, Ho, Wo, lib=lib)
@@ -164,20 +165,20 @@ def wgrad_splits(M, Cout, Ktot, target_blocks=192, halo_geom=None, lib=None):
         colblocks = (Cin // 64) * (Cout // 64)
         # every workgroup writes a 9x64x64 fp32 partial (147 KB): keep ~2 workgroups per CU so
         # the split-K traffic (blocks x 147 KB, written then re-read) stays well below the MFMA time
-        tb = int(os.environ.get('VFS_WGRAD_TB', 192))   # whole-step A/B on MI355X (the kernels run beside the dgrad chain): round 2: 256 > 128 > 512; round 6 (leaner main chain): 192 > 256 > 384 (R18 6.84 -> 6.79 ms)
+        tb = knobs.integer('VFS_WGRAD_TB')
         nsplit = max(1, min(ntiles, (tb + colblocks - 1) // colblocks))
         tps = (ntiles + nsplit - 1) // nsplit
         nsplit = (ntiles + tps - 1) // tps
         return nsplit, tps * 128
-    target_blocks = int(os.environ.get('VFS_WGRAD_TBG', target_blocks))      # round 6 re-tune: 192 (R50 7.95 -> 7.88 ms; 160 level, 128 / 256 / 384 slower)
+    target_blocks = knobs.optional('VFS_WGRAD_TBG', target_blocks)
     nkb = (Ktot + 127) // 128
     ncb = Cout // (128 if Cout % 128 == 0 else 64)
-    # round 6 A/B knobs: a target of their own for the layers with few tiles (large maps: the operands dwarf the partials, more
+    # A/B knobs: a target of their own for the layers with few tiles (large maps: the operands dwarf the partials, more
     # workgroups per CU hide the load latency) and for the layers with many tiles (small maps: the partials rival the operands)
-    if nkb * ncb <= 4 and 'VFS_WGRAD_TBG_SMALL' in os.environ:
-        target_blocks = int(os.environ['VFS_WGRAD_TBG_SMALL'])
-    if nkb * ncb >= 16 and 'VFS_WGRAD_TBG_DEEP' in os.environ:
-        target_blocks = int(os.environ['VFS_WGRAD_TBG_DEEP'])
+    if nkb * ncb <= 4:
+        target_blocks = knobs.optional('VFS_WGRAD_TBG_SMALL', target_blocks)
+    if nkb * ncb >= 16:
+        target_blocks = knobs.optional('VFS_WGRAD_TBG_DEEP', target_blocks)
     # every split writes (and wgrad_reduce re-reads) a full Cout x Ktot fp32 partial: aim for ~2-4
     # workgroups per CU, at least 8 pixel steps (512 pixels) per split, and <= 48 MB of partials
     max_split = max(1, M // 512)

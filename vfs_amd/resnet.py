@@ -4,13 +4,18 @@
 Parameters live in torch.nn containers with the reference's module names so state_dicts are
 interchangeable (`conv1.conv.weight`, `layer2.0.downsample.bn.running_mean`, ...); the arithmetic
 is done by vfs_amd.engine on NHWC bf16 buffers.  There is no torch fallback."""
-import os
-
 import torch
 import torch.nn as nn
 
+from . import knobs
 from .engine import BF16, ConvUnit, Engine
 from .registry import BACKBONES
+
+
+def eval_precision(explicit=None):
+    """'fp32' (the reference's arithmetic, bit-defined) or 'bf16' (the training path's kernels) for an evaluation path: what the
+    caller names (ResNet.eval_precision, test_cfg.precision), else VFS_EVAL_PRECISION"""
+    return explicit or knobs.text('VFS_EVAL_PRECISION')
 
 
 def _kaiming_fan_out_relu_(w):
@@ -377,7 +382,7 @@ class ResNet(nn.Module):
         stem = self.conv1.unit
         count = eng.stem_pool_bn_bwd(stem, g, ctx['pooled'], ctx['idx'], ctx['stem_raw'], N, Hs, Ws, ctx['Hp'], ctx['Wp2'], G,
                                      xpool=ctx.get('xpool'))
-        if os.environ.get('VFS_STEM_FUSED', '1') == '1':
+        if knobs.flag('VFS_STEM_FUSED'):
             eng.stem_wgrad_fused(stem, ctx['x4'], ctx['H'], ctx['Wp'], g, ctx['pooled'], ctx['idx'], ctx['stem_raw'],
                                  N, Hs, Ws, ctx['Hp'], ctx['Wp2'], G, count)
         else:   # materialise dx, then the generic implicit-GEMM stem wgrad
@@ -442,7 +447,7 @@ class ResNet(nn.Module):
             raise RuntimeError('ResNet.forward is the inference entry point; use SimSiamBaseTracker.forward_train')
         eng = shared_engine(x.device)
         N, _, H, W = x.shape
-        precision = getattr(self, 'eval_precision', None) or os.environ.get('VFS_EVAL_PRECISION', 'fp32')
+        precision = eval_precision(getattr(self, 'eval_precision', None))
         if not self.training and precision == 'fp32':
             # eval mode: the reference's fp32 arithmetic, bit-defined (vfs_amd/exact.py, csrc/exact_f32.hip)
             from .exact import exact_state

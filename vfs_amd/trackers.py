@@ -8,7 +8,6 @@ chain through a single autograd node, which accumulates into `param.grad` and --
 torch.distributed is initialised -- all-reduces the flat gradient arena over RCCL in buckets
 that overlap the remaining backward kernels (the DDP reducer's job in the reference,
 apis/train.py:62-66)."""
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -16,8 +15,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import builder
-from .engine import BF16, bump_params_epoch, shared_engine
+from . import builder, knobs
+from .engine import BF16, bump_params_epoch, shared_engine, side_stream_on
 from .registry import TRACKERS
 from .resnet import ResNet
 
@@ -36,7 +35,7 @@ class _hp_chain:
 
     def __init__(self, dev):
         self.dev = dev
-        want = os.environ.get('VFS_MAIN_PRIO')
+        want = knobs.text('VFS_MAIN_PRIO')
         self.on = dev.type == 'cuda' and (want == '1' or (want is None and shared_engine().collectives_on))
 
     def __enter__(self):
@@ -170,7 +169,7 @@ def _freeze_gc_once():
     +3.5 ms per step although the GPU never waited for the host otherwise.  The objects stay alive anyway; young garbage is
     still collected.  Process-wide, therefore OPT-IN: VFS_GC_FREEZE=1 (bench.py sets it; a training script that owns its
     process can too)."""
-    if _GC_FROZEN[0] or os.environ.get('VFS_GC_FREEZE', '0') != '1':
+    if _GC_FROZEN[0] or not knobs.flag('VFS_GC_FREEZE'):
         return
     import gc
     gc.collect()
@@ -339,9 +338,9 @@ class SimSiamBaseTracker(BaseTracker):
         eng = shared_engine()
         if eng.prof is not None:
             return None
-        if dev.type == 'cuda' and os.environ.get('VFS_GRAPHS', '0') == '1' and not eng.collectives_on:
+        if dev.type == 'cuda' and knobs.flag('VFS_GRAPHS') and not eng.collectives_on:
             return 'graph'
-        return 'tape' if os.environ.get('VFS_TAPE', '1') == '1' else None
+        return 'tape' if knobs.flag('VFS_TAPE') else None
 
     def _step_forward(self, imgs):
         dev = imgs.device
@@ -489,17 +488,17 @@ class SimSiamBaseTracker(BaseTracker):
         self.img_head.loss_bwd_nhwc(eng, p, z, gl, dp, Nv, c['T'], c['K'], c['weight'])
         # split-K partials of the weight gradients are reduced by one table-driven launch per stage (data parallel: the
         # stage's gradients must be final before their all-reduce) or one for the whole step (single process)
-        eng.defer_wgrad = os.environ.get('VFS_WGRAD_BATCH', '0') == '1'
+        eng.defer_wgrad = knobs.flag('VFS_WGRAD_BATCH')
         # Data parallel: the gradients of a stage are all-reduced as soon as they are final.  Round 6: the buckets are issued FROM THE
         # SIDE STREAM (the stream the weight gradients run on) - rounds 2-5 joined the side stream into the main chain at every stage
         # boundary, so the dgrad chain waited five times per step for the weight-gradient stream it is supposed to run ahead of.
-        ddp_side = os.environ.get('VFS_DDP_SIDE', '1') == '1'
+        ddp_side = knobs.flag('VFS_DDP_SIDE')
 
         def reduce_now(rng):
             if not eng.collectives_on:
                 return
             eng.flush_wgrad(dev)
-            if ddp_side and dev.type == 'cuda' and os.environ.get('VFS_SIDE_STREAM', '1') == '1':
+            if ddp_side and side_stream_on(dev):
                 with eng.on_side_stream(dev):
                     self._allreduce_range(rng)
             else:
@@ -557,12 +556,12 @@ class SimSiamBaseTracker(BaseTracker):
         cur = torch.cuda.current_stream(g.device) if g.device.type == 'cuda' else None      # the stream the buckets are ordered behind
         world = dist.get_world_size()
         step = max(1, self.grad_bucket_bytes // 4)
-        bf16 = os.environ.get('VFS_GRAD_BF16', '0') == '1'      # opt-in: bf16 buckets halve the xGMI traffic (the reference reduces fp32)
+        bf16 = knobs.flag('VFS_GRAD_BF16')
         if bf16:
             stage = eng.buf('ddp.grad_bf16', (g.numel(),), BF16, g.device)
         # the collective library's own mean (every rank's contribution multiplied by 1 / world on its way into the sum - the very
         # products the separate `scale` launch made, so the bits do not change) saves one pass over the 153 MB gradient arena per step
-        avg = (not bf16 and g.device.type == 'cuda' and dist.get_backend() == 'nccl' and os.environ.get('VFS_DDP_AVG', '1') == '1')
+        avg = (not bf16 and g.device.type == 'cuda' and dist.get_backend() == 'nccl' and knobs.flag('VFS_DDP_AVG'))
         for a in range(lo, hi, step):
             b = min(hi, a + step)
             chunk = g[a:b]
@@ -602,7 +601,7 @@ class SimSiamBaseTracker(BaseTracker):
         eager torch launches between the forward and the backward chain (they left the GPU idle for
         0.33 ms of an 8.5 ms ResNet-18 step).  Same keys, same values (double accumulation), same autograd
         contract: outputs['loss'].backward() runs the backward chain."""
-        if not self.with_img_head or os.environ.get('VFS_FAST_TRAIN_STEP', '1') != '1' or \
+        if not self.with_img_head or not knobs.flag('VFS_FAST_TRAIN_STEP') or \
                 not {'imgs'} <= set(k for k, v in data_batch.items() if v is not None) <= {'imgs', 'label'}:
             return super().train_step(data_batch, optimizer, **kwargs)
         self.iteration += 1
@@ -621,8 +620,8 @@ class SimSiamBaseTracker(BaseTracker):
         else:
             packed = self._loss_means.clone()                  # the engine buffer is rewritten by the next step
         keys = [f'img_head.{i}.loss_feat' for i in range(rows.shape[0])] + ['loss']
-        if os.environ.get('VFS_LAZY_LOG', '1') == '1':
-            if packed.is_cuda and os.environ.get('VFS_LOG_ASYNC', '1') == '1':
+        if knobs.flag('VFS_LAZY_LOG'):
+            if packed.is_cuda and knobs.flag('VFS_LOG_ASYNC'):
                 # the values travel to pinned host memory right behind the forward chain; reading them later waits for THAT
                 # copy only.  A blocking .tolist() on the device tensor drains the whole stream instead: a consumer that
                 # looks once per iteration (mmcv's log buffer, bench.py) then restarts the launch queue from empty every
