@@ -110,10 +110,32 @@ int vfs_conv_dgrad_splitk(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, 
                           int stride, int pad, vfs_stream_t stream);
 /* forward conv with dilated taps (resnet.py:51-58,172-179: ConvModule(padding=dilation, dilation=dilation) of a ResNet built
  * with dilations != 1 - the frozen backbone of the SiamFC probe, projects/siamfc-pytorch/siamfc/default_config_base.py:40-49).
- * Forward only: there is no dgrad / wgrad for dilated layers.  Ho = (H + 2 pad - dilation (KH - 1) - 1) / stride + 1. */
+ * Its backward: vfs_conv_dgrad_dilated / vfs_conv_wgrad_dilated below.  Ho = (H + 2 pad - dilation (KH - 1) - 1) / stride + 1. */
 int vfs_conv_fwd_dilated(const vfs_bf16* x, const vfs_bf16* wf, vfs_bf16* y, const float* bias, float* stats, int N,
                          int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                          int dilation, vfs_stream_t stream);
+/* dgrad of vfs_conv_fwd_dilated (torch autograd of the same call sites, resnet.py:51-58,172-179: ConvModule(padding=dilation,
+ * dilation=dilation) wrt its input - a dilated backbone that is fine-tuned, siamfc_tracker_base.py:131-144 with frozen_stages < 4):
+ *   dx[N,H,W,Cin] = sum over taps (r, s) and Cout of dy[N,Ho,Wo,Cout] at ((h + pad - r dilation) / stride, (w + pad - s dilation) /
+ *   stride) * wd  (+ add, gated by add_mask)
+ * bf16 NHWC operands, wd in the dgrad packing [Cin][KH][KW][Cout], fp32 accumulation on MFMA, ONE bf16 rounding of the output.
+ * add / add_mask as in vfs_conv_dgrad_maskadd: the residual gradient added before the rounding and the bit-packed ReLU mask of its
+ * own tensor that gates it (the identity branch of a dilated BasicBlock); both may be NULL (add_mask needs add).  No fused
+ * BatchNorm-backward statistics: the consumer runs vfs_bn_bwd_reduce.  Stride 1 is the tuned case (the cost of the undilated
+ * implicit-GEMM dgrad); stride > 1 is correct but gathers over the strided gradient: taps that fall between the samples of dy
+ * are multiplied as inserted zeros.  Cin % 64 == 0, Cout % 64 == 0, KH * KW <= 32, every tensor below 4 GiB (VFS_ERR_SHAPE);
+ * dilation >= 1 and non-null dy, wd, dx (VFS_ERR_ARG). */
+int vfs_conv_dgrad_dilated(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, const uint8_t* add_mask,
+                           int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                           int dilation, vfs_stream_t stream);
+/* wgrad of vfs_conv_fwd_dilated (autograd of the same call sites wrt the weight), with the split-K contract of vfs_conv_wgrad:
+ * partial: float[nsplit][Cout][KH*KW*Cin] over linear pixel ranges of pix_per_split pixels (pix_per_split % 64 == 0,
+ * nsplit * pix_per_split >= N*Ho*Wo; pixels past N*Ho*Wo contribute exactly zero), summed in split order and ACCUMULATED into
+ * grad[Cout][Cin][KH][KW] (fp32, OIHW); grad == NULL: only the partials are written (vfs_wgrad_reduce_table reduces them later; every
+ * plan is taken as offered).  Bit-identical from run to run.  Same shape rules and error codes as vfs_conv_dgrad_dilated. */
+int vfs_conv_wgrad_dilated(const vfs_bf16* dy, const vfs_bf16* x, float* partial, float* grad, int N, int H, int W, int Cin,
+                           int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int dilation, int nsplit,
+                           int pix_per_split, vfs_stream_t stream);
 /* conv-BN-ReLU -> conv without materialising the activation: x_raw is the RAW output of the producer unit,
  * in_bnp its float[G][4][Cin] {scale, shift, mean, invstd}, in_npg images per group; relu(x*scale+shift)
  * (rounded to bf16 exactly as vfs_bn_act) is applied while the operand is staged, padding stays zero.

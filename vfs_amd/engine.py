@@ -467,16 +467,17 @@ class Engine:
         ppb = math.gcd(mpg, cap)
         return ppb if ppb >= 16 else mpg
 
-    def bn_bwd(self, u, g, ymask, raw, M, G, want_gm=False, relu=False, rows=None):
+    def bn_bwd(self, u, g, ymask, raw, M, G, want_gm=False, relu=False, rows=None, tag=''):
         """gradient wrt the raw conv output (and optionally the ReLU-masked incoming gradient).
         ymask: the unit's output (residual units); relu=True without ymask: conv->BN->ReLU unit,
         the mask is recomputed from raw inside the kernels.
-        rows: the BwdRows the conv_bwd that produced g returned (the reduce pass is skipped), or None."""
+        rows: the BwdRows the conv_bwd that produced g returned (the reduce pass is skipped), or None.
+        tag: buffer namespace of the pass (a second context of another size alive at the same time keeps its own buffers)."""
         assert rows is None or rows.unit is u, 'backward statistics rows of another unit'
         if knobs.flag('VFS_DEBUG_NOMASK'):
             ymask = None       # what-if only (WRONG gradients): the step without the mask operand reads
         if not u.bn.training:
-            return self._bn_bwd_eval(u, g, ymask, raw, M, want_gm, relu, rows)
+            return self._bn_bwd_eval(u, g, ymask, raw, M, want_gm, relu, rows, tag)
         dev = raw.device
         s = self.stream(dev)
         lib = self.lib
@@ -497,11 +498,11 @@ class Engine:
         else:
             self.timed('bn_bwd_reduce', (0.0, 2.0 * M * C * 2 + mask_bytes), dev, lib.bn_bwd_reduce, g, ymask, raw, u.bnp,
                        partial, M, C, mpg, ppb, rl, s)
-        dx = self.buf(f'{u.name}.dx', raw.shape, BF16, dev)
+        dx = self.buf(f'{u.name}{tag}.dx', raw.shape, BF16, dev)
         # with the bit-packed mask the masked gradient is not materialised: its consumers take (g, mask) instead (conv_bwd add_mask,
         # the downsample unit's bn_bwd)
         want_gm = want_gm and not (bits and knobs.flag('VFS_MASK_ADD') and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
-        gm = self.buf(f'{u.name}.gm', raw.shape, BF16, dev) if want_gm else None
+        gm = self.buf(f'{u.name}{tag}.gm', raw.shape, BF16, dev) if want_gm else None
         abytes = 2.0 * M * C * (3 + want_gm) + mask_bytes      # g, raw in; dx out; activation (or its bit mask) in; masked gradient out
         if raw_row:
             self.timed('bn_bwd_apply', (0.0, abytes + 2.0 * M * C * 2 + mask_bytes), dev, lib.bn_bwd_apply_raw, g, ymask, raw, u.bnp, u.bsums, u.bn.weight.grad, u.bn.bias.grad,
@@ -529,7 +530,7 @@ class Engine:
         """double[1][2][C] of zeros (never written): BatchNorm backward without the batch-statistic terms"""
         return self.zeros(f'ws.zero_sums.{C}', 2 * C, torch.float64, dev)
 
-    def _bn_bwd_eval(self, u, g, ymask, raw, M, want_gm, relu, rows):
+    def _bn_bwd_eval(self, u, g, ymask, raw, M, want_gm, relu, rows, tag=''):
         """BatchNorm in eval mode inside a training step (resnet.py:577-654: frozen_stages, norm_eval, partial_bn): the output is
         an affine map of the input with FIXED coefficients, so dx = g * mask * scale - the apply kernel with zero statistic
         sums - and, when gamma / beta are still trained (norm_eval), dgamma = sum g*mask*xhat, dbeta = sum g*mask with xhat
@@ -551,9 +552,9 @@ class Engine:
             scratch = self.buf(f'{u.name}.bsums', (1, 2, C), torch.float64, dev)
             self.timed('bn_stats', (0.0, 8.0 * nblk * C), dev, lib.bn_bwd_sums_paramgrad, partial, scratch, self.bn_scratch(1, C, dev),
                        u.bn.weight.grad, u.bn.bias.grad, 1, nblk, C, s)
-        dx = self.buf(f'{u.name}.dx', raw.shape, BF16, dev)
+        dx = self.buf(f'{u.name}{tag}.dx', raw.shape, BF16, dev)
         want_gm = want_gm and not (bits and knobs.flag('VFS_MASK_ADD') and C % 64 == 0)      # (the mask-gated add reads whole 64-channel mask words)
-        gm = self.buf(f'{u.name}.gm', raw.shape, BF16, dev) if want_gm else None
+        gm = self.buf(f'{u.name}{tag}.gm', raw.shape, BF16, dev) if want_gm else None
         self.timed('bn_bwd_apply', (0.0, 2.0 * M * C * (3 + want_gm)), dev, lib.bn_bwd_apply, g, ymask, raw, u.bnp, self.zero_sums(C, dev), dx, gm,
                    M, C, M, 1.0, rl, s)
         return dx, gm
@@ -667,7 +668,7 @@ class Engine:
         with self.on_side_stream(dev):
             self.lib.wgrad_reduce_table(tab[0], tab[1], tab[2], self.stream(dev))
 
-    def conv_bwd(self, u, dx, x_in, N, H, W, Ho, Wo, need_dgrad, add=None, g_out=None, bn_next=None, x_in_bn=None, add_mask=None):
+    def conv_bwd(self, u, dx, x_in, N, H, W, Ho, Wo, need_dgrad, add=None, g_out=None, bn_next=None, x_in_bn=None, add_mask=None, tag=''):
         """weight (and bias) gradients accumulate into .grad; returns (input gradient or None, BwdRows or None).
         bn_next = (unit, raw, ymask, relu, G): the BatchNorm unit whose backward consumes the input
         gradient; for stride-1 convs the dgrad epilogue also emits that unit's backward statistics
@@ -677,8 +678,8 @@ class Engine:
         lib = self.lib
         M = N * Ho * Wo
         if u.dil != 1:
-            raise NotImplementedError(f'{u.name}: dilated convolutions are forward-only here (the SiamFC probe freezes its '
-                                      'dilated backbone: frozen_stages=4, norm_eval=True)')
+            raise NotImplementedError(f'{u.name}: conv_bwd takes undilated units; the backward of a dilated convolution is '
+                                      'Engine.conv_bwd_dilated (ResNet._block_bwd routes there)')
         if u.kind == 'stem':
             nsplit, pps = wgrad_splits(M, 64, 256)
             partial = self.wgrad_partial(u, nsplit, 64, 256, dev)
@@ -716,7 +717,7 @@ class Engine:
                     lib.bias_grad(dx, u.bias.grad, M, u.cout, ss)
         if not need_dgrad:
             return None, None
-        gin = g_out if g_out is not None else self.buf(f'{u.name}.gin', (N, H, W, u.cin), BF16, dev)
+        gin = g_out if g_out is not None else self.buf(f'{u.name}{tag}.gin', (N, H, W, u.cin), BF16, dev)
         if bn_next is not None and u.stride == 1 and knobs.flag('VFS_BN_FUSE'):
             pu, praw, pymask, prelu, G = bn_next
             if knobs.flag('VFS_DEBUG_NOMASK'):
@@ -738,6 +739,36 @@ class Engine:
         work = (flops, dbytes + (2.0 * N * H * W * u.cin if add is not None else 0.0))
         self.timed(self.conv_kind(u, N, H, W, dgrad=True), work, dev, lib.conv_dgrad_maskadd, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo, u.cout,
                    u.k, u.k, u.stride, u.pad, s)
+        return gin, None
+
+    def conv_bwd_dilated(self, u, dx, x_in, N, H, W, Ho, Wo, need_dgrad, add=None, add_mask=None, g_out=None, tag=''):
+        """conv_bwd for a unit with u.dil != 1 (vfs_conv_wgrad_dilated / vfs_conv_dgrad_dilated): the weight gradient accumulates
+        into .grad on the side stream (none for a frozen weight; deferred reduction as in conv_bwd), the input gradient takes the
+        residual `add`, gated by the bit-packed `add_mask`.  The dilated dgrad emits no BatchNorm-backward statistics rows: returns
+        (input gradient or None, None) and the consumer's bn_bwd runs its own reduce pass."""
+        dev = dx.device
+        lib = self.lib
+        if u.kind != 'conv' or u.dil == 1:
+            raise ValueError(f'{u.name}: conv_bwd_dilated takes dilated conv units (dil={u.dil}, kind={u.kind})')
+        M = N * Ho * Wo
+        ktot = u.k * u.k * u.cin
+        flops = 2.0 * M * u.cout * ktot
+        if u.weight.requires_grad:
+            nsplit, pps = wgrad_splits(M, u.cout, ktot, lib=self.host_lib)
+            partial = self.wgrad_partial(u, nsplit, u.cout, ktot, dev)
+            wtarget = self.wgrad_target(u, partial, nsplit, u.cout, ktot, u.cin, u.k, 0)
+            with self.on_side_stream(dev):
+                ss = self.stream(dev)
+                self.timed('conv_wgrad_dilated', (flops, 2.0 * (M * u.cout + N * H * W * u.cin) + 8.0 * u.cout * ktot), dev, lib.conv_wgrad_dilated,
+                           dx, x_in, partial, wtarget, N, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, u.dil, nsplit, pps, ss)
+                if u.bias is not None and u.bias.requires_grad:
+                    lib.bias_grad(dx, u.bias.grad, M, u.cout, ss)
+        if not need_dgrad:
+            return None, None
+        gin = g_out if g_out is not None else self.buf(f'{u.name}{tag}.gin', (N, H, W, u.cin), BF16, dev)
+        dbytes = 2.0 * (M * u.cout + N * H * W * u.cin * (2 if add is not None else 1) + u.cout * ktot)
+        self.timed('conv_dgrad_dilated', (flops, dbytes), dev, lib.conv_dgrad_dilated, dx, u.wd, gin, add, add_mask, N, H, W, u.cin, Ho, Wo,
+                   u.cout, u.k, u.k, u.stride, u.pad, u.dil, self.stream(dev))
         return gin, None
 
 

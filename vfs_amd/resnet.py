@@ -251,19 +251,21 @@ class ResNet(nn.Module):
     def last_stage(self):
         return max(self.out_indices)
 
-    def forward_nhwc(self, eng, x4, N, H, W_true, G, train, stop_after_out=True):
-        """x4: NHWC4 bf16 [N,H,Wp,4].  Returns ({stage: (act, h, w, C)}, ctx for backward)."""
-        ctx = dict(N=N, G=G, x4=x4, H=H, Wp=x4.shape[2], blocks=[])
+    def forward_nhwc(self, eng, x4, N, H, W_true, G, train, stop_after_out=True, tag=''):
+        """x4: NHWC4 bf16 [N,H,Wp,4].  Returns ({stage: (act, h, w, C)}, ctx for backward).
+        tag: buffer namespace of this pass - two passes of different sizes whose contexts are alive at the same time (the SiamFC
+        probe's exemplar and search branches) each keep their own activations instead of reallocating the other's."""
+        ctx = dict(N=N, G=G, x4=x4, H=H, Wp=x4.shape[2], blocks=[], tag=tag)
         stem = self.conv1.unit
         stem.true_w = W_true
         stem_train = train and self.conv1.bn.training
-        raw, Hs, Ws, _ = eng.conv_fwd(stem, x4, N, H, x4.shape[2], G, stem_train)
+        raw, Hs, Ws, _ = eng.conv_fwd(stem, x4, N, H, x4.shape[2], G, stem_train, tag=tag)
         Hp, Wp = (Hs + 2 - 3) // 2 + 1, (Ws + 2 - 3) // 2 + 1
         dev = x4.device
-        pooled = eng.buf('backbone.pool', (N, Hp, Wp, 64), BF16, dev)
-        idx = eng.buf('backbone.pool_idx', (N, Hp, Wp, 64), torch.uint8, dev) if train else None
+        pooled = eng.buf(f'backbone.pool{tag}', (N, Hp, Wp, 64), BF16, dev)
+        idx = eng.buf(f'backbone.pool_idx{tag}', (N, Hp, Wp, 64), torch.uint8, dev) if train else None
         # raw conv output at each argmax: the stem's BatchNorm backward reads it instead of gathering from raw
-        xpool = eng.buf('backbone.pool_x', (N, Hp, Wp, 64), BF16, dev) if train else None
+        xpool = eng.buf(f'backbone.pool_x{tag}', (N, Hp, Wp, 64), BF16, dev) if train else None
         npg = N // G if stem_train else N
         eng.timed('bn_relu_maxpool', (0.0, 2.0 * N * Hs * Ws * 64 + N * Hp * Wp * 64 * (2.0 + (3.0 if train else 0.0))), dev,
                   eng.lib.bn_relu_maxpool, raw, stem.bnp, pooled, idx, xpool, N, Hs, Ws, 64, Hp, Wp, npg, eng.stream(dev))
@@ -272,7 +274,7 @@ class ResNet(nn.Module):
         outs = {}
         for si, lname in enumerate(self.res_layers):
             for blk in getattr(self, lname):
-                x, h, w, bctx = self._block_fwd(eng, blk, x, N, h, w, G, train)
+                x, h, w, bctx = self._block_fwd(eng, blk, x, N, h, w, G, train, tag)
                 ctx['blocks'].append(bctx)
             if si in self.out_indices:
                 outs[si] = (x, h, w, x.shape[-1])
@@ -280,7 +282,7 @@ class ResNet(nn.Module):
                 break   # the reference computes the remaining stages and discards them
         return outs, ctx
 
-    def _block_fwd(self, eng, blk, x, N, h, w, G, train):
+    def _block_fwd(self, eng, blk, x, N, h, w, G, train, tag=''):
         convs = blk.convs
         bctx = dict(blk=blk, x=x, h=h, w=w, acts=[], raws=[], dims=[])
         a, ah, aw = x, h, w
@@ -294,7 +296,7 @@ class ResNet(nn.Module):
             # the statistics can be finished by the bn_act that follows directly (not by a folding consumer, and not
             # when the downsample conv - which re-uses the statistics workspace - runs in between)
             defer = (not fold) and not (last and blk.downsample is not None)
-            raw, oh, ow, fin = eng.conv_fwd(c.unit, a, N, ah, aw, G, tr, in_bn=in_bn, defer_fin=defer)
+            raw, oh, ow, fin = eng.conv_fwd(c.unit, a, N, ah, aw, G, tr, tag=tag, in_bn=in_bn, defer_fin=defer)
             bctx['raws'].append(raw)
             bctx['dims'].append((ah, aw, oh, ow))
             M = N * oh * ow
@@ -308,7 +310,7 @@ class ResNet(nn.Module):
                     a = raw
                     bctx['acts'].append(raw)
                 else:
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, tag=tag)
                     bctx['acts'].append(a)
                 bctx['act_bn'].append(in_bn)
                 ah, aw = oh, ow
@@ -316,12 +318,12 @@ class ResNet(nn.Module):
                 if blk.downsample is not None:
                     d = blk.downsample
                     dtr = train and d.bn.training
-                    draw, dh, dw, _ = eng.conv_fwd(d.unit, x, N, h, w, G, dtr)
+                    draw, dh, dw, _ = eng.conv_fwd(d.unit, x, N, h, w, G, dtr, tag=tag)
                     assert (dh, dw) == (oh, ow)
                     bctx['draw'] = draw
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, rres=draw, rbnp=d.unit.bnp, want_mask=train)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, rres=draw, rbnp=d.unit.bnp, want_mask=train, tag=tag)
                 else:
-                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, res=x, want_mask=train)
+                    a = eng.bn_act(c.unit, raw, M, G, tr, True, fin, res=x, want_mask=train, tag=tag)
                 bctx['out'] = a
                 # what the backward needs of the block output: its ReLU mask (bit-packed when the engine wrote one)
                 bctx['mask'] = c.unit.mask_bits if c.unit.mask_bits is not None else a
@@ -368,7 +370,7 @@ class ResNet(nn.Module):
             # the BatchNorm unit that consumes this block's INPUT gradient: the join unit of the block before
             prev = blocks[i - 1] if i > 0 else None
             next_bn = None if prev is None else (prev['blk'].convs[-1].unit, prev['raws'][-1], prev['mask'])
-            g, rows = self._block_bwd(eng, blocks[i], g, N, G, next_bn, need_input_grad=stem_trains or i > first, rows=rows)
+            g, rows = self._block_bwd(eng, blocks[i], g, N, G, next_bn, need_input_grad=stem_trains or i > first, rows=rows, tag=ctx.get('tag', ''))
             if on_stage_done is not None and i in stage_start:
                 notified.add(stage_start[i])
                 on_stage_done(getattr(self, self.res_layers[stage_start[i]]))
@@ -393,7 +395,7 @@ class ResNet(nn.Module):
         if on_stage_done is not None:
             on_stage_done(self.conv1)
 
-    def _block_bwd(self, eng, bctx, g, N, G, next_bn=None, need_input_grad=True, rows=None):
+    def _block_bwd(self, eng, bctx, g, N, G, next_bn=None, need_input_grad=True, rows=None, tag=''):
         """next_bn = (unit, raw, out) of the preceding block's join: the dgrad that completes this block's
         input gradient also emits that unit's BatchNorm-backward statistics (Engine.conv_bwd), returned next to the
         input gradient; rows = those the following block emitted for this block's join.
@@ -407,12 +409,12 @@ class ResNet(nn.Module):
         ih, iw, oh, ow = bctx['dims'][last]
         M = N * oh * ow
         # join: y = relu(bn_last(raw) + identity)
-        dx, gm = eng.bn_bwd(convs[last].unit, g, bctx['mask'], bctx['raws'][last], M, G, want_gm=True, rows=rows)
+        dx, gm = eng.bn_bwd(convs[last].unit, g, bctx['mask'], bctx['raws'][last], M, G, want_gm=True, rows=rows, tag=tag)
         gmask = None
         if gm is None:       # bit-packed mask: the masked gradient g * (y > 0) is applied on the fly by its consumers
             gm, gmask = g, bctx['mask']
         if blk.downsample is not None:
-            ddx, _ = eng.bn_bwd(blk.downsample.unit, gm, gmask, bctx['draw'], M, G)
+            ddx, _ = eng.bn_bwd(blk.downsample.unit, gm, gmask, bctx['draw'], M, G, tag=tag)
         for ci in range(last, -1, -1):
             c = convs[ci]
             ih, iw, oh, ow = bctx['dims'][ci]
@@ -425,17 +427,22 @@ class ResNet(nn.Module):
             else:
                 bn_next = None
             x_in_bn = bctx['act_bn'][ci - 1] if ci > 0 else None
-            gin, rows = eng.conv_bwd(c.unit, dx, x_in, N, ih, iw, oh, ow, need_dgrad=(ci > 0 or need_input_grad), add=add, bn_next=bn_next,
-                               x_in_bn=x_in_bn, add_mask=gmask if add is not None else None)
+            if c.unit.dil != 1:      # dilated taps: kernels of their own, no fused statistics rows (the bn_bwd below reduces)
+                assert x_in_bn is None      # (can_fold_input_bn refuses dilated consumers)
+                gin, rows = eng.conv_bwd_dilated(c.unit, dx, x_in, N, ih, iw, oh, ow, need_dgrad=(ci > 0 or need_input_grad), add=add,
+                                                 add_mask=gmask if add is not None else None, tag=tag)
+            else:
+                gin, rows = eng.conv_bwd(c.unit, dx, x_in, N, ih, iw, oh, ow, need_dgrad=(ci > 0 or need_input_grad), add=add, bn_next=bn_next,
+                                         x_in_bn=x_in_bn, add_mask=gmask if add is not None else None, tag=tag)
             if ci > 0:
                 p = convs[ci - 1]
                 _, _, ph, pw = bctx['dims'][ci - 1]
-                dx, _ = eng.bn_bwd(p.unit, gin, None, bctx['raws'][ci - 1], N * ph * pw, G, relu=True, rows=rows)
+                dx, _ = eng.bn_bwd(p.unit, gin, None, bctx['raws'][ci - 1], N * ph * pw, G, relu=True, rows=rows, tag=tag)
         if blk.downsample is not None:
             d = blk.downsample
             boh, bow = bctx['dims'][last][2:]
             bn_next = None if next_bn is None else (next_bn[0], next_bn[1], next_bn[2], True, groups(next_bn[0]))
-            gin, rows = eng.conv_bwd(d.unit, ddx, bctx['x'], N, h, w, boh, bow, need_dgrad=need_input_grad, add=gin, g_out=gin, bn_next=bn_next)
+            gin, rows = eng.conv_bwd(d.unit, ddx, bctx['x'], N, h, w, boh, bow, need_dgrad=need_input_grad, add=gin, g_out=gin, bn_next=bn_next, tag=tag)
         return gin, rows
 
     # ------------------------------------------------------------------ module-level forward

@@ -1,9 +1,12 @@
-"""The SiamFC linear probe on a frozen VFS backbone (OTB-100 metric of the reference, README.md:87-90): the training and
+"""The SiamFC probe on a frozen or partly unfrozen VFS backbone (OTB-100 metric of the reference, README.md:87-90): the training and
 tracking logic of `TrackerSiamFC` (projects/siamfc-pytorch/siamfc/siamfc_tracker_base.py:88-500) on the HIP kernels, without
 its third-party scaffolding (got10k's Tracker base / dataset classes, cv2, torchvision).
 
   train_step   (:364-387)  frozen dilated backbone (eval) -> 1x1 convs -> cross-correlation -> Balanced / Focal loss ->
                            backward through the head (vfs_xcorr_bwd, vfs_conv_wgrad, vfs_bias_grad) -> Adam / SGD
+                           frozen_stages < 4 (:131-144, the optimizer holds the backbone too): both branches through the bf16
+                           training path, the backward continues through vfs_conv_dgrad of the 1x1 convs into
+                           ResNet.backward_nhwc (dilated layers: vfs_conv_dgrad_dilated / vfs_conv_wgrad_dilated)
   _create_labels (:456-500), current_lr (:349-362), the optimizer / scheduler choices of __init__ (:131-166)
   init / update / track (:199-347): the tracking loop.  Crops and the response up-sampling are cv2 calls in the reference
                            (ops.crop_and_resize -> image_utils.get_cropped_input, cv2.resize INTER_CUBIC); cv2 is absent in
@@ -86,13 +89,20 @@ def create_labels(size, r_pos, r_neg, total_stride, device):
 def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=True):
     """responses = head(z, x); loss (losses.py: 'balance' | 'focal'); with backward=True the head's parameter gradients are
     ACCUMULATED into .grad (create them with zero_grad first).  zf / xf: NCHW fp32 features.  -> (loss tensor [1], responses)"""
-    eng = shared_engine(xf.device)
-    dev = xf.device
+    out, resp, _, _ = head_loss_backward_nhwc(head, _nhwc_bf16(zf), _nhwc_bf16(xf), labels, loss, param, backward)
+    return out, resp
+
+
+def head_loss_backward_nhwc(head, z, x, labels, loss='focal', param=None, backward=True, feat_grads=False):
+    """head_loss_backward on NHWC bf16 features (what the backbone's training path hands over).  feat_grads (fine-tuning,
+    siamfc_tracker_base.py:131-144: the optimizer holds the backbone too): also the gradients wrt z and x, bf16 NHWC - through
+    vfs_xcorr_bwd and, for SiamConvFC, vfs_conv_dgrad of the two 1x1 convs.  -> (loss tensor [1], responses, dz, dx)"""
+    eng = shared_engine(x.device)
+    dev = x.device
     s = eng.stream(dev)
-    n_resp = xf.shape[0] * (xf.shape[2] - zf.shape[2] + 1) * (xf.shape[3] - zf.shape[3] + 1)      # the 1x1 convs keep the size
+    n_resp = x.shape[0] * (x.shape[1] - z.shape[1] + 1) * (x.shape[2] - z.shape[2] + 1)      # the 1x1 convs keep the size
     if labels.numel() != n_resp:      # the loss kernel reads n_resp labels: a map built for another response size would be read past its end
         raise ValueError(f'head_loss_backward: {labels.numel()} labels {tuple(labels.shape)} for {n_resp} responses')
-    z, x = _nhwc_bf16(zf), _nhwc_bf16(xf)
     convs = isinstance(head, SiamConvFC)
     if convs and (len(head.z_convs) != 1):
         raise NotImplementedError('probe training: num_convs=1 heads (siamfc_tracker_base.py:108-113)')
@@ -108,9 +118,13 @@ def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=
     out = torch.empty(1, device=dev)
     g = torch.empty_like(resp) if backward else None
     eng.lib.siamfc_loss(resp, labels.contiguous(), out, g, resp.numel(), mode, float(param), 1.0, s)
-    if backward and convs:
+    dz = dx = None
+    if backward and (convs or feat_grads):
         dzc, dxc = torch.empty_like(zc), torch.empty_like(xc)
         eng.lib.xcorr_bwd(zc, xc, g, dzc, dxc, nz, nx, hz, wz, h, w, c, float(head.out_scale), s)
+        if feat_grads and not convs:
+            dz, dx = dzc, dxc
+    if backward and convs:
         for conv, feat, d in ((head.z_convs[0], z, dzc), (head.x_convs[0], x, dxc)):
             n_, hh, ww, cin = feat.shape
             M, cout = n_ * hh * ww, conv.out_channels
@@ -123,7 +137,14 @@ def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=
                 if conv.bias.grad is None:
                     conv.bias.grad = torch.zeros_like(conv.bias)
                 eng.lib.bias_grad(d, conv.bias.grad, M, cout, s)
-    return out, resp
+            if feat_grads:
+                gf = torch.empty_like(feat)
+                eng.lib.conv_dgrad(d, head._packed_wd(conv), gf, None, n_, hh, ww, cin, hh, ww, cout, 1, 1, 1, 0, s)
+                if feat is z:
+                    dz = gf
+                else:
+                    dx = gf
+    return out, resp, dz, dx
 
 
 class SiamFCProbe:
@@ -140,7 +161,11 @@ class SiamFCProbe:
                      else SiamFC(out_scale=c['out_scale']))
         self.backbone.to(self.device).eval()          # frozen_stages=4 + norm_eval: train(True) leaves every layer in eval mode
         self.head.to(self.device)
-        params = [p for p in self.head.parameters() if p.requires_grad]
+        # frozen_stages < 4 (siamfc_tracker_base.py:131-144): the optimizer holds self.net.parameters(), backbone included; the
+        # backbone runs its bf16 training path inside train_step and stays in eval mode (fp32 executor) everywhere else
+        self.finetune = c['backbone'].get('frozen_stages', -1) < 4 and any(p.requires_grad for p in self.backbone.parameters())
+        params = [p for p in self.backbone.parameters() if p.requires_grad] if self.finetune else []
+        params += [p for p in self.head.parameters() if p.requires_grad]
         wd = c['weight_decay'] if (c['backbone'].get('frozen_stages', -1) < 4 or c['force_wd']) else 0     # :135-137
         if not params:
             self.optimizer = None
@@ -186,6 +211,8 @@ class SiamFCProbe:
 
     def train_step(self, batch, backward=True):
         """batch = (z [N,3,ez,ez], x [N,3,ix,ix]) uint8-range RGB floats, as the reference's Pair dataset yields them"""
+        if self.finetune and backward and self.optimizer is not None:
+            return self._train_step_finetune(batch)
         zf, xf = self.features(batch[0]), self.features(batch[1])
         nz, _, hz, wz = zf.shape
         nx, _, h, w = xf.shape
@@ -199,6 +226,52 @@ class SiamFCProbe:
         if backward and self.optimizer is not None:
             self.optimizer.step()
         return float(loss.item())
+
+    def _train_step_finetune(self, batch):
+        """train_step with a partly unfrozen backbone: loss + gradients of backbone and head, one optimizer step over both"""
+        loss = self.finetune_loss_backward(batch)
+        self.optimizer.step()
+        return float(loss.item())
+
+    def finetune_loss_backward(self, batch, branches=('z', 'x')):
+        """exemplar and search images through the bf16 training path (train() mode; norm_eval keeps every BatchNorm on its running
+        statistics), the loss backward through the head into the backbone passes named in `branches` (the reference: both) - two
+        contexts of different sizes alive at once, each in its own buffer namespace.  Gradients of every optimizer parameter are
+        zeroed, then accumulated into .grad.  -> loss tensor [1]"""
+        eng = shared_engine(self.device)
+        dev, bb = self.device, self.backbone
+        s = eng.stream(dev)
+        bb.train()
+        try:
+            bb.attach(eng)
+            eng.pack_weights()
+            stage = bb.last_stage()
+            feats, ctxs = [], []
+            for tag, imgs in (('.z', batch[0]), ('.x', batch[1])):
+                x = self.normalize(imgs.to(dev).float()).contiguous()
+                N, _, H, W = x.shape
+                Wp = W + (W & 1)
+                x4 = eng.buf(f'backbone.x4{tag}', (N, H, Wp, 4), BF16, dev)
+                eng.lib.imgs_to_nhwc4(x, x4, N, 1, 1, H, W, Wp, s)
+                outs, ctx = bb.forward_nhwc(eng, x4, N, H, W, 1, True, tag=tag)
+                feats.append(outs[stage][0])
+                ctxs.append(ctx)
+            z, x = feats
+            labels = self._create_labels((x.shape[0], 1, x.shape[1] - z.shape[1] + 1, x.shape[2] - z.shape[2] + 1))
+            self.optimizer.zero_grad(set_to_none=False)
+            for grp in self.optimizer.param_groups:
+                for p in grp['params']:
+                    if p.grad is None:
+                        p.grad = torch.zeros_like(p)
+            loss, _, dz, dx = head_loss_backward_nhwc(self.head, z, x, labels, self.cfg['loss'], backward=True, feat_grads=True)
+            if 'x' in branches:
+                bb.backward_nhwc(eng, ctxs[1], {stage: dx})
+            if 'z' in branches:
+                bb.backward_nhwc(eng, ctxs[0], {stage: dz})
+            eng.wgrad_join(dev)
+        finally:
+            bb.eval()
+        return loss
 
     # ------------------------------------------------------------------ tracking (:199-347)
     def _start_state(self, img, box):

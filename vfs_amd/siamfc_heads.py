@@ -68,6 +68,22 @@ class SiamConvFC(nn.Module):
                          conv.out_channels, 1, 1, 1, 0, eng.stream(t.device))
         return y
 
+    def _packed_wd(self, conv):
+        """the conv's weight in the dgrad packing [Cin][1][1][Cout] (the probe's fine-tuning backward: vfs_conv_dgrad towards the
+        backbone features), re-packed when the weight changes"""
+        eng = shared_engine(conv.weight.device)
+        from .engine import params_epoch
+        key = (conv.weight.data_ptr(), conv.weight._version, params_epoch())
+        slot = ('wd', id(conv))
+        if self._packed.get(slot, (None,))[0] != key:
+            dev = conv.weight.device
+            wf = torch.empty(conv.out_channels, 1, 1, conv.in_channels, dtype=BF16, device=dev)
+            wd = torch.empty(conv.in_channels, 1, 1, conv.out_channels, dtype=BF16, device=dev)
+            tab, n, total = build_pack_table([(conv.weight.data, wf, wd, 0)], dev)
+            eng.lib.pack_weights(tab, n, total, eng.stream(dev))
+            self._packed[slot] = (key, wd, wf, tab)
+        return self._packed[slot][1]
+
     def forward(self, z, x):
         z, x = _nhwc_bf16(z), _nhwc_bf16(x)
         for cz, cx in zip(self.z_convs, self.x_convs):
