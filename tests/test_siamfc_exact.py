@@ -55,6 +55,14 @@ Bounded quantities (everything else is equality).  u = 2^-24, the fp32 unit roun
         ulp of a correctly rounded powf alone uses up to half of it.  m and v get the factor 1.001 as well.  The worst
         observed fractions are in MEASUREMENTS.md.
 
+The head on the engine's unit path (section 6).  vfs_amd.SiamConvFC holds one engine.ConvUnit per 1x1 conv, and
+head_loss_backward_nhwc runs their backward through Engine.conv_bwd.  The test restates the head's forward and backward as
+plain library calls in the documented order (conv_fwd per conv; xcorr_fwd, siamfc_loss, xcorr_bwd; per conv conv_wgrad with
+packing.wgrad_splits(M, cout, cin), bias_grad, conv_dgrad) on weights it packs itself.  The same kernels on the same operands
+with the same split plan give the same bits, so everything is compared with torch.equal: loss, responses, dz, dx, both weight
+and both bias gradients, from a non-zero starting .grad.  Shapes: z [2,3,3,C], x [4,5,7,C] - nx = 2 nz, 18 and 140 pixels
+against the 128-pixel tile (ragged, one and two blocks); C = 64 -> 64 and 128 -> 64 (cin != cout in the dgrad packing).
+
 Every case takes well under a second on the emulator, so none is marked `gpu` only.
 backend=emu: host build through the fiber emulator; backend=gpu: libvfs_hip.so on the MI355X."""
 import numpy as np
@@ -474,3 +482,222 @@ def test_head_loss_backward_refuses_labels_of_another_size(backend, head_type):
         backend.eng.lib = lib
     loss, resp = SF.head_loss_backward(head, zf, xf, good, 'balance', backward=False)      # the right count passes
     assert tuple(resp.shape) == (4, 1, 4, 6) and bool(torch.isfinite(loss).all())
+
+
+# ---------------------------------------------------------------------------------------------- 6. the head on the engine's unit path
+HEAD_SCALE = 0.01
+SIDES = ('z', 'x')
+
+
+def head_operands(cin, cout):
+    """features z [2,3,3,cin] / x [4,5,7,cin] NHWC bf16, labels for the [4,1,3,5] responses, and per side (weight, bias) with the
+    (weight, bias) gradients the backward starts from; cout = None: no convs (SiamFC)"""
+    from vfs_amd import siamfc as SF
+    g = seed(36, cin, cout or 0)
+    z, x = torch.randn(2, 3, 3, cin, generator=g).to(BF16), torch.randn(4, 5, 7, cin, generator=g).to(BF16)
+    labels = SF.create_labels((4, 1, 3, 5), 16, 0, 8, CPU)
+    assert set(labels.unique().tolist()) == {0.0, 1.0}, 'test bug: the labels lack a class'
+    if cout is None:
+        return z, x, labels, None, None
+    weights = {side: (torch.randn(cout, cin, 1, 1, generator=g) * 0.1, torch.randn(cout, generator=g) * 0.1) for side in SIDES}
+    start = {side: (torch.randn(cout, cin, 1, 1, generator=g), torch.randn(cout, generator=g)) for side in SIDES}
+    return z, x, labels, weights, start
+
+
+def head_direct(be, z, x, labels, weights, start, loss):
+    """the head's forward and backward as plain library calls -> dict of CPU tensors"""
+    from tests.test_emu_conv import pack
+    from vfs_amd.packing import wgrad_splits
+    lib = be.hostlib
+    feats, conv, wds = dict(z=z, x=x), dict(z=z, x=x), {}
+    for side in SIDES if weights is not None else ():
+        w, b = weights[side]
+        wf, wds[side] = (t.cpu() for t in pack(be, w))
+        n, h, wi, cin = feats[side].shape
+        conv[side] = nan_like((n, h, wi, w.shape[0]), CPU)
+        lib.conv_fwd(feats[side], wf, conv[side], b, None, n, h, wi, cin, h, wi, w.shape[0], 1, 1, 1, 0, None)
+    zc, xc = conv['z'], conv['x']
+    nz, hz, wz, c = zc.shape
+    nx, h, w, _ = xc.shape
+    out = dict(resp=nan_like((nx, 1, h - hz + 1, w - wz + 1), CPU, F32), loss=nan_like((1,), CPU, F32))
+    lib.xcorr_fwd(zc, xc, out['resp'], nz, nx, hz, wz, h, w, c, HEAD_SCALE, None)
+    g = nan_like(out['resp'].shape, CPU, F32)
+    mode = {'balance': 0, 'focal': 1}[loss]
+    lib.siamfc_loss(out['resp'], labels, out['loss'], g, g.numel(), mode, 1.0 if mode == 0 else 2.0, 1.0, None)
+    d = dict(z=nan_like(zc.shape, CPU), x=nan_like(xc.shape, CPU))
+    lib.xcorr_bwd(zc, xc, g, d['z'], d['x'], nz, nx, hz, wz, h, w, c, HEAD_SCALE, None)
+    for side in SIDES:
+        if weights is None:
+            out['d' + side] = d[side]
+            continue
+        n, hh, ww, cin = feats[side].shape
+        M, cout = n * hh * ww, weights[side][0].shape[0]
+        nsplit, pps = wgrad_splits(M, cout, cin)
+        gw, gb = (t.clone() for t in start[side])
+        lib.conv_wgrad(d[side], feats[side], nan_like((nsplit * cout * cin,), CPU, F32), gw, n, hh, ww, cin, hh, ww, cout, 1, 1, 1, 0,
+                       nsplit, pps, None)
+        lib.bias_grad(d[side], gb, M, cout, None)
+        out['d' + side] = nan_like(feats[side].shape, CPU)
+        lib.conv_dgrad(d[side], wds[side], out['d' + side], None, n, hh, ww, cin, hh, ww, cout, 1, 1, 1, 0, None)
+        out[side + '.weight.grad'], out[side + '.bias.grad'] = gw, gb
+    return out
+
+
+_HEAD_REFS = {}
+
+
+def head_reference(be, cin, cout, loss):
+    """(operands, head_direct's result), computed once per backend and case"""
+    key = (be.name, cin, cout, loss)
+    if key not in _HEAD_REFS:
+        ops = head_operands(cin, cout)
+        _HEAD_REFS[key] = (ops, head_direct(be, *ops, loss))
+    return _HEAD_REFS[key]
+
+
+def head_module(be, cin, cout, weights, start):
+    """vfs_amd.SiamConvFC (SiamFC for cout = None) holding `weights`, every .grad at its `start` value"""
+    import vfs_amd
+    if cout is None:
+        return vfs_amd.SiamFC(out_scale=HEAD_SCALE)
+    head = vfs_amd.SiamConvFC(cin, cout, out_scale=HEAD_SCALE)
+    with torch.no_grad():
+        for side in SIDES:
+            conv = getattr(head, side + '_convs')[0]
+            conv.weight.copy_(weights[side][0])
+            conv.bias.copy_(weights[side][1])
+    head.to(be.dev)
+    for side in SIDES:
+        conv = getattr(head, side + '_convs')[0]
+        conv.weight.grad, conv.bias.grad = (t.clone().to(be.dev) for t in start[side])
+    return head
+
+
+def head_engine(be, head, z, x, labels, loss):
+    """head_loss_backward_nhwc(feat_grads=True) -> the dict head_direct returns"""
+    from vfs_amd import siamfc as SF
+    dev = be.dev
+    loss_t, resp, dz, dx = SF.head_loss_backward_nhwc(head, z.to(dev), x.to(dev), labels.to(dev), loss, feat_grads=True)
+    out = dict(loss=loss_t, resp=resp, dz=dz, dx=dx)
+    for side in SIDES if hasattr(head, 'z_convs') else ():
+        conv = getattr(head, side + '_convs')[0]
+        out[side + '.weight.grad'], out[side + '.bias.grad'] = conv.weight.grad, conv.bias.grad
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def assert_same(got, want, what, skip=()):
+    assert sorted(got) == sorted(want)
+    for k in want:
+        if k not in skip:
+            assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), f'{what}: {k} differs from the direct launches'
+    assert bool(torch.isfinite(torch.cat([v.float().flatten() for v in want.values()])).all()), 'test bug: the reference is not finite'
+
+
+@pytest.mark.parametrize('loss', ['balance', 'focal'])
+@pytest.mark.parametrize('cin,cout', [(64, 64), (128, 64), (64, None)], ids=['c64_64', 'c128_64', 'no_convs'])
+def test_head_backward_equals_direct_launches(backend, cin, cout, loss):
+    (z, x, labels, weights, start), want = head_reference(backend, cin, cout, loss)
+    if start is not None:
+        assert all(not torch.equal(want[s + k], start[s][i]) for s in SIDES for i, k in enumerate(('.weight.grad', '.bias.grad'))), \
+            'test bug: a gradient did not move from its starting value'
+    got = head_engine(backend, head_module(backend, cin, cout, weights, start), z, x, labels, loss)
+    assert_same(got, want, f'head {cin} -> {cout} {loss}')
+
+
+def test_head_backward_frozen_conv(backend):
+    """x_convs[0].weight.requires_grad = False: its .grad is left alone, every other result is what the direct launches give"""
+    (z, x, labels, weights, start), want = head_reference(backend, 64, 64, 'focal')
+    head = head_module(backend, 64, 64, weights, start)
+    head.x_convs[0].weight.requires_grad_(False)
+    kept = head.x_convs[0].weight.grad
+    got = head_engine(backend, head, z, x, labels, 'focal')
+    assert head.x_convs[0].weight.grad is kept and torch.equal(got['x.weight.grad'], start['x'][0])
+    assert_same(got, want, 'head with a frozen x conv', skip=('x.weight.grad',))
+
+
+class CountPacks:
+    """the engine's library with vfs_pack_weights launches counted"""
+
+    def __init__(self, lib):
+        self._lib, self.packs = lib, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != 'pack_weights':
+            return fn
+
+        def counted(*args):
+            self.packs += 1
+            return fn(*args)
+        return counted
+
+
+def test_head_packs_once_per_epoch(backend):
+    """one pack launch per conv and parameter epoch; one more, once, when the first backward asks for the dgrad packing"""
+    from vfs_amd.engine import bump_params_epoch
+    (z, x, labels, weights, start), _ = head_reference(backend, 64, 64, 'focal')
+    head = head_module(backend, 64, 64, weights, start)
+    zf, xf = (t.float().permute(0, 3, 1, 2).to(backend.dev) for t in (z, x))
+    lib = backend.eng.lib
+    backend.eng.lib = count = CountPacks(lib)
+    try:
+        with torch.no_grad():
+            head(zf, xf)
+            head(zf, xf)
+        head_engine(backend, head, z, x, labels, 'focal')
+        assert 2 <= count.packs <= 4, count.packs      # two convs: wf each, and at most one repack each for wd
+        seen = count.packs
+        with torch.no_grad():
+            head(zf, xf)
+        head_engine(backend, head, z, x, labels, 'focal')
+        assert count.packs == seen, 'a repack within one parameter epoch'
+        bump_params_epoch()
+        with torch.no_grad():
+            head(zf, xf)
+        head_engine(backend, head, z, x, labels, 'focal')
+        assert count.packs == seen + 2, 'not exactly one pack launch per conv after the epoch moved'
+    finally:
+        backend.eng.lib = lib
+
+
+@pytest.mark.parametrize('name', ['Adam', 'ParamSGD'])
+def test_probe_optimizer_state(backend, name):
+    """two steps on two tensors: state_dict keys and values, and the parameters, equal a loop of adam_step / sgd_step launches"""
+    from vfs_amd import siamfc as SF
+    from vfs_amd.engine import params_epoch
+    g = seed(37)
+    dev, lib = backend.dev, backend.hostlib
+    init = [torch.randn(5, 3, generator=g), torch.randn(7, generator=g)]
+    grads = [[torch.randn(p.shape, generator=g) for p in init] for _ in range(2)]
+    params = [torch.nn.Parameter(p.clone().to(dev)) for p in init]
+    if name == 'Adam':
+        hyper = dict(lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1)
+        want_state = [dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p)) for p in init]
+    else:
+        hyper = dict(lr=0.1, momentum=0.9, weight_decay=5e-4)
+        want_state = [dict(momentum_buffer=torch.zeros_like(p)) for p in init]
+    opt = getattr(SF, name)(params, **hyper)
+    want = [p.clone() for p in init]
+    epoch = params_epoch()
+    for step in range(2):
+        for p, gr in zip(params, grads[step]):
+            p.grad = gr.clone().to(dev)
+        opt.step()
+        for p, gr, st in zip(want, grads[step], want_state):
+            if name == 'Adam':
+                st['step'] += 1
+                lib.adam_step(p, gr, st['exp_avg'], st['exp_avg_sq'], p.numel(), hyper['lr'], *hyper['betas'], hyper['eps'],
+                              hyper['weight_decay'], st['step'], None)
+            else:
+                lib.sgd_step(p, gr, st['momentum_buffer'], p.numel(), hyper['lr'], hyper['momentum'], hyper['weight_decay'], None, None)
+    assert params_epoch() == epoch + 2      # every step tells the caches of derived weights
+    sd = opt.state_dict()
+    assert sorted(sd) == ['param_groups', 'state'] and sorted(sd['state']) == [0, 1]
+    assert len(sd['param_groups']) == 1 and sd['param_groups'][0]['params'] == [0, 1]
+    assert {k: sd['param_groups'][0][k] for k in hyper} == hyper
+    for i, st in enumerate(want_state):
+        assert list(sd['state'][i]) == list(st)
+        for k, v in st.items():
+            got = sd['state'][i][k]
+            assert (got == v) if k == 'step' else torch.equal(got.cpu(), v), (i, k)
+        assert torch.equal(params[i].detach().cpu(), want[i]), i

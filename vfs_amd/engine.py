@@ -715,6 +715,9 @@ class Engine:
                                Wo, u.cout, u.k, u.k, u.stride, u.pad, nsplit, pps, ss)
                 if u.bias is not None and u.bias.requires_grad:
                     lib.bias_grad(dx, u.bias.grad, M, u.cout, ss)
+        elif u.bias is not None and u.bias.requires_grad:      # a trainable bias under a frozen weight (the SiamFC head allows it)
+            with self.on_side_stream(dev):
+                lib.bias_grad(dx, u.bias.grad, M, u.cout, self.stream(dev))
         if not need_dgrad:
             return None, None
         gin = g_out if g_out is not None else self.buf(f'{u.name}{tag}.gin', (N, H, W, u.cin), BF16, dev)

@@ -3,9 +3,9 @@ tracking logic of `TrackerSiamFC` (projects/siamfc-pytorch/siamfc/siamfc_tracker
 its third-party scaffolding (got10k's Tracker base / dataset classes, cv2, torchvision).
 
   train_step   (:364-387)  frozen dilated backbone (eval) -> 1x1 convs -> cross-correlation -> Balanced / Focal loss ->
-                           backward through the head (vfs_xcorr_bwd, vfs_conv_wgrad, vfs_bias_grad) -> Adam / SGD
+                           backward through the head (vfs_xcorr_bwd, Engine.conv_bwd of the 1x1 convs) -> Adam / SGD
                            frozen_stages < 4 (:131-144, the optimizer holds the backbone too): both branches through the bf16
-                           training path, the backward continues through vfs_conv_dgrad of the 1x1 convs into
+                           training path, the backward continues through the 1x1 convs' input gradients into
                            ResNet.backward_nhwc (dilated layers: vfs_conv_dgrad_dilated / vfs_conv_wgrad_dilated)
   _create_labels (:456-500), current_lr (:349-362), the optimizer / scheduler choices of __init__ (:131-166)
   init / update / track (:199-347): the tracking loop.  Crops and the response up-sampling are cv2 calls in the reference
@@ -16,10 +16,8 @@ its third-party scaffolding (got10k's Tracker base / dataset classes, cv2, torch
 Only num_convs=1, kernel_size=1 heads train here (what the probe's config builds, default_config_base.py:33-37)."""
 import numpy as np
 import torch
-import torch.nn as nn
 
 from .engine import BF16, bump_params_epoch, shared_engine
-from .packing import wgrad_splits
 from .siamfc_heads import SiamConvFC, SiamFC, _nhwc_bf16
 
 DEFAULT_CFG = dict(      # default_config_base.py:2-51
@@ -32,11 +30,8 @@ MEAN = (123.675, 116.28, 103.53)
 STD = (58.395, 57.12, 57.375)
 
 
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam (amsgrad off) through vfs_adam_step, one launch per parameter tensor (the probe has four)"""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _PerTensorOptimizer(torch.optim.Optimizer):
+    """one launch per parameter tensor (the frozen probe has four); subclasses name their state and launch their kernel"""
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -48,33 +43,44 @@ class Adam(torch.optim.Optimizer):
                     continue
                 st = self.state[p]
                 if not st:
-                    st['step'] = 0
-                    st['exp_avg'], st['exp_avg_sq'] = torch.zeros_like(p), torch.zeros_like(p)
-                st['step'] += 1
-                eng.lib.adam_step(p.data, p.grad, st['exp_avg'], st['exp_avg_sq'], p.numel(), float(grp['lr']), float(grp['betas'][0]),
-                                  float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']), int(st['step']),
-                                  eng.stream(p.device))
+                    st.update(self._new_state(p))
+                self._launch(eng.lib, grp, p, st, eng.stream(p.device))
 
 
-class ParamSGD(torch.optim.Optimizer):
-    """torch.optim.SGD (momentum, weight decay) through vfs_sgd_step, one launch per parameter tensor"""
+class Adam(_PerTensorOptimizer):
+    """torch.optim.Adam (amsgrad off) through vfs_adam_step"""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _new_state(self, p):
+        return dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
+
+    def _launch(self, lib, grp, p, st, s):
+        st['step'] += 1
+        lib.adam_step(p.data, p.grad, st['exp_avg'], st['exp_avg_sq'], p.numel(), float(grp['lr']), float(grp['betas'][0]),
+                      float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']), int(st['step']), s)
+
+
+class ParamSGD(_PerTensorOptimizer):
+    """torch.optim.SGD (momentum, weight decay) through vfs_sgd_step"""
 
     def __init__(self, params, lr=1e-2, momentum=0.9, weight_decay=0):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        eng = shared_engine()
-        bump_params_epoch()      # raw-pointer update: packed / folded copies of the parameters must refresh
-        for grp in self.param_groups:
-            for p in grp['params']:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if 'momentum_buffer' not in st:
-                    st['momentum_buffer'] = torch.zeros_like(p)
-                eng.lib.sgd_step(p.data, p.grad, st['momentum_buffer'], p.numel(), float(grp['lr']), float(grp['momentum']),
-                                 float(grp['weight_decay']), None, eng.stream(p.device))
+    def _new_state(self, p):
+        return dict(momentum_buffer=torch.zeros_like(p))
+
+    def _launch(self, lib, grp, p, st, s):
+        lib.sgd_step(p.data, p.grad, st['momentum_buffer'], p.numel(), float(grp['lr']), float(grp['momentum']),
+                     float(grp['weight_decay']), None, s)
+
+
+def _ensure_grads(params):
+    """a zero .grad for every trainable parameter that has none: the backward kernels accumulate into it through its pointer"""
+    for p in params:
+        if p.requires_grad and p.grad is None:
+            p.grad = torch.zeros_like(p)
 
 
 def create_labels(size, r_pos, r_neg, total_stride, device):
@@ -94,9 +100,10 @@ def head_loss_backward(head, zf, xf, labels, loss='focal', param=None, backward=
 
 
 def head_loss_backward_nhwc(head, z, x, labels, loss='focal', param=None, backward=True, feat_grads=False):
-    """head_loss_backward on NHWC bf16 features (what the backbone's training path hands over).  feat_grads (fine-tuning,
-    siamfc_tracker_base.py:131-144: the optimizer holds the backbone too): also the gradients wrt z and x, bf16 NHWC - through
-    vfs_xcorr_bwd and, for SiamConvFC, vfs_conv_dgrad of the two 1x1 convs.  -> (loss tensor [1], responses, dz, dx)"""
+    """head_loss_backward on NHWC bf16 features (what the backbone's training path hands over); SiamConvFC's 1x1 convs go back
+    through Engine.conv_bwd (weight / bias gradients on the side stream, joined before the return).  feat_grads (fine-tuning,
+    siamfc_tracker_base.py:131-144: the optimizer holds the backbone too): also the gradients wrt z and x, bf16 NHWC - for
+    SiamConvFC ENGINE BUFFERS (<unit name>.gin), valid until the next call.  -> (loss tensor [1], responses, dz, dx)"""
     eng = shared_engine(x.device)
     dev = x.device
     s = eng.stream(dev)
@@ -106,7 +113,7 @@ def head_loss_backward_nhwc(head, z, x, labels, loss='focal', param=None, backwa
     convs = isinstance(head, SiamConvFC)
     if convs and (len(head.z_convs) != 1):
         raise NotImplementedError('probe training: num_convs=1 heads (siamfc_tracker_base.py:108-113)')
-    zc, xc = (head._conv1x1(head.z_convs[0], z), head._conv1x1(head.x_convs[0], x)) if convs else (z, x)
+    zc, xc = (head._conv1x1(head.z_units[0], z), head._conv1x1(head.x_units[0], x)) if convs else (z, x)
     nz, hz, wz, c = zc.shape
     nx, h, w, _ = xc.shape
     ho, wo = h - hz + 1, w - wz + 1
@@ -120,30 +127,17 @@ def head_loss_backward_nhwc(head, z, x, labels, loss='focal', param=None, backwa
     eng.lib.siamfc_loss(resp, labels.contiguous(), out, g, resp.numel(), mode, float(param), 1.0, s)
     dz = dx = None
     if backward and (convs or feat_grads):
-        dzc, dxc = torch.empty_like(zc), torch.empty_like(xc)
-        eng.lib.xcorr_bwd(zc, xc, g, dzc, dxc, nz, nx, hz, wz, h, w, c, float(head.out_scale), s)
-        if feat_grads and not convs:
-            dz, dx = dzc, dxc
+        dz, dx = torch.empty_like(zc), torch.empty_like(xc)
+        eng.lib.xcorr_bwd(zc, xc, g, dz, dx, nz, nx, hz, wz, h, w, c, float(head.out_scale), s)
     if backward and convs:
-        for conv, feat, d in ((head.z_convs[0], z, dzc), (head.x_convs[0], x, dxc)):
-            n_, hh, ww, cin = feat.shape
-            M, cout = n_ * hh * ww, conv.out_channels
-            nsplit, pps = wgrad_splits(M, cout, cin)
-            partial = eng.ws('ws.wgrad', nsplit * cout * cin, torch.float32, dev)
-            if conv.weight.grad is None:
-                conv.weight.grad = torch.zeros_like(conv.weight)
-            eng.lib.conv_wgrad(d, feat, partial, conv.weight.grad, n_, hh, ww, cin, hh, ww, cout, 1, 1, 1, 0, nsplit, pps, s)
-            if conv.bias is not None:
-                if conv.bias.grad is None:
-                    conv.bias.grad = torch.zeros_like(conv.bias)
-                eng.lib.bias_grad(d, conv.bias.grad, M, cout, s)
-            if feat_grads:
-                gf = torch.empty_like(feat)
-                eng.lib.conv_dgrad(d, head._packed_wd(conv), gf, None, n_, hh, ww, cin, hh, ww, cout, 1, 1, 1, 0, s)
-                if feat is z:
-                    dz = gf
-                else:
-                    dx = gf
+        _ensure_grads(head.parameters())
+        gins = []
+        for u, feat, d in ((head.z_units[0], z, dz), (head.x_units[0], x, dx)):
+            n_, hh, ww, _ = feat.shape
+            head._pack(u, need_wd=feat_grads)
+            gins.append(eng.conv_bwd(u, d, feat, n_, hh, ww, hh, ww, need_dgrad=feat_grads)[0])
+        dz, dx = gins
+        eng.wgrad_join(dev)      # callers step an optimizer right after
     return out, resp, dz, dx
 
 
@@ -209,6 +203,11 @@ class SiamFCProbe:
     def current_lr(self):
         return [g['lr'] for g in self.optimizer.param_groups]
 
+    def _zero_grads(self):
+        """every optimizer parameter gets a zeroed .grad: the backward kernels accumulate into it"""
+        self.optimizer.zero_grad(set_to_none=False)
+        _ensure_grads(p for grp in self.optimizer.param_groups for p in grp['params'])
+
     def train_step(self, batch, backward=True):
         """batch = (z [N,3,ez,ez], x [N,3,ix,ix]) uint8-range RGB floats, as the reference's Pair dataset yields them"""
         if self.finetune and backward and self.optimizer is not None:
@@ -218,10 +217,7 @@ class SiamFCProbe:
         nx, _, h, w = xf.shape
         labels = self._create_labels((nx, 1, h - hz + 1, w - wz + 1))
         if backward and self.optimizer is not None:
-            self.optimizer.zero_grad(set_to_none=False)
-            for p in self.head.parameters():
-                if p.grad is None:
-                    p.grad = torch.zeros_like(p)
+            self._zero_grads()
         loss, _ = head_loss_backward(self.head, zf, xf, labels, self.cfg['loss'], backward=backward and self.optimizer is not None)
         if backward and self.optimizer is not None:
             self.optimizer.step()
@@ -258,11 +254,7 @@ class SiamFCProbe:
                 ctxs.append(ctx)
             z, x = feats
             labels = self._create_labels((x.shape[0], 1, x.shape[1] - z.shape[1] + 1, x.shape[2] - z.shape[2] + 1))
-            self.optimizer.zero_grad(set_to_none=False)
-            for grp in self.optimizer.param_groups:
-                for p in grp['params']:
-                    if p.grad is None:
-                        p.grad = torch.zeros_like(p)
+            self._zero_grads()
             loss, _, dz, dx = head_loss_backward_nhwc(self.head, z, x, labels, self.cfg['loss'], backward=True, feat_grads=True)
             if 'x' in branches:
                 bb.backward_nhwc(eng, ctxs[1], {stage: dx})
