@@ -95,6 +95,19 @@ int vfs_conv_dgrad_bn_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* 
                               const vfs_bf16* bn_x, const vfs_bf16* bn_y, const float* bnp, float* bn_partial,
                               int bn_mpg, int bn_relu, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH,
                               int KW, int stride, int pad, vfs_stream_t stream);
+/* dgrad of a 1x1 / stride-2 / pad-0 convolution (the downsample branch of a stage entry, resnet.py:267-277) without the zero planes:
+ * such a convolution reads only the pixels with even h and even w, so three quarters of its input gradient are exactly zero and the
+ * rest is the pure GEMM dy[N*Ho*Wo, Cout] x wd over the quarter grid, Ho = ceil(H / 2), Wo = ceil(W / 2); wd = [Cin][1][1][Cout].
+ *   compact = 0: dx and add are DENSE [N,H,W,Cin] tensors of which only the pixels (n, 2 ho, 2 wo) are read and written:
+ *                dx = dgrad + add there, every other pixel of dx keeps what it holds.  With add == dx (the residual branch's
+ *                gradient, completed in place) the result equals vfs_conv_dgrad(..., stride 2) with the same add, bit for bit
+ *                where the launch lands in a kernel of the same summation order.
+ *   compact = 1: dx and add are contiguous [N,Ho,Wo,Cin] tensors, dx = dgrad (+ add).
+ * add may be NULL.  The launch runs on the kernels of a 1x1 / stride-1 dgrad of the same pixel count (vfs_conv_dgrad_ds_plan:
+ * wide = 128-channel tiles, ring = the LDS-DMA ring); Cin % 8 == 0, Cout % 64 == 0.  No mask-gated add, no statistics rows. */
+int vfs_conv_dgrad_ds(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int compact, int N, int H, int W,
+                      int Cin, int Ho, int Wo, int Cout, vfs_stream_t stream);
+int vfs_conv_dgrad_ds_plan(int compact, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int* wide, int* ring);
 /* Split-K variants for problems with few output pixels and a long reduction - the SimSiam head's Linear
  * layers (sim_siam_head.py:78-111: 2048x2048 on 64 rows fill 16 workgroups otherwise): the K loop is cut into
  * ksplit slices that run as separate workgroups; the last slice to finish adds the fp32 partial tiles in

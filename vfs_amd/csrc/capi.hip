@@ -300,6 +300,12 @@ int vfs_stem_fwd(const vfs_bf16* x4, const vfs_bf16* wf, vfs_bf16* y, float* sta
 
 int vfs_conv_dgrad_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, const uint8_t* add_mask, int N,
                            int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, vfs_stream_t stream) {
+  // the downsample branch of a stage entry: a 1x1 / stride-2 / pad-0 dgrad that completes the residual branch's gradient IN PLACE.
+  // Three of its four parity classes have no tap - their workgroups would copy `add` to itself - so only the quarter grid runs
+  // (vfs_conv_dgrad_ds); every pixel of dx ends with the value the four classes would leave.
+  if (vfs_option_igemm_ds_quarter && KH == 1 && KW == 1 && stride == 2 && pad == 0 && add && add == dx && !add_mask && H >= 1 && W >= 1 &&
+      Ho == (H + 1) / 2 && Wo == (W + 1) / 2)
+    return vfs_conv_dgrad_ds(dy, wd, dx, add, 0, N, H, W, Cin, Ho, Wo, Cout, stream);
   ConvArgs a = conv_dgrad_args(dy, wd, dx, add, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
   if (int rc = set_add_mask(a, add, add_mask, N, H, W, Cin)) return rc;
   return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
@@ -307,6 +313,31 @@ int vfs_conv_dgrad_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx,
 int vfs_conv_dgrad(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int N, int H, int W, int Cin,
                    int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, vfs_stream_t stream) {
   return vfs_conv_dgrad_maskadd(dy, wd, dx, add, nullptr, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, stream);
+}
+// dgrad of a 1x1 / stride-2 / pad-0 convolution on the quarter grid: a 1x1 / stride-1 dgrad over the Ho x Wo pixels of dy, whose
+// output rows are the compact tensor's (compact) or the even-even pixels of the dense one (a.out_H, a.out_W: GATHER_DGRADQ)
+static int conv_dgrad_ds_args(ConvArgs& a, const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int compact, int N,
+                              int H, int W, int Cin, int Ho, int Wo, int Cout) {
+  if (N < 1 || H < 1 || W < 1 || Ho != (H + 1) / 2 || Wo != (W + 1) / 2)
+    return vfs_set_error(VFS_ERR_SHAPE, "conv_dgrad_ds: Ho = ceil(H / 2), Wo = ceil(W / 2) of a 1x1 / stride-2 / pad-0 convolution");
+  a = conv_dgrad_args(dy, wd, dx, add, N, Ho, Wo, Cin, Ho, Wo, Cout, 1, 1, 1, 0);
+  if (!compact) { a.out_H = H; a.out_W = W; }
+  return VFS_OK;
+}
+int vfs_conv_dgrad_ds(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, int compact, int N, int H, int W,
+                      int Cin, int Ho, int Wo, int Cout, vfs_stream_t stream) {
+  if (!dy || !wd || !dx) return vfs_set_error(VFS_ERR_ARG, "conv_dgrad_ds: null operand");
+  ConvArgs a{};
+  if (int rc = conv_dgrad_ds_args(a, dy, wd, dx, add, compact, N, H, W, Cin, Ho, Wo, Cout)) return rc;
+  return vfs_conv_igemm_dispatch(a, GATHER_DGRAD, stream_of(stream));
+}
+int vfs_conv_dgrad_ds_plan(int compact, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int* wide, int* ring) {
+  if (!wide || !ring) return vfs_set_error(VFS_ERR_ARG, "conv_dgrad_ds_plan: bad argument");
+  ConvArgs a{};
+  if (int rc = conv_dgrad_ds_args(a, nullptr, nullptr, nullptr, nullptr, compact, N, H, W, Cin, Ho, Wo, Cout)) return rc;
+  const IgemmTiling tl = vfs_conv_igemm_tiling(a, GATHER_DGRAD);
+  *wide = tl.wide; *ring = tl.ring;
+  return VFS_OK;
 }
 int vfs_conv_dgrad_bn_maskadd(const vfs_bf16* dy, const vfs_bf16* wd, vfs_bf16* dx, const vfs_bf16* add, const uint8_t* add_mask,
                               const vfs_bf16* bn_x, const vfs_bf16* bn_y, const float* bnp, float* bn_partial, int bn_mpg, int bn_relu,

@@ -20,6 +20,8 @@
 //   * stride-2 dgrad runs per OUTPUT PARITY CLASS (blockIdx.y = (h&1, w&1)): a class only sees the
 //     taps r = (h+pad) mod 2, s = (w+pad) mod 2 (1, 2, 2 or 4 of the 9 taps of a 3x3), so no MFMA
 //     multiplies the zeros a gather over the dilated gradient would insert
+//   * the dgrad of a 1x1 / stride-2 / pad-0 convolution (ResNet's downsample) has ONE class with a tap: it runs as the pure GEMM
+//     over the quarter grid (GATHER_DGRADQ) and its epilogue adds into the even-even pixels of the dense gradient, in place
 //   * epilogue: lane holds 4 consecutive channels of one pixel -> one 8-byte NHWC store;
 //     optional per-channel (sum, sum of squares) of the bf16-ROUNDED outputs, reduced
 //     wave-wide with shuffles and written as one deterministic partial per pixel-block
@@ -109,8 +111,9 @@ __global__ __launch_bounds__(256, PIPE >= 3 ? (BC == 64 ? 2 : 1) : (PIPE == 1 ? 
   // no (n, h, w) decomposition (two integer divisions per row), no tap loop.  SQ counters of the 64 -> 256 layer: 563 of the
   // 1055 VALU and ~all 550 SALU instructions a wave executed were this prologue, and the kernel is instruction-issue bound
   // (3 workgroups per CU: VALU busy 78 %, not HBM: 3.4 TB/s).
-  const bool pure = (MODE == GATHER_FWD || MODE == GATHER_DGRAD) && g.KH * g.KW == 1 && g.stride == 1 && g.pad == 0 &&
-                    g.H == g.Ho && g.W == g.Wo;
+  // GATHER_DGRADQ (the quarter grid of a 1x1 / stride-2 dgrad) is a pure GEMM by construction: only its epilogue knows the dense grid.
+  const bool pure = MODE == GATHER_DGRADQ || ((MODE == GATHER_FWD || MODE == GATHER_DGRAD) && g.KH * g.KW == 1 && g.stride == 1 &&
+                                              g.pad == 0 && g.H == g.Ho && g.W == g.Wo);
   // descriptor of destination pixel m, 16-byte chunk jc of its gathered rows: byte offset base (mod 2^32) + tap validity bits
   auto row_desc = [&](int m, int jc, unsigned& xb, unsigned& xm) {
     unsigned mask = 0;
@@ -428,7 +431,7 @@ static int launch_igemm(const ConvArgs& a, hipStream_t stream) {
   int ncb = (a.Cout + BC - 1) / BC;
   int ks = 1;
   if (a.ksplit > 1) {
-    if (MODE == GATHER_DGRAD2 || MODE == GATHER_STEM || !a.ks_ws || npb * ncb > KS_TICKETS)
+    if (MODE == GATHER_DGRAD2 || MODE == GATHER_DGRADQ || MODE == GATHER_STEM || !a.ks_ws || npb * ncb > KS_TICKETS)
       return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: split-K needs a stride-1 problem with at most 1024 tiles and a workspace");
     ks = a.ksplit;
   }
@@ -439,6 +442,20 @@ static int launch_igemm(const ConvArgs& a, hipStream_t stream) {
 // statistics rows of a launch of this kernel family (conv_pw.hip shares the epilogue): one per 128-pixel block `pb` of the
 // destination grid, in pixel order (vfs_igemm_epi.h)
 int vfs_conv_igemm_stats_rows(const ConvArgs& a) { return (a.g.M + 127) / 128; }
+
+// 128-channel tiles, unless that leaves the chip under-filled (deep stages: 16x16 / 8x8 maps, the head): with fewer than
+// igemm_narrow_below tiles the 64-channel tile doubles the workgroups - two latency-bound K chains per CU instead of one.
+// DMA ring: pure GEMM (1x1, stride 1, no padding), at least 4 K-steps, at most vfs_option_igemm_ring_tiles tiles
+IgemmTiling vfs_conv_igemm_tiling(const ConvArgs& a, int mode) {
+  const long long tiles128 = (long long)((a.g.M + 127) / 128) * ((a.Cout + 127) / 128);
+  const bool wide = (a.Cout % 128 == 0) && vfs_option_igemm_bc != 64 && tiles128 >= vfs_option_igemm_narrow_below;
+  const int bc = wide ? 128 : 64;
+  const long long tiles = (long long)((a.g.M + 127) / 128) * ((a.Cout + bc - 1) / bc);
+  const bool ring = vfs_option_igemm_ring_tiles > 0 && a.g.KH * a.g.KW == 1 && a.g.stride == 1 && a.g.pad == 0 &&
+                    a.g.Ktot >= 256 && tiles <= vfs_option_igemm_ring_tiles && (!a.bn.partial || vfs_option_igemm_ring_fbn) &&
+                    (mode == GATHER_FWD || mode == GATHER_DGRAD) && !a.in_bnp;      // (the DMA ring cannot transform what it moves)
+  return {wide, ring};
+}
 
 int vfs_conv_igemm_dispatch(const ConvArgs& a_in, int mode, hipStream_t stream) {
   ConvArgs a = a_in;
@@ -456,20 +473,24 @@ int vfs_conv_igemm_dispatch(const ConvArgs& a_in, int mode, hipStream_t stream) 
   if (a.in_bnp && !(mode == GATHER_FWD && a.g.KH * a.g.KW == 1 && a.g.stride == 1 && a.g.pad == 0 && a.g.H == a.g.Ho && a.g.W == a.g.Wo &&
                     a.in_npg > 0 && ((long long)a.in_npg * a.g.H * a.g.W) % 128 == 0 && a.ksplit <= 1))
     return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: the input BatchNorm folds into the 1x1 / stride-1 forward only, groups of whole 128-pixel tiles");
-  if (!a.in_bnp && vfs_conv_skinny_eligible(a, mode)) return vfs_conv_skinny_dispatch(a, stream);   // at most 128 rows (conv_pw.hip)
-  if (!a.in_bnp && vfs_conv_pw_eligible(a, mode)) return vfs_conv_pw_dispatch(a, mode, stream);   // persistent kernel (conv_pw.hip)
-  // 128-channel tiles, unless that leaves the chip under-filled (deep stages: 16x16 / 8x8 maps, the head): with fewer than
-  // igemm_narrow_below tiles the 64-channel tile doubles the workgroups - two latency-bound K chains per CU instead of one
-  const long long tiles128 = (long long)((a.g.M + 127) / 128) * ((a.Cout + 127) / 128);
-  const bool wide = (a.Cout % 128 == 0) && vfs_option_igemm_bc != 64 && tiles128 >= vfs_option_igemm_narrow_below;
+  if (!a.in_bnp && a.out_H == 0 && vfs_conv_skinny_eligible(a, mode)) return vfs_conv_skinny_dispatch(a, stream);   // at most 128 rows (conv_pw.hip)
+  if (!a.in_bnp && a.out_H == 0 && vfs_conv_pw_eligible(a, mode)) return vfs_conv_pw_dispatch(a, mode, stream);   // persistent kernel (conv_pw.hip)
+  const IgemmTiling tl = vfs_conv_igemm_tiling(a, mode);
+  const bool wide = tl.wide, ring = tl.ring;
   const bool onek = vfs_option_igemm_onek >= 3 || (vfs_option_igemm_onek == 2 && a.g.KH * a.g.KW == 1) ||
                     (vfs_option_igemm_onek == 1 && a.g.Ktot == 64);
-  // DMA ring: pure GEMM (1x1, stride 1, no padding), at least 4 K-steps, at most vfs_option_igemm_ring_tiles tiles
   const int bc = wide ? 128 : 64;
-  const long long tiles = (long long)((a.g.M + 127) / 128) * ((a.Cout + bc - 1) / bc);
-  const bool ring = vfs_option_igemm_ring_tiles > 0 && a.g.KH * a.g.KW == 1 && a.g.stride == 1 && a.g.pad == 0 &&
-                    a.g.Ktot >= 256 && tiles <= vfs_option_igemm_ring_tiles && (!a.bn.partial || vfs_option_igemm_ring_fbn) &&
-                    (mode == GATHER_FWD || mode == GATHER_DGRAD) && !a.in_bnp;      // (the DMA ring cannot transform what it moves)
+  // the quarter grid of a 1x1 / stride-2 dgrad (a.out_H > 0: vfs_conv_dgrad_ds): the pure-GEMM instances of a stride-1 1x1 dgrad of
+  // the same M, K, Cout - DMA ring or register pipeline, as the tiling says - with the scattering epilogue
+  if (a.out_H > 0) {
+    if (mode != GATHER_DGRAD || a.g.KH * a.g.KW != 1 || a.g.stride != 1 || a.g.pad != 0 || a.g.H != a.g.Ho || a.g.W != a.g.Wo ||
+        a.bn.partial || a.add_mask || a.ksplit > 1 || 2 * (a.g.Ho - 1) >= a.out_H || 2 * (a.g.Wo - 1) >= a.out_W)
+      return vfs_set_error(VFS_ERR_SHAPE, "conv_igemm: the quarter-grid scatter takes a plain 1x1 dgrad whose even-even pixels lie inside the dense tensor");
+    if (ring && vfs_option_igemm_ring_mfma32) return wide ? launch_igemm<128, GATHER_DGRADQ, 5>(a, stream) : launch_igemm<64, GATHER_DGRADQ, 5>(a, stream);
+    if (ring) return wide ? launch_igemm<128, GATHER_DGRADQ, 3>(a, stream) : launch_igemm<64, GATHER_DGRADQ, 3>(a, stream);
+    if (onek) return wide ? launch_igemm<128, GATHER_DGRADQ, 1>(a, stream) : launch_igemm<64, GATHER_DGRADQ, 1>(a, stream);
+    return wide ? launch_igemm<128, GATHER_DGRADQ>(a, stream) : launch_igemm<64, GATHER_DGRADQ>(a, stream);
+  }
   if (ring && vfs_option_igemm_ring_upfront && !a.bn.partial) {
     if (mode == GATHER_FWD) return wide ? launch_igemm<128, GATHER_FWD, 4>(a, stream) : launch_igemm<64, GATHER_FWD, 4>(a, stream);
     return wide ? launch_igemm<128, GATHER_DGRAD, 4>(a, stream) : launch_igemm<64, GATHER_DGRAD, 4>(a, stream);

@@ -15,7 +15,10 @@
 #pragma once
 #include "vfs_common.h"
 
-enum { GATHER_FWD = 0, GATHER_DGRAD = 1, GATHER_STEM = 2, GATHER_DGRAD2 = 3 };
+// GATHER_DGRADQ: the dgrad of a 1x1 / stride-2 / pad-0 convolution as the pure GEMM it is on the quarter grid - pixel (n, hc, wc) of
+// dy [N,Ho,Wo,Cout] is the only source of pixel (n, 2 hc, 2 wc) of dx - whose epilogue reads `add` and writes `out` at that pixel of
+// the dense [N, out_H, out_W, Cin] tensor; the other three quarters of dx receive nothing from the convolution and are not touched
+enum { GATHER_FWD = 0, GATHER_DGRAD = 1, GATHER_STEM = 2, GATHER_DGRAD2 = 3, GATHER_DGRADQ = 4 };
 
 struct ConvGeom {
   int N, H, W, C;   // gather-source tensor (NHWC), C = physical channels per pixel
@@ -76,6 +79,9 @@ struct ConvArgs {
   int coarse_log2 = 0;
   int mfma_stats = 0;    // implicit-GEMM kernel: forward statistics rows by MFMA from the staged bf16 tile (set by the dispatcher)
   int xcd_swizzle = 0;   // implicit-GEMM kernel: XCD-aware logical tile order (set by the dispatcher)
+  // quarter-grid scatter (GATHER_DGRADQ; 0: off): GEMM pixel (n, hc, wc) of the g.Ho x g.Wo grid reads `add` and writes `out` at row
+  // (n * out_H + 2 hc) * out_W + 2 wc of a [N, out_H, out_W, Cout] tensor (2 (g.Ho - 1) < out_H, 2 (g.Wo - 1) < out_W)
+  int out_H = 0, out_W = 0;
 };
 #define KS_TICKETS 1024
 
@@ -110,6 +116,10 @@ __device__ __forceinline__ u32x4 bn_relu_vec(u32x4 v, const f32x4& sc0, const f3
 }
 
 int vfs_conv_igemm_dispatch(const ConvArgs& a, int mode, hipStream_t stream);
+// the tile width (128 or 64 channels) the implicit-GEMM dispatcher gives a launch, and whether its pure-GEMM LDS-DMA ring takes it
+// (host only; the dispatcher asks the same function)
+struct IgemmTiling { bool wide, ring; };
+IgemmTiling vfs_conv_igemm_tiling(const ConvArgs& a, int mode);
 
 // Tail of a forward epilogue with coarse statistics rows: this workgroup has WRITTEN its fine rows (agent-scope stores, channels
 // [c0, c0 + nch)); it takes a ticket of its group, and the last of the group's `arrivals` workgroups adds the group's fine rows

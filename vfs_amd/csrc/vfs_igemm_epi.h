@@ -50,11 +50,12 @@ __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const int m0, 
   const bool mstats = do_stats && !do_add && !do_bias && a.mfma_stats;   // uniform
   bf16_t* slab = smem + wave * (64 * SROW);
   auto pixel_dst = [&](int m) -> size_t {         // class-local pixel -> row of the output matrix
-    if (MODE != GATHER_DGRAD2) return (size_t)m;
+    if (MODE != GATHER_DGRAD2 && MODE != GATHER_DGRADQ) return (size_t)m;
     const int hw = Hc * Wc;
     const int n = m / hw;
     const int rem = m - n * hw;
     const int hc = rem / Wc, wcx = rem - hc * Wc;
+    if (MODE == GATHER_DGRADQ) return ((size_t)n * a.out_H + 2 * hc) * a.out_W + 2 * wcx;      // the even-even pixels of the dense tensor
     return ((size_t)n * g.Ho + (2 * hc + ph)) * g.Wo + (2 * wcx + pw);
   };
   float s1[TM][4], s2[TM][4];

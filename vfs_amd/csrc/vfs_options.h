@@ -28,7 +28,8 @@
   X(igemm_ring_mfma32, 1)     /* the pure-GEMM DMA ring on 32x32x16 MFMAs with the lean DMA issue (PIPE 5; 0: PIPE 3, A/B knob) */  \
   X(igemm_ring_gather, 0)     /* DMA ring for GATHERED problems (3x3 / strided forward, stride-1 and stride-2 dgrad classes) with at most this many tiles (0: off; measured) */ \
   X(igemm_ring_upfront, 0)    /* ring variant: all fragment reads of a K-step before its MFMAs (measured, no gain) */               \
-  X(igemm_skinny, 1)          /* skinny GEMM for <= 128-row problems: the head's Linear layers (A/B knob) */                        \
+  X(igemm_ds_quarter, 1)      /* 1x1 / stride-2 / pad-0 dgrad that completes the residual gradient in place (add == dx: the downsample branch of a stage entry): pure GEMM over the quarter grid, no zero planes written or read back (A/B knob; 0: the four parity classes) - same bits */ \
+  X(igemm_skinny, 1)         /* skinny GEMM for <= 128-row problems: the head's Linear layers (A/B knob) */                        \
   X(igemm_pw, 0)              /* persistent 1x1 kernel.  0: off (measured slower than the one-tile kernels, MEASUREMENTS.md round 5); 1: where its plan says so; 2: every eligible 1x1 */ \
   X(igemm_pw_min_tiles, 192)  /* igemm_pw = 1: fewer 128-pixel tiles than this leave CUs idle, the split-channel kernels take over */ \
   /* ---- weight gradient (conv_wgrad.hip, conv_wgrad_halo.hip) */                                                                  \
