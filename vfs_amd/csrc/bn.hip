@@ -9,6 +9,10 @@
 //
 // bnp layout (per layer): float[G][4][C] = {scale = gamma*invstd, shift = beta - mean*scale,
 //                                           mean, invstd}
+// The arithmetic itself (statistics -> coefficients, masked gradient, S1 / S2, dx coefficients) is in vfs_bn.h: this file holds the
+// data movement around it.
+#include <type_traits>
+#include "vfs_bn.h"
 #include "vfs_ops.h"
 #include "vfs_p2p.h"
 #include "vfs_stem.h"
@@ -34,12 +38,25 @@ __device__ __forceinline__ void bn_store_sum(const P2PTail& x, double* p, double
 }
 
 // ------------------------------------------------------------------------------------------
+// The column reductions: 256 threads = 32 channels (cl = t & 31) x 8 row lanes (sl = t >> 5).  Every lane sums its rows in
+// double, the eight lanes of a channel are added in lane order through LDS: every thread calls this with its partial sums, the
+// threads of row lane 0 return with the column sums.  (A caller that loops puts a barrier in front: sh is re-used.)
+__device__ __forceinline__ void bn_cols_reduce(double (*sh)[2][32], double& a0, double& a1) {
+  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  sh[sl][0][cl] = a0;
+  sh[sl][1][cl] = a1;
+  __syncthreads();
+  if (sl != 0) return;
+  a0 = 0.0; a1 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { a0 += sh[k][0][cl]; a1 += sh[k][1][cl]; }
+}
+
 // partial[nblk][2][C] (fp32, one per producer block) -> sums[G][2][C] (fp64), fixed order.
 // group gi owns rows [gi*bpg, (gi+1)*bpg).  Large row counts are reduced in two deterministic
 // stages (row chunks in parallel -> fp64 chunk sums -> final) so that e.g. the 16384 partials
 // per view of the stem do not serialise on four workgroups.
-template <typename TIN>
-__global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const TIN* __restrict__ in, double* __restrict__ out, int bpg,
+__global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const float* __restrict__ in, double* __restrict__ out, int bpg,
                                                              int C, int rpc, int nchunks, P2PTail x) {
   __shared__ double sh[8][2][32];
   const int t = threadIdx.x, cl = t & 31, sl = t >> 5;
@@ -47,35 +64,37 @@ __global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const TIN* __restri
   const int r0 = ch * rpc, r1 = min(bpg, r0 + rpc);
   double a0 = 0.0, a1 = 0.0;
   if (c < C) {
-    const TIN* p = in + (size_t)gi * bpg * 2 * C;
+    const float* p = in + (size_t)gi * bpg * 2 * C;
     for (int b = r0 + sl; b < r1; b += 8) {
       a0 += (double)p[(size_t)b * 2 * C + c];
       a1 += (double)p[(size_t)b * 2 * C + C + c];
     }
   }
-  sh[sl][0][cl] = a0;
-  sh[sl][1][cl] = a1;
-  __syncthreads();
+  bn_cols_reduce(sh, a0, a1);
   if (sl == 0 && c < C) {
-    double r0s = 0.0, r1s = 0.0;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) { r0s += sh[s][0][cl]; r1s += sh[s][1][cl]; }
     double* o = out + ((size_t)gi * nchunks + ch) * 2 * C;
-    bn_store_sum(x, &o[c], r0s);
-    bn_store_sum(x, &o[C + c], r1s);
+    bn_store_sum(x, &o[c], a0);
+    bn_store_sum(x, &o[C + c], a1);
   }
   if (x.peers) bn_xchg_tail(x, out, (int)(gridDim.y * 2 * C), gridDim.x * gridDim.y);      // (only launched with nchunks == 1: out = sums)
 }
 
-// running = (1 - momentum) * running + momentum * statistic (unbiased variance).  A NaN statistic - the poison a failed SyncBN
-// window exchange writes into its sums (vfs_p2p.h) - must not reach the running statistics: they outlive the step (checkpoints).
-// (written with explicit fmaf: the compiler contracted `a * b + c * d` differently in different kernels - the fused and the
-// two-launch finalisation must produce the same bits, tests/test_emu_bn.py::test_bn_chunked_single_launch_reduction)
-// (bn_running_update: vfs_ops.h - shared with the fused Linear + BatchNorm1d launch of csrc/conv_pw.hip)
+// what the last reduction stage does with the sums of a group, by MODE: 0 finalize (bnp, running statistics updated group after
+// group - each group is one BN call of the reference), 1 parameter gradients (dbeta += sum_g S1, dgamma += sum_g S2: LOCAL sums,
+// DDP averages them), 2 nothing (the sums are the result)
+struct BnStatOut {
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  float* bnp = nullptr;
+  float* running_mean = nullptr;
+  float* running_var = nullptr;
+  double count = 1.0;
+  float eps = 0.f, momentum = 0.f;
+  float* dgamma = nullptr;
+  float* dbeta = nullptr;
+};
 
-// sums[G][2][C] (sum x, sum x^2; already all-reduced across ranks for SyncBN) + count ->
-// bnp, and the running statistics updated group after group (each group is one BN call of the
-// reference: running = (1-momentum)*running + momentum*stat, unbiased variance).
+// sums[G][2][C] (sum x, sum x^2; already all-reduced across ranks for SyncBN) + count -> bnp, running statistics
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ bnp,
                                                           float* __restrict__ running_mean, float* __restrict__ running_var,
@@ -84,161 +103,129 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
   if (c >= C) return;
   float rm = running_mean ? running_mean[c] : 0.f, rv = running_var ? running_var[c] : 0.f;
   for (int gi = 0; gi < G; ++gi) {
-    const double mean = sums[((size_t)gi * 2) * C + c] / count;
-    double var = sums[((size_t)gi * 2 + 1) * C + c] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float scale = gamma[c] * invstd;
-    float* o = bnp + (size_t)gi * 4 * C;
-    o[c] = scale;
-    o[C + c] = beta[c] - (float)mean * scale;
-    o[2 * C + c] = (float)mean;
-    o[3 * C + c] = invstd;
-    const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-    bn_running_update(rm, rv, momentum, mean, unbiased);
+    const BnCoef k = bn_finalize_channel(sums[((size_t)gi * 2) * C + c], sums[((size_t)gi * 2 + 1) * C + c], count, eps, gamma[c], beta[c]);
+    bn_store_params(bnp, gi, C, c, k);
+    bn_running_update(rm, rv, momentum, k.mean, k.unbiased);
   }
   if (running_mean) running_mean[c] = rm;
   if (running_var) running_var[c] = rv;
 }
 
-// Single-process fast path: the last reduction stage fused with bn_finalize (MODE 0) or with
-// bn_param_grad (MODE 1) -- one launch less per BatchNorm layer and direction.  One workgroup owns
-// 32 channels and walks the groups in order (the running statistics are updated group by group).
-template <typename TIN, int MODE>
-__global__ __launch_bounds__(256) void bn_reduce_fused_kernel(const TIN* __restrict__ in, double* __restrict__ sums, int G, int rows,
-                                                              int C, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              float* __restrict__ bnp, float* __restrict__ running_mean,
-                                                              float* __restrict__ running_var, double count, float eps,
-                                                              float momentum, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                              P2PTail x) {
-  __shared__ double sh[8][2][32];
+// The last reduction stage with its MODE step fused in (one launch less per BatchNorm layer and direction): the workgroup owns
+// 32 channels and walks the groups in order; src.accumulate(gi, sl, c, a0, a1) adds row lane sl's rows of group gi, channel c.
+template <int MODE, class RowSource>
+__device__ __forceinline__ void bn_finish_groups(const RowSource& src, double (*sh)[2][32], double* sums, int G, int C,
+                                                 const BnStatOut& o, const P2PTail& x) {
   const int t = threadIdx.x, cl = t & 31, sl = t >> 5;
   const int c = blockIdx.x * 32 + cl;
   float rm = 0.f, rv = 0.f;
   double g1 = 0.0, g2 = 0.0;
-  if (MODE == 0 && sl == 0 && c < C) { rm = running_mean ? running_mean[c] : 0.f; rv = running_var ? running_var[c] : 0.f; }
+  if (MODE == 0 && sl == 0 && c < C) { rm = o.running_mean ? o.running_mean[c] : 0.f; rv = o.running_var ? o.running_var[c] : 0.f; }
   for (int gi = 0; gi < G; ++gi) {
     double a0 = 0.0, a1 = 0.0;
-    if (c < C) {
-      const TIN* p = in + (size_t)gi * rows * 2 * C;
-      for (int b = sl; b < rows; b += 8) {
-        a0 += (double)p[(size_t)b * 2 * C + c];
-        a1 += (double)p[(size_t)b * 2 * C + C + c];
-      }
-    }
+    if (c < C) src.accumulate(gi, sl, c, a0, a1);
     __syncthreads();
-    sh[sl][0][cl] = a0;
-    sh[sl][1][cl] = a1;
-    __syncthreads();
+    bn_cols_reduce(sh, a0, a1);
     if (sl == 0 && c < C) {
-      double r0 = 0.0, r1 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { r0 += sh[k][0][cl]; r1 += sh[k][1][cl]; }
-      bn_store_sum(x, &sums[((size_t)gi * 2 + 0) * C + c], r0);
-      bn_store_sum(x, &sums[((size_t)gi * 2 + 1) * C + c], r1);
+      bn_store_sum(x, &sums[((size_t)gi * 2 + 0) * C + c], a0);
+      bn_store_sum(x, &sums[((size_t)gi * 2 + 1) * C + c], a1);
       if (MODE == 0) {
-        const double mean = r0 / count;
-        double var = r1 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float scale = gamma[c] * invstd;
-        float* o = bnp + (size_t)gi * 4 * C;
-        o[c] = scale;
-        o[C + c] = beta[c] - (float)mean * scale;
-        o[2 * C + c] = (float)mean;
-        o[3 * C + c] = invstd;
-        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        bn_running_update(rm, rv, momentum, mean, unbiased);
-      } else {
-        g1 += r0; g2 += r1;
+        const BnCoef k = bn_finalize_channel(a0, a1, o.count, o.eps, o.gamma[c], o.beta[c]);
+        bn_store_params(o.bnp, gi, C, c, k);
+        bn_running_update(rm, rv, o.momentum, k.mean, k.unbiased);
+      } else if (MODE == 1) {
+        g1 += a0; g2 += a1;
       }
     }
   }
   if (sl == 0 && c < C) {
     if (MODE == 0) {
-      if (running_mean) running_mean[c] = rm;
-      if (running_var) running_var[c] = rv;
-    } else {
-      dbeta[c] += (float)g1;
-      dgamma[c] += (float)g2;
+      if (o.running_mean) o.running_mean[c] = rm;
+      if (o.running_var) o.running_var[c] = rv;
+    } else if (MODE == 1) {
+      o.dbeta[c] += (float)g1;
+      o.dgamma[c] += (float)g2;
     }
   }
+}
+// the three row sources
+struct BnRowsF32 {       // fp32 statistics rows [G][rows][2][C]
+  const float* in;
+  int rows, C;
+  __device__ __forceinline__ void accumulate(int gi, int sl, int c, double& a0, double& a1) const {
+    const float* p = in + (size_t)gi * rows * 2 * C;
+    for (int b = sl; b < rows; b += 8) {
+      a0 += (double)p[(size_t)b * 2 * C + c];
+      a1 += (double)p[(size_t)b * 2 * C + C + c];
+    }
+  }
+};
+struct BnRowsRaw {       // the stored bf16 tensor itself [G][rows][C]: v, v * v
+  const bf16_t* x;
+  int rows, C;
+  __device__ __forceinline__ void accumulate(int gi, int sl, int c, double& a0, double& a1) const {
+    const bf16_t* p = x + (size_t)gi * rows * C;
+    for (int b = sl; b < rows; b += 8) {
+      const double v = (double)bf2f(p[(size_t)b * C + c]);
+      a0 += v;
+      a1 += v * v;
+    }
+  }
+};
+struct BnRowsChunks {    // fp64 chunk sums [G][nchunks][2][C] of OTHER workgroups of this launch: device-coherent loads, four chunks
+  const double* chunks;  // (eight loads) in flight per lane - they bypass the L2, ~1 us each
+  int nchunks, C;
+  __device__ __forceinline__ void accumulate(int gi, int sl, int c, double& a0, double& a1) const {
+    const double* p = chunks + (size_t)gi * nchunks * 2 * C;
+    int b = sl;
+    for (; b + 24 < nchunks; b += 32) {
+      const double x0 = vfs_load_agent(&p[(size_t)b * 2 * C + c]), y0 = vfs_load_agent(&p[(size_t)b * 2 * C + C + c]);
+      const double x1 = vfs_load_agent(&p[(size_t)(b + 8) * 2 * C + c]), y1 = vfs_load_agent(&p[(size_t)(b + 8) * 2 * C + C + c]);
+      const double x2 = vfs_load_agent(&p[(size_t)(b + 16) * 2 * C + c]), y2 = vfs_load_agent(&p[(size_t)(b + 16) * 2 * C + C + c]);
+      const double x3 = vfs_load_agent(&p[(size_t)(b + 24) * 2 * C + c]), y3 = vfs_load_agent(&p[(size_t)(b + 24) * 2 * C + C + c]);
+      a0 += (x0 + x1) + (x2 + x3);
+      a1 += (y0 + y1) + (y2 + y3);
+    }
+    for (; b < nchunks; b += 8) {
+      a0 += vfs_load_agent(&p[(size_t)b * 2 * C + c]);
+      a1 += vfs_load_agent(&p[(size_t)b * 2 * C + C + c]);
+    }
+  }
+};
+
+// Single-process fast path (few rows): one workgroup per 32 channels reduces the rows and finishes, MODE 0 or 1
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_reduce_fused_kernel(const float* __restrict__ in, double* __restrict__ sums, int G, int rows,
+                                                              int C, BnStatOut o, P2PTail x) {
+  __shared__ double sh[8][2][32];
+  bn_finish_groups<MODE>(BnRowsF32{in, rows, C}, sh, sums, G, C, o, x);
   if (MODE != 0 && x.peers) bn_xchg_tail(x, sums, G * 2 * C, gridDim.x);
 }
 
 // Statistics straight from the stored bf16 conv output for SMALL groups (the head's Linear layers: 32 rows per view):
 // lets one conv launch cover all groups when a group is not a multiple of the 128-pixel statistics rows.
 __global__ __launch_bounds__(256) void bn_stats_raw_kernel(const bf16_t* __restrict__ x, double* __restrict__ sums, int G, int rows, int C,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ bnp, float* __restrict__ running_mean,
-                                                           float* __restrict__ running_var, double count, float eps, float momentum) {
+                                                           BnStatOut o) {
   __shared__ double sh[8][2][32];
-  const int t = threadIdx.x, cl = t & 31, sl = t >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  float rm = 0.f, rv = 0.f;
-  if (sl == 0 && c < C) { rm = running_mean ? running_mean[c] : 0.f; rv = running_var ? running_var[c] : 0.f; }
-  for (int gi = 0; gi < G; ++gi) {
-    double a0 = 0.0, a1 = 0.0;
-    if (c < C) {
-      const bf16_t* p = x + (size_t)gi * rows * C;
-      for (int b = sl; b < rows; b += 8) {
-        const double v = (double)bf2f(p[(size_t)b * C + c]);
-        a0 += v;
-        a1 += v * v;
-      }
-    }
-    __syncthreads();
-    sh[sl][0][cl] = a0;
-    sh[sl][1][cl] = a1;
-    __syncthreads();
-    if (sl == 0 && c < C) {
-      double r0 = 0.0, r1 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { r0 += sh[k][0][cl]; r1 += sh[k][1][cl]; }
-      sums[((size_t)gi * 2 + 0) * C + c] = r0;
-      sums[((size_t)gi * 2 + 1) * C + c] = r1;
-      const double mean = r0 / count;
-      double var = r1 / count - mean * mean;
-      if (var < 0.0) var = 0.0;
-      const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-      const float scale = gamma[c] * invstd;
-      float* o = bnp + (size_t)gi * 4 * C;
-      o[c] = scale;
-      o[C + c] = beta[c] - (float)mean * scale;
-      o[2 * C + c] = (float)mean;
-      o[3 * C + c] = invstd;
-      const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-      bn_running_update(rm, rv, momentum, mean, unbiased);
-    }
-  }
-  if (sl == 0 && c < C) {
-    if (running_mean) running_mean[c] = rm;
-    if (running_var) running_var[c] = rv;
-  }
+  bn_finish_groups<0>(BnRowsRaw{x, rows, C}, sh, sums, G, C, o, P2PTail{});
 }
 int vfs_bn_stats_raw_launch(const bf16_t* x, double* sums, int G, int rows, int C, const float* gamma, const float* beta, float* bnp,
                             float* rm, float* rv, double count, float eps, float momentum, hipStream_t s) {
   if (G <= 0 || rows <= 0 || C <= 0) return vfs_set_error(VFS_ERR_SHAPE, "bn_stats_raw: empty");
-  hipLaunchKernelGGL(bn_stats_raw_kernel, dim3((C + 31) / 32), dim3(256), 0, s, x, sums, G, rows, C, gamma, beta, bnp, rm, rv, count,
-                     eps, momentum);
+  const BnStatOut o{gamma, beta, bnp, rm, rv, count, eps, momentum};
+  hipLaunchKernelGGL(bn_stats_raw_kernel, dim3((C + 31) / 32), dim3(256), 0, s, x, sums, G, rows, C, o);
   return vfs_check_launch("bn_stats_raw");
 }
 
 // The same two stages in ONE launch for large row counts: grid (channel blocks, groups, row chunks);
 // every workgroup writes the fp64 sums of its chunk to `chunks`, publishes them (agent-scope fence)
 // and draws a ticket for its channel block; the workgroup that draws the LAST ticket of a channel
-// block finishes that block: fixed-order sum over the chunks, then the fused finalize (MODE 0),
-// parameter-gradient (MODE 1) or plain sums (MODE 2) step.  Deterministic (the summation order does
-// not depend on which workgroup is last); the ticket counters return to zero.
+// block finishes that block: fixed-order sum over the chunks, then the MODE step.  Deterministic (the
+// summation order does not depend on which workgroup is last); the ticket counters return to zero.
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_reduce_ticket_kernel(const float* __restrict__ in, double* __restrict__ sums,
                                                                double* __restrict__ chunks, unsigned* __restrict__ tickets,
-                                                               int G, int bpg, int C, int rpc, int nchunks,
-                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               float* __restrict__ bnp, float* __restrict__ running_mean,
-                                                               float* __restrict__ running_var, double count, float eps,
-                                                               float momentum, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               P2PTail x) {
+                                                               int G, int bpg, int C, int rpc, int nchunks, BnStatOut o, P2PTail x) {
   __shared__ double sh[8][2][32];
   __shared__ unsigned s_ticket;
   const int t = threadIdx.x, cl = t & 31, sl = t >> 5;
@@ -263,16 +250,11 @@ __global__ __launch_bounds__(256) void bn_reduce_ticket_kernel(const float* __re
         a1 += (double)p[(size_t)b * 2 * C + C + c];
       }
     }
-    sh[sl][0][cl] = a0;
-    sh[sl][1][cl] = a1;
-    __syncthreads();
+    bn_cols_reduce(sh, a0, a1);
     if (sl == 0 && c < C) {
-      double r0s = 0.0, r1s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { r0s += sh[k][0][cl]; r1s += sh[k][1][cl]; }
-      double* o = chunks + ((size_t)gi * nchunks + ch) * 2 * C;
-      vfs_store_agent(&o[c], r0s);       // device-coherent stores (no L2 write-back fence, see vfs_common.h)
-      vfs_store_agent(&o[C + c], r1s);
+      double* dst = chunks + ((size_t)gi * nchunks + ch) * 2 * C;
+      vfs_store_agent(&dst[c], a0);      // device-coherent stores (no L2 write-back fence, see vfs_common.h)
+      vfs_store_agent(&dst[C + c], a1);
     }
   }
   vfs_release_workgroup();               // this wave's chunk sums have been performed
@@ -280,67 +262,11 @@ __global__ __launch_bounds__(256) void bn_reduce_ticket_kernel(const float* __re
   if (t == 0) s_ticket = vfs_ticket_agent(&tickets[blockIdx.x]);
   __syncthreads();
   if (s_ticket != (unsigned)(gridDim.y * gridDim.z) - 1u) return;
-  float rm = 0.f, rv = 0.f;
-  double g1 = 0.0, g2 = 0.0;
-  if (MODE == 0 && sl == 0 && c < C) { rm = running_mean ? running_mean[c] : 0.f; rv = running_var ? running_var[c] : 0.f; }
-  for (int gi = 0; gi < G; ++gi) {
-    double a0 = 0.0, a1 = 0.0;
-    if (c < C) {
-      const double* p = chunks + (size_t)gi * nchunks * 2 * C;
-      int b = sl;                          // device-coherent loads of the other workgroups' sums, four chunks
-      for (; b + 24 < nchunks; b += 32) {  // (eight loads) in flight per lane: they bypass the L2, ~1 us each
-        const double x0 = vfs_load_agent(&p[(size_t)b * 2 * C + c]), y0 = vfs_load_agent(&p[(size_t)b * 2 * C + C + c]);
-        const double x1 = vfs_load_agent(&p[(size_t)(b + 8) * 2 * C + c]), y1 = vfs_load_agent(&p[(size_t)(b + 8) * 2 * C + C + c]);
-        const double x2 = vfs_load_agent(&p[(size_t)(b + 16) * 2 * C + c]), y2 = vfs_load_agent(&p[(size_t)(b + 16) * 2 * C + C + c]);
-        const double x3 = vfs_load_agent(&p[(size_t)(b + 24) * 2 * C + c]), y3 = vfs_load_agent(&p[(size_t)(b + 24) * 2 * C + C + c]);
-        a0 += (x0 + x1) + (x2 + x3);
-        a1 += (y0 + y1) + (y2 + y3);
-      }
-      for (; b < nchunks; b += 8) {
-        a0 += vfs_load_agent(&p[(size_t)b * 2 * C + c]);
-        a1 += vfs_load_agent(&p[(size_t)b * 2 * C + C + c]);
-      }
-    }
-    __syncthreads();
-    sh[sl][0][cl] = a0;
-    sh[sl][1][cl] = a1;
-    __syncthreads();
-    if (sl == 0 && c < C) {
-      double r0 = 0.0, r1 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { r0 += sh[k][0][cl]; r1 += sh[k][1][cl]; }
-      bn_store_sum(x, &sums[((size_t)gi * 2 + 0) * C + c], r0);
-      bn_store_sum(x, &sums[((size_t)gi * 2 + 1) * C + c], r1);
-      if (MODE == 0) {
-        const double mean = r0 / count;
-        double var = r1 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float scale = gamma[c] * invstd;
-        float* o = bnp + (size_t)gi * 4 * C;
-        o[c] = scale;
-        o[C + c] = beta[c] - (float)mean * scale;
-        o[2 * C + c] = (float)mean;
-        o[3 * C + c] = invstd;
-        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        bn_running_update(rm, rv, momentum, mean, unbiased);
-      } else if (MODE == 1) {
-        g1 += r0; g2 += r1;
-      }
-    }
-  }
-  if (sl == 0 && c < C) {
-    if (MODE == 0) {
-      if (running_mean) running_mean[c] = rm;
-      if (running_var) running_var[c] = rv;
-    } else if (MODE == 1) {
-      dbeta[c] += (float)g1;
-      dgamma[c] += (float)g2;
-    }
-  }
+  bn_finish_groups<MODE>(BnRowsChunks{chunks, nchunks, C}, sh, sums, G, C, o, x);
   if (t == 0) tickets[blockIdx.x] = 0u;  // ready for the next launch on this stream
   if (MODE != 0 && x.peers) bn_xchg_tail(x, sums, G * 2 * C, gridDim.x);      // one finisher per channel block arrives here
 }
+
 
 // eval-mode BN: bnp from running statistics (G = 1)
 __global__ __launch_bounds__(256) void bn_eval_params_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -377,7 +303,7 @@ struct SlabGeom {
 // 2 C bytes.  Measured ceiling of this box for the same traffic pattern (2 reads + 1 write, torch's elementwise add): 5.7-6.0 TB/s;
 // the 64-channel slabs reached 4.4-4.8 (tools/probe_stream_bw.py, MEASUREMENTS.md).  The bit-packed mask keeps its slab-major
 // layout (64-channel sub-slabs, vfs_common.h): a lane still writes / reads the byte of its own 8 channels.
-__device__ __forceinline__ int slab_width(int C, int wide) { return C < 64 ? C : (wide ? (C < 512 ? C : 512) : 64); }
+__host__ __device__ __forceinline__ int slab_width(int C, int wide = 0) { return C < 64 ? C : (wide ? (C < 512 ? C : 512) : 64); }
 __device__ __forceinline__ SlabGeom slab_geom(long long M, int C, int mpg, int ppb, int wide = 0) {
   SlabGeom s;
   const int cslab = slab_width(C, wide);
@@ -399,8 +325,8 @@ __device__ __forceinline__ SlabGeom slab_geom(long long M, int C, int mpg, int p
 // host side: pixels per block (a multiple of the 4-row trip) for ~4096 workgroups, and the grid
 static inline int slab_wide_ok(int C) { return C >= 128 && (C <= 512 ? (512 % C == 0 || C % 64 == 0) && 256 % (C >> 3) == 0 : C % 512 == 0); }
 static inline dim3 slab_grid(long long M, int C, int mpg, int* ppb_out, int wide = 0) {
-  const int cslab = C < 64 ? C : (wide ? (C < 512 ? C : 512) : 64), rows = 256 / (cslab >> 3), unit = 4 * rows;
-  const int slabs = C < 64 ? 1 : C / cslab;
+  const int cslab = slab_width(C, wide), rows = 256 / (cslab >> 3), unit = 4 * rows;
+  const int slabs = C / cslab;
   long long per = (M * slabs + 4095) / 4096;
   long long ppb = ((per + unit - 1) / unit) * unit;
   if (ppb < unit) ppb = unit;
@@ -453,7 +379,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a, BnFin f, int p
     __shared__ float coef[2][64];
     __shared__ double xloc[256];                 // folded exchange: the lead's sums [g][row][channel of the slab]
     __shared__ int s_failed;
-    const int t = threadIdx.x, cslab = a.C < 64 ? a.C : 64;
+    const int t = threadIdx.x, cslab = slab_width(a.C);
     const bool lead = blockIdx.x == 0;            // first block of group 0: writes bnp / sums / running statistics
     const bool xch = f.x.peers != nullptr;        // SyncBN: the slab leads exchange their sums with the peers' leads (vfs_p2p.h)
     const int c = blockIdx.y * cslab + t;
@@ -491,15 +417,10 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a, BnFin f, int p
         __syncthreads();
       }
       if (t < cslab) {
-        const double mean = sums_s[0][t] / f.count;
-        double var = sums_s[1][t] / f.count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)f.eps));
-        const float scale = f.gamma[c] * invstd, shift = f.beta[c] - (float)mean * scale;
-        if (g == s.gi) { coef[0][t] = scale; coef[1][t] = shift; }
+        const BnCoef k = bn_finalize_channel(sums_s[0][t], sums_s[1][t], f.count, f.eps, f.gamma[c], f.beta[c]);
+        if (g == s.gi) { coef[0][t] = k.scale; coef[1][t] = k.shift; }
         if (lead) {
-          float* o = f.bnp + (size_t)g * 4 * a.C;
-          o[c] = scale; o[a.C + c] = shift; o[2 * a.C + c] = (float)mean; o[3 * a.C + c] = invstd;
+          bn_store_params(f.bnp, g, a.C, c, k);
           if (xch) {
             vfs_store_agent(f.sums + ((size_t)g * 2 + 0) * a.C + c, sums_s[0][t]);
             vfs_store_agent(f.sums + ((size_t)g * 2 + 1) * a.C + c, sums_s[1][t]);
@@ -507,8 +428,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a, BnFin f, int p
             f.sums[((size_t)g * 2 + 0) * a.C + c] = sums_s[0][t];
             f.sums[((size_t)g * 2 + 1) * a.C + c] = sums_s[1][t];
           }
-          const double unbiased = f.count > 1.0 ? var * (f.count / (f.count - 1.0)) : var;
-          bn_running_update(rm, rv, f.momentum, mean, unbiased);
+          bn_running_update(rm, rv, f.momentum, k.mean, k.unbiased);
         }
       }
     }
@@ -695,91 +615,103 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_kernel(PoolBwdArgs a) {
 }
 
 
+// The load batch of the BatchNorm-backward streams: (g, x, mask operand) of channels c..c+7 of the four pixel rows m, m + step, ...
+// - 8-12 independent 16-byte loads in flight per lane.  A row from mend on is not ok: it loads row mfirst and is skipped.
+struct BnBwdBatch {
+  u32x4 gv[4], xv[4];
+  unsigned ym[4];      // with a.y: bit i <-> the activation of channel c + i is positive
+  bool ok[4];
+};
+__device__ __forceinline__ void bn_bwd_load4(const BnBwdArgs& a, long long m, int step, long long mend, long long mfirst, int c,
+                                             BnBwdBatch& b) {
+  long long moff[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long long mu = m + (long long)u * step;
+    b.ok[u] = mu < mend;
+    moff[u] = b.ok[u] ? mu : mfirst;
+    const size_t o = (size_t)moff[u] * a.C + c;
+    b.gv[u] = ld16(a.g + o);
+    b.xv[u] = ld16(a.x + o);
+  }
+  // the mask operand in its own straight-line batch per mode (a load inside the per-row conditional is waited for alone)
+  if (a.y && a.relu == VFS_MASK_BITS) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) b.ym[u] = mask8_load(a.y, moff[u], c, a.M, a.C);
+  } else if (a.y) {
+    u32x4 yv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) yv[u] = ld16(a.y + (size_t)moff[u] * a.C + c);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) b.ym[u] = mask8_of(yv[u]);
+  }
+}
+// row u of a batch: x and the masked gradient of its eight channels (sc, sh: the scale / shift rows of bnp)
+__device__ __forceinline__ void bn_bwd_unpack(const BnBwdArgs& a, const BnBwdBatch& b, int u, const float* sc, const float* sh, float* g,
+                                              float* x) {
+  unpack8(b.gv[u], g);
+  unpack8(b.xv[u], x);
+  bn_mask_grad(g, x, b.ym[u], a.y != nullptr, a.relu, sc, sh);
+}
+
+// The tail of the S1 / S2 row kernels: every thread spills its sums to red[t][0..16) (S1 of its 8 channels, then S2) ...
+__device__ __forceinline__ void bn_row_spill17(float (*red)[17], const float* s1, const float* s2) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { red[threadIdx.x][i] = s1[i]; red[threadIdx.x][8 + i] = s2[i]; }
+  __syncthreads();
+}
+// ... and element e < cv * 16 of the row (channel (e / 16) * 8 + (e & 7), statistic (e % 16) >> 3) is the sum over the row
+// threads in fixed order
+__device__ __forceinline__ float bn_row_sum17(float (*red)[17], int cv, int rows, int e) {
+  const int ec = e / 16, ei = e % 16;
+  float s = 0.f;
+  for (int r = 0; r < rows; ++r) s += red[r * cv + ec][ei];
+  return s;
+}
+
 // One statistics row of the BatchNorm backward: S1 = sum g*mask, S2 = sum g*mask*xhat over the ppb pixels from m0 on, for the <= 64
-// channels of slab blockIdx.y; every thread of the workgroup calls it; the row lands in red and thread (ec, ei) of the
-// first cv * 16 returns ITS element (channel ec * 8 + (ei & 7), statistic ei >> 3) - summed over the row threads in fixed order.
+// channels of slab blockIdx.y; every thread of the workgroup calls it; the row lands in red and thread e of the first cv * 16
+// returns ITS element (bn_row_sum17).
 // Shared by bn_bwd_reduce_kernel (the row goes to HBM) and bn_bwd_apply_kernel<true, true> (round 6: the row never leaves the launch).
 __device__ __forceinline__ float bn_bwd_row(const BnBwdArgs& a, long long m0, int ppb, float (*red)[17], int e) {
-  const int cslab = a.C < 64 ? a.C : 64;
+  const int cslab = slab_width(a.C);
   const int cv = cslab >> 3;        // chunk-threads per pixel (<= 8)
   const int rows = 256 / cv;        // pixels processed per step
   const int t = threadIdx.x;
   const int ct = t % cv, rt = t / cv;
   const int gi = (int)(m0 / a.mpg);
   const int c = blockIdx.y * cslab + ct * 8;
-  const bool bits = a.relu == VFS_MASK_BITS;
   float s1[8], s2[8], mean[8], inv[8], sc[8], sh[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
   if (rt < rows) {
-    ld8f(a.bnp + (size_t)gi * 4 * a.C + c, sc);
-    ld8f(a.bnp + (size_t)gi * 4 * a.C + a.C + c, sh);
-    ld8f(a.bnp + (size_t)gi * 4 * a.C + 2 * a.C + c, mean);
-    ld8f(a.bnp + (size_t)gi * 4 * a.C + 3 * a.C + c, inv);
-    // four pixel rows per trip: 8-12 independent 16-byte loads in flight per lane
+    const float* bp = a.bnp + (size_t)gi * 4 * a.C + c;
+    ld8f(bp, sc);
+    ld8f(bp + a.C, sh);
+    ld8f(bp + 2 * a.C, mean);
+    ld8f(bp + 3 * a.C, inv);
+    const long long mend = m0 + ppb < a.M ? m0 + ppb : a.M;
     for (int r = rt; r < ppb; r += 4 * rows) {
-      u32x4 gv[4], xv[4];
-      unsigned ym[4];
-      long long moff[4];
-      bool ok[4];
+      BnBwdBatch b;
+      bn_bwd_load4(a, m0 + r, rows, mend, m0, c, b);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const long long m = m0 + r + u * rows;
-        ok[u] = (r + u * rows < ppb) && (m < a.M);
-        const size_t o = (size_t)(ok[u] ? m : m0) * a.C + c;
-        gv[u] = ld16(a.g + o);
-        xv[u] = ld16(a.x + o);
-        moff[u] = ok[u] ? m : m0;
-      }
-      // the mask operand in its own straight-line batch per mode (a load inside the per-row conditional is waited for alone)
-      if (a.y && bits) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ym[u] = mask8_load(a.y, moff[u], c, a.M, a.C);
-      } else if (a.y) {
-        u32x4 yv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) yv[u] = ld16(a.y + (size_t)moff[u] * a.C + c);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ym[u] = mask8_of(yv[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (!ok[u]) continue;
+        if (!b.ok[u]) continue;
         float g[8], x[8];
-        unpack8(gv[u], g);
-        unpack8(xv[u], x);
-        if (a.y) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) g[i] = ((ym[u] >> i) & 1u) ? g[i] : 0.f;
-        } else if (a.relu) {   // plain conv->BN->ReLU unit: the mask is recomputed from x (saves a read)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) g[i] = (x[i] * sc[i] + sh[i] > 0.f) ? g[i] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          s1[i] += g[i];
-          s2[i] += g[i] * ((x[i] - mean[i]) * inv[i]);
-        }
+        bn_bwd_unpack(a, b, u, sc, sh, g, x);
+        bn_bwd_accum(s1, s2, g, x, mean, inv);
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t][i] = s1[i]; red[t][8 + i] = s2[i]; }
-  __syncthreads();
-  // thread (ct, i16) sums over the row-threads in fixed order
-  float s = 0.f;
-  if (e < cv * 16) {
-    const int ec = e / 16, ei = e % 16;
-    for (int r = 0; r < rows; ++r) s += red[r * cv + ec][ei];
-  }
-  return s;
+  bn_row_spill17(red, s1, s2);
+  return e < cv * 16 ? bn_row_sum17(red, cv, rows, e) : 0.f;
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnBwdArgs a) {
   // workgroup = ppb pixels x one slab of <= 64 channels (blockIdx.y): wide layers (C up to 2048 with
   // few pixels) still fill the chip, and every lane keeps 8-12 independent 16-byte loads in flight
   __shared__ float red[256][17];
-  const int cslab = a.C < 64 ? a.C : 64, cv = cslab >> 3;
+  const int cslab = slab_width(a.C), cv = cslab >> 3;
   const int e = threadIdx.x;        // cv * 16 <= 128 result elements: one per thread
   const float s = bn_bwd_row(a, (long long)blockIdx.x * a.ppb, a.ppb, red, e);
   if (e < cv * 16) {
@@ -788,6 +720,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnBwdArgs a) {
     a.partial[(size_t)blockIdx.x * 2 * a.C + (ei >> 3) * a.C + ch] = s;
   }
 }
+
 
 // pass 2: dx = scale * (gm - S1/count - xhat * S2/count) = A*gm + B*x + D with per-channel
 // A = scale, B = -scale*invstd*m2, D = scale*(mean*invstd*m2 - m1) held in registers
@@ -802,7 +735,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a, BnFin f,
     __shared__ double red[4][2][64], sums_s[2][64], mine[2][64];
     __shared__ double xloc[256];                 // folded exchange: the lead's sums [g][row][channel of the slab]
     __shared__ int s_failed;
-    const int t = threadIdx.x, cslab = a.C < 64 ? a.C : 64;
+    const int t = threadIdx.x, cslab = slab_width(a.C);
     const bool lead = blockIdx.x == 0;            // writes sums, accumulates dgamma / dbeta over the groups
     const bool xch = f.x.peers != nullptr;        // SyncBN: S1 / S2 over all ranks (vfs_p2p.h); dgamma / dbeta stay LOCAL sums
     const int c = blockIdx.y * cslab + t;
@@ -869,7 +802,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a, BnFin f,
 #pragma unroll
     for (int i = 0; i < 8; ++i) { s1d[i] = sp[i]; s2d[i] = sp[a.C + i]; }
   }
-  const bool bits = a.relu == VFS_MASK_BITS;
   float A[8], B[8], D[8], sh[8];
   {
     float mean[8], inv[8];
@@ -880,49 +812,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a, BnFin f,
     ld8f(bp + 3 * a.C, inv);
     const float rc = (float)(1.0 / a.count);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float m1 = (float)s1d[i] * rc, m2 = (float)s2d[i] * rc;
-      B[i] = -A[i] * inv[i] * m2;
-      D[i] = A[i] * (mean[i] * inv[i] * m2 - m1);
-    }
+    for (int i = 0; i < 8; ++i) bn_bwd_coefs(A[i], mean[i], inv[i], s1d[i], s2d[i], rc, B[i], D[i]);
   }
   for (long long r = s.m0 + s.rt; r < s.mend; r += 4 * s.rows) {
-    u32x4 gv[4], xv[4];
-    unsigned ym[4];
-    long long moff[4];
-    bool ok[4];
+    BnBwdBatch b;
+    bn_bwd_load4(a, r, s.rows, s.mend, s.m0, s.c, b);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const long long m = r + (long long)u * s.rows;
-      ok[u] = m < s.mend;
-      moff[u] = ok[u] ? m : s.m0;
-      const size_t o = (size_t)moff[u] * a.C + s.c;
-      gv[u] = ld16(a.g + o);
-      xv[u] = ld16(a.x + o);
-    }
-    if (a.y && bits) {          // the mask operand in its own straight-line batch per mode (see bn_bwd_reduce_kernel)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) ym[u] = mask8_load(a.y, moff[u], s.c, a.M, a.C);
-    } else if (a.y) {
-      u32x4 yv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) yv[u] = ld16(a.y + (size_t)moff[u] * a.C + s.c);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) ym[u] = mask8_of(yv[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (!ok[u]) continue;
+      if (!b.ok[u]) continue;
       float g[8], x[8], d[8];
-      unpack8(gv[u], g);
-      unpack8(xv[u], x);
-      if (a.y) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g[i] = ((ym[u] >> i) & 1u) ? g[i] : 0.f;
-      } else if (a.relu) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g[i] = (x[i] * A[i] + sh[i] > 0.f) ? g[i] : 0.f;
-      }
+      bn_bwd_unpack(a, b, u, A, sh, g, x);
 #pragma unroll
       for (int i = 0; i < 8; ++i) d[i] = A[i] * g[i] + (B[i] * x[i] + D[i]);
       const size_t o = (size_t)(r + (long long)u * s.rows) * a.C + s.c;
@@ -973,11 +872,8 @@ __global__ __launch_bounds__(256) void stem_pool_bn_bwd_reduce_kernel(StemBwdArg
           unpack8(gv[u], g);
           unpack8(xv[u], x);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            g[i] = (((i < 4 ? iv[u].x : iv[u].y) >> (8 * (i & 3))) & 0xffu) != 0xffu ? g[i] : 0.f;
-            s1[i] += g[i];
-            s2[i] += g[i] * ((x[i] - mean[i]) * inv[i]);
-          }
+          for (int i = 0; i < 8; ++i) g[i] = (((i < 4 ? iv[u].x : iv[u].y) >> (8 * (i & 3))) & 0xffu) != 0xffu ? g[i] : 0.f;
+          bn_bwd_accum(s1, s2, g, x, mean, inv);
         }
       }
     } else
@@ -1010,19 +906,15 @@ __global__ __launch_bounds__(256) void stem_pool_bn_bwd_reduce_kernel(StemBwdArg
           const unsigned pos = (unsigned)(dy * 3 + dx);
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            if (code[i] == pos) s2[i] += g[i] * ((x[i] - mean[i]) * inv[i]);
+            if (code[i] == pos) s2[i] += g[i] * bn_xhat(x[i], mean[i], inv[i]);
         }
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t][i] = s1[i]; red[t][8 + i] = s2[i]; }
-  __syncthreads();
+  bn_row_spill17(red, s1, s2);
   for (int e = t; e < cv * 16; e += 256) {
     const int ec = e / 16, ei = e % 16;
-    float s = 0.f;
-    for (int r = 0; r < rows; ++r) s += red[r * cv + ec][ei];
-    a.partial[(size_t)blockIdx.x * 2 * a.C + (ei >> 3) * a.C + ec * 8 + (ei & 7)] = s;
+    a.partial[(size_t)blockIdx.x * 2 * a.C + (ei >> 3) * a.C + ec * 8 + (ei & 7)] = bn_row_sum17(red, cv, rows, e);
   }
 }
 
@@ -1084,10 +976,18 @@ static inline void bn_chunk_plan(int bpg, int* nchunks, int* rpc) {
   *rpc = (bpg + n - 1) / n;
   *nchunks = (bpg + *rpc - 1) / *rpc;
 }
+// f(std::integral_constant<int, MODE>) for the MODE (0, 1, anything else: 2) given at run time
+template <class F>
+static inline void bn_mode_switch(int mode, F&& f) {
+  if (mode == 0) f(std::integral_constant<int, 0>{});
+  else if (mode == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
+}
 int vfs_bn_reduce_fused_launch(int mode, const float* partial, double* sums, double* scratch, int G, int bpg, int C,
                                const float* gamma, const float* beta, float* bnp, float* rm, float* rv, double count, float eps,
                                float momentum, float* dgamma, float* dbeta, hipStream_t s, const P2PTail* tail) {
   const int cb = (C + 31) / 32;
+  const BnStatOut o{gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta};
   P2PTail x;
   if (tail) {
     if (mode == 0) return vfs_set_error(VFS_ERR_ARG, "bn_reduce: the fused finalize has no exchange (SyncBN finalizes after the exchange)");
@@ -1101,14 +1001,16 @@ int vfs_bn_reduce_fused_launch(int mode, const float* partial, double* sums, dou
     unsigned* tickets = reinterpret_cast<unsigned*>(scratch);
     double* chunks = scratch + VFS_BN_TICKETS / 2;
     const dim3 grid(cb, G, nchunks);
-    if (mode == 0) hipLaunchKernelGGL((bn_reduce_ticket_kernel<0>), grid, dim3(256), 0, s, partial, sums, chunks, tickets, G, bpg, C, rpc, nchunks, gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta, x);
-    else if (mode == 1) hipLaunchKernelGGL((bn_reduce_ticket_kernel<1>), grid, dim3(256), 0, s, partial, sums, chunks, tickets, G, bpg, C, rpc, nchunks, gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta, x);
-    else hipLaunchKernelGGL((bn_reduce_ticket_kernel<2>), grid, dim3(256), 0, s, partial, sums, chunks, tickets, G, bpg, C, rpc, nchunks, gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta, x);
+    bn_mode_switch(mode, [&](auto m) {
+      hipLaunchKernelGGL((bn_reduce_ticket_kernel<decltype(m)::value>), grid, dim3(256), 0, s, partial, sums, chunks, tickets, G, bpg, C, rpc,
+                         nchunks, o, x);
+    });
     return vfs_check_launch("bn_reduce_ticket");
   }
-  if (mode == 0) hipLaunchKernelGGL((bn_reduce_fused_kernel<float, 0>), dim3(cb), dim3(256), 0, s, partial, sums, G, bpg, C, gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta, x);
-  else if (mode == 1) hipLaunchKernelGGL((bn_reduce_fused_kernel<float, 1>), dim3(cb), dim3(256), 0, s, partial, sums, G, bpg, C, gamma, beta, bnp, rm, rv, count, eps, momentum, dgamma, dbeta, x);
-  else hipLaunchKernelGGL((bn_reduce_rows_kernel<float>), dim3(cb, G, 1), dim3(256), 0, s, partial, sums, bpg, C, bpg, 1, x);
+  bn_mode_switch(mode, [&](auto m) {
+    if constexpr (decltype(m)::value == 2) hipLaunchKernelGGL(bn_reduce_rows_kernel, dim3(cb, G, 1), dim3(256), 0, s, partial, sums, bpg, C, bpg, 1, x);
+    else hipLaunchKernelGGL((bn_reduce_fused_kernel<decltype(m)::value>), dim3(cb), dim3(256), 0, s, partial, sums, G, bpg, C, o, x);
+  });
   return vfs_check_launch("bn_reduce_fused");
 }
 // mode 0: statistics -> bnp + running stats ; mode 1: backward sums -> bsums + dgamma/dbeta ; 2: sums only
@@ -1145,7 +1047,7 @@ static int fin_check(const BnFin& f, long long M, int mpg, const char* who, bool
 // the folded SyncBN exchange (BnFin::x): what the windows and the slab layout can hold
 static int fin_xchg_check(const BnFin& f, int C, const char* who) {
   if (!f.x.peers) return VFS_OK;
-  const int cslab = C < 64 ? C : 64, slabs = C < 64 ? 1 : C / 64;
+  const int cslab = slab_width(C), slabs = C / cslab;
   if (!f.partial || f.G * 2 * cslab > 256 || slabs > P2P_MAXSLAB || f.G * 2 * C > P2P_MAXN || f.x.world < 1 || f.x.world > P2P_MAXW ||
       f.x.rank < 0 || f.x.rank >= f.x.world || !f.x.state)
     return vfs_set_error(VFS_ERR_ARG, who);
@@ -1173,9 +1075,8 @@ int vfs_maxpool_relu_bwd_launch(const PoolBwdArgs& a, hipStream_t s) {
   return vfs_check_launch("maxpool_relu_bwd");
 }
 int vfs_bn_bwd_reduce_launch(const BnBwdArgs& a, int nblk, hipStream_t s) {
-  if (a.C % 8 || (a.C < 64 && 256 % (a.C >> 3)) || (a.C >= 64 && a.C % 64))
-    return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_reduce: C must be 8*2^k below 64, a multiple of 64 above");
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk, a.C < 64 ? 1 : a.C / 64), dim3(256), 0, s, a);
+  if (!slab_ok(a.C)) return vfs_set_error(VFS_ERR_SHAPE, "bn_bwd_reduce: C must be 8*2^k below 64, a multiple of 64 above");
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk, a.C / slab_width(a.C)), dim3(256), 0, s, a);
   return vfs_check_launch("bn_bwd_reduce");
 }
 int vfs_bn_bwd_apply_launch(const BnBwdArgs& a, hipStream_t s) {

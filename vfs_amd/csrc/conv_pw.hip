@@ -20,6 +20,7 @@
 // after a tile's last K-step (T: the last stage is free) and the epilogue's own (the loaders mirror them).
 #include "vfs_igemm_epi.h"
 #include "vfs_ops.h"
+#include "vfs_bn.h"
 
 
 template <int BC, bool FBN>
@@ -327,21 +328,11 @@ __global__ __launch_bounds__(256) void linear_bn_act_kernel(LinBnArgs a) {
       for (int k = 0; k < 8; ++k) { r0 += sh[k][0][cl]; r1 += sh[k][1][cl]; }
       a.sums[((size_t)gi * 2 + 0) * C + c] = r0;
       a.sums[((size_t)gi * 2 + 1) * C + c] = r1;
-      const double mean = r0 / a.count;
-      double var = r1 / a.count - mean * mean;
-      if (var < 0.0) var = 0.0;
-      const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
-      const float scale = a.gamma[c] * invstd;
-      const float shift = a.beta[c] - (float)mean * scale;
-      float* o = a.bnp + (size_t)gi * 4 * C;
-      o[c] = scale;
-      o[C + c] = shift;
-      o[2 * C + c] = (float)mean;
-      o[3 * C + c] = invstd;
-      sCoef[gi][0][cl] = scale;
-      sCoef[gi][1][cl] = shift;
-      const double unbiased = a.count > 1.0 ? var * (a.count / (a.count - 1.0)) : var;
-      bn_running_update(rm, rv, a.momentum, mean, unbiased);
+      const BnCoef k = bn_finalize_channel(r0, r1, a.count, a.eps, a.gamma[c], a.beta[c]);
+      bn_store_params(a.bnp, gi, C, c, k);
+      sCoef[gi][0][cl] = k.scale;
+      sCoef[gi][1][cl] = k.shift;
+      bn_running_update(rm, rv, a.momentum, k.mean, k.unbiased);
     }
   }
   if (stat_thread && sl == 0) {

@@ -14,6 +14,7 @@
 //           starting at column 2wo-4 (tap s=-1 and row 7 carry zero weights): K = 8*8*4 = 256
 #pragma once
 #include "vfs_common.h"
+#include "vfs_bn.h"
 
 // GATHER_DGRADQ: the dgrad of a 1x1 / stride-2 / pad-0 convolution as the pure GEMM it is on the quarter grid - pixel (n, hc, wc) of
 // dy [N,Ho,Wo,Cout] is the only source of pixel (n, 2 hc, 2 wc) of dx - whose epilogue reads `add` and writes `out` at that pixel of
@@ -322,18 +323,8 @@ __device__ __forceinline__ void bnfuse_accum(BnFuseLane& L, const BnBwdFuse& bn,
   float g[8], x[8];
   unpack8(gv, g);
   unpack8(xv, x);
-  if (bn.y) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) g[i] = ((ymask >> i) & 1u) ? g[i] : 0.f;
-  } else if (bn.relu) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) g[i] = (x[i] * L.sc[i] + L.sh[i] > 0.f) ? g[i] : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    L.s1[i] += g[i];
-    L.s2[i] += g[i] * ((x[i] - L.mean[i]) * L.inv[i]);
-  }
+  bn_mask_grad(g, x, ymask, bn.y != nullptr, bn.relu, L.sc, L.sh);
+  bn_bwd_accum(L.s1, L.s2, g, x, L.mean, L.inv);
 }
 // lane -> LDS [wave][pixel group][stat][WCH channels]; the caller syncs and sums groups / pixel waves
 __device__ __forceinline__ void bnfuse_spill(const BnFuseLane& L, float* sB, int wave, int grp, int ngrp, int wch, int ch) {

@@ -1,5 +1,6 @@
 // Argument structs + host launchers of every kernel file except the convolutions (vfs_conv.h), grouped by the .hip file that
-// defines the launchers.  A new launcher goes under its file's heading.
+// defines the launchers.  A new launcher goes under its file's heading.  The BatchNorm arithmetic that several kernel
+// files share (bn_running_update, bn_finalize_channel, ...) is not here: vfs_bn.h.
 #pragma once
 #include "vfs_common.h"
 #include "vfs_p2p.h"
@@ -18,14 +19,6 @@ struct BnActArgs {
   unsigned char* mbits = nullptr;   // optional second output: the bit-packed mask y > 0, [M][C/8] (vfs_common.h mask8_of)
   int wide = 0;         // plain (non-FIN) launch: whole pixel rows per workgroup (set by the launcher, bn.hip slab_geom)
 };
-
-// running = (1 - momentum) * running + momentum * statistic; a NaN statistic (the poison of a failed SyncBN exchange) is kept out
-__device__ __forceinline__ void bn_running_update(float& rm, float& rv, float momentum, double mean, double unbiased) {
-  if (mean != mean || unbiased != unbiased) return;
-  const float keep = 1.f - momentum;
-  rm = __builtin_fmaf(momentum, (float)mean, keep * rm);
-  rv = __builtin_fmaf(momentum, (float)unbiased, keep * rv);
-}
 
 // Optional in-kernel statistics finalisation for the apply passes (bn_act / bn_bwd_apply, SMALL row counts): the
 // workgroup reduces the partial rows of its own (group, channel slab) in its prologue - every workgroup gets the same

@@ -2,6 +2,7 @@
 // gradient wrt the raw stem conv output of one 8-channel vector, rebuilt from the pooled tensors.
 #pragma once
 #include "vfs_ops.h"
+#include "vfs_bn.h"
 
 #define STEM_MAX_GROUPS 8
 #define STEM_TAB (3 * 64)   // per group: A, B, D of dx = A*ga + B*x + D (as bn_bwd_apply_kernel) for 64 channels
@@ -12,12 +13,9 @@ __device__ __forceinline__ void stem_fill_table(const StemBwdArgs& a, float* tab
   for (int i = threadIdx.x; i < ngroups * 64; i += blockDim.x) {
     const int gi = i >> 6, c = i & 63;
     const float* bp = a.bnp + (size_t)gi * 4 * 64 + c;
-    const float A = bp[0], mean = bp[2 * 64], inv = bp[3 * 64];
-    const float m1 = (float)a.sums[((size_t)gi * 2) * 64 + c] * rc, m2 = (float)a.sums[((size_t)gi * 2 + 1) * 64 + c] * rc;
     float* tb = tab + gi * STEM_TAB + c;
-    tb[0] = A;
-    tb[64] = -A * inv * m2;
-    tb[128] = A * (mean * inv * m2 - m1);
+    tb[0] = bp[0];
+    bn_bwd_coefs(bp[0], bp[2 * 64], bp[3 * 64], a.sums[((size_t)gi * 2) * 64 + c], a.sums[((size_t)gi * 2 + 1) * 64 + c], rc, tb[64], tb[128]);
   }
 }
 
