@@ -90,11 +90,7 @@ def im2col64_dil(x, stride, dil):
     return cols.reshape(N, Cin, 9, -1).permute(0, 3, 2, 1).reshape(-1, 9 * Cin)
 
 
-@pytest.mark.parametrize('regime', ['A', 'B'])
-@pytest.mark.parametrize('case', [CASES[0], CASES[2], CASES[3]])
-def test_dilated_backward_exact_operands(backend, case, regime):
-    """every dgrad output is the RNE of the float64 sum (the residual added before the rounding, gated by the mask); every
-    wgrad partial slice is the float64 sum over its pixel range, slices past M all zero; the reduced gradient is exact"""
+def run_dilated_backward_exact_operands(backend, case, regime):
     N, H, W, Cin, Cout, stride, dil = case
     lib, d, dev = backend.lib, backend.d, backend.dev
     g = torch.Generator().manual_seed(N * 100 + H + Cout + dil)
@@ -135,6 +131,14 @@ def test_dilated_backward_exact_operands(backend, case, regime):
         want = (dyq[sl].t() @ cols[sl]).float() if s * pps < M else torch.zeros(Cout, 9 * Cin)
         assert_bits(part[s], want, f'wgrad partial slice {s} of {nsplit} {case} regime {regime}', pixels=False)
     assert_bits(grad, (grad0.double() + oihw(dyq.t() @ cols, Cout, Cin, 3)).float(), f'wgrad {case} regime {regime}', pixels=False)
+
+
+@pytest.mark.parametrize('regime', ['A', 'B'])
+@pytest.mark.parametrize('case', [CASES[0], CASES[2], CASES[3]])
+def test_dilated_backward_exact_operands(backend, case, regime):
+    """every dgrad output is the RNE of the float64 sum (the residual added before the rounding, gated by the mask); every
+    wgrad partial slice is the float64 sum over its pixel range, slices past M all zero; the reduced gradient is exact"""
+    run_dilated_backward_exact_operands(backend, case, regime)
 
 
 GOOD = dict(N=1, H=8, W=8, Cin=64, Ho=8, Wo=8, Cout=64, KH=3, KW=3, stride=1, pad=2, dilation=2)

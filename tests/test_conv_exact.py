@@ -263,17 +263,7 @@ def bn_rows_check(regime, part, gq, xq, mean, mask, linear, what):
             assert_bits(part[:, col].sum(0), val.sum(0), f'{what}: BatchNorm-backward column {col}, total')
 
 
-@pytest.mark.parametrize('regime', REGIMES)
-@pytest.mark.parametrize('N,H,W,Cin,Cout,k', [
-    (2, 8, 16, 128, 64, 1),      # implicit-GEMM dgrad, one 128-channel tile (64-channel waves)
-    (3, 7, 7, 64, 256, 1),       # implicit-GEMM dgrad, 64-channel tile (32-channel waves), DMA ring, ragged M
-    (2, 16, 32, 128, 64, 3),     # halo dgrad, 128 output channels
-    (2, 32, 32, 64, 64, 3),      # halo dgrad, 64 output channels (16x16 tiles)
-    (4, 7, 7, 128, 128, 3),      # halo dgrad on whole 7x7 images
-])
-def test_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout, k):
-    """vfs_conv_dgrad_maskadd, vfs_conv_dgrad_bn (bit-packed mask operand) and vfs_conv_dgrad_bn_maskadd (mask recomputed from
-    x scale + shift) against float64; dyadic BatchNorm parameters, invstd = 1"""
+def run_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout, k):
     lib, d, dev = backend.lib, backend.d, backend.dev
     g = torch.Generator().manual_seed(N * 13 + Cin + k)
     pad = k // 2
@@ -312,6 +302,20 @@ def test_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout,
     assert_bits(dx3, want, 'conv_dgrad_bn_maskadd')
     relu = ((xq * scale.double() + shift.double()) > 0).double()
     bn_rows_check(regime, pb, gq, xq, mean.double(), relu, linear, 'conv_dgrad_bn_maskadd, mask from x scale + shift')
+
+
+@pytest.mark.parametrize('regime', REGIMES)
+@pytest.mark.parametrize('N,H,W,Cin,Cout,k', [
+    (2, 8, 16, 128, 64, 1),      # implicit-GEMM dgrad, 128 produced channels: two 64-channel tiles by default (4 < igemm_narrow_below tiles)
+    (3, 7, 7, 64, 256, 1),       # implicit-GEMM dgrad, 64-channel tile (32-channel waves), DMA ring, ragged M
+    (2, 16, 32, 128, 64, 3),     # halo dgrad, 128 output channels
+    (2, 32, 32, 64, 64, 3),      # halo dgrad, 64 output channels (16x16 tiles)
+    (4, 7, 7, 128, 128, 3),      # halo dgrad on whole 7x7 images
+])
+def test_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout, k):
+    """vfs_conv_dgrad_maskadd, vfs_conv_dgrad_bn (bit-packed mask operand) and vfs_conv_dgrad_bn_maskadd (mask recomputed from
+    x scale + shift) against float64; dyadic BatchNorm parameters, invstd = 1"""
+    run_dgrad_masked_add_and_fused_bn_rows(backend, regime, N, H, W, Cin, Cout, k)
 
 
 # ---------------------------------------------------------------------------------------------- wgrad
@@ -446,9 +450,7 @@ def test_stem(backend, regime):
 
 
 # ---------------------------------------------------------------------------------------------- dilated, split-K
-@pytest.mark.parametrize('regime', REGIMES)
-@pytest.mark.parametrize('N,H,W,Cin,Cout,stride,dil', [(2, 12, 16, 64, 128, 1, 2), (1, 16, 16, 128, 64, 1, 4), (2, 13, 13, 64, 64, 2, 2)])
-def test_dilated_forward(backend, regime, N, H, W, Cin, Cout, stride, dil):
+def run_dilated_forward(backend, regime, N, H, W, Cin, Cout, stride, dil):
     lib, d = backend.lib, backend.d
     g = torch.Generator().manual_seed(N + H + dil)
     Ho, Wo = out_size(H, W, 3, stride, dil, dil)
@@ -463,13 +465,12 @@ def test_dilated_forward(backend, regime, N, H, W, Cin, Cout, stride, dil):
 
 
 @pytest.mark.parametrize('regime', REGIMES)
-@pytest.mark.parametrize('M,Cin,Cout', [(64, 512, 256), (200, 256, 192), (8, 1024, 128),
-                                        (40, 512, 512)])      # ragged M, eight K-steps in both directions
-def test_splitk_equals_plain_kernel_and_float64(backend, regime, M, Cin, Cout):
-    """exact partial tiles: the split-K forward / dgrad must equal the plain kernel element for element, statistics rows
-    included, and both the float64 result; the tickets come back to zero (second launch).  The forward splits on every
-    shape.  The dgrad's K is Cout: the planner splits only from four 64-channel K-steps on, so conv_dgrad_splitk runs on
-    (64, 512, 256) and (40, 512, 512); with Cout = 192 and 128 the plan is one slice and the plain dgrad is all there is."""
+@pytest.mark.parametrize('N,H,W,Cin,Cout,stride,dil', [(2, 12, 16, 64, 128, 1, 2), (1, 16, 16, 128, 64, 1, 4), (2, 13, 13, 64, 64, 2, 2)])
+def test_dilated_forward(backend, regime, N, H, W, Cin, Cout, stride, dil):
+    run_dilated_forward(backend, regime, N, H, W, Cin, Cout, stride, dil)
+
+
+def run_splitk(backend, regime, M, Cin, Cout):
     lib, d, dev = backend.lib, backend.d, backend.dev
     g = torch.Generator().manual_seed(M + Cin)
     x, w, bias, dy, add = operands(regime, g, M, 1, 1, Cin, Cout, 1, 1, 1)
@@ -514,23 +515,19 @@ def test_splitk_equals_plain_kernel_and_float64(backend, regime, M, Cin, Cout):
         assert torch.equal(ws2[:1024].cpu(), torch.zeros(1024))
 
 
-# ---------------------------------------------------------------------------------------------- folded input BatchNorm
 @pytest.mark.parametrize('regime', REGIMES)
-@pytest.mark.parametrize('N,H,W,Cin,Cout,G,k', [
-    (2, 16, 32, 128, 128, 2, 3),     # 8x16 tiles, two channel chunks, two groups
-    (2, 32, 32, 64, 64, 2, 3),       # 16x16 tiles (64 output channels)
-    (4, 8, 8, 64, 128, 2, 3),        # whole 8x8 images, two per tile
-    (2, 14, 14, 64, 128, 2, 3),      # ragged 8x16 tiles
-    (4, 7, 7, 64, 128, 2, 3),        # whole 7x7 images, two per tile
-    (2, 28, 28, 64, 64, 1, 3),       # ragged 16x16 tiles (forward) / 8x16 tiles (weight gradient)
-    (2, 8, 16, 64, 256, 2, 1),       # 1x1: one K-step (the single-buffer pipeline), 128-channel tiles, two groups
-    (4, 8, 8, 128, 512, 2, 1),       # 1x1: two K-steps, two groups of 128 pixels
-    (2, 16, 16, 256, 128, 1, 1),     # 1x1: four K-steps
-    (2, 8, 8, 64, 64, 1, 1),         # 1x1: 64-channel tile
-])
-def test_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
-    """vfs_conv_fwd_bnin / vfs_conv_wgrad_bnin (/ vfs_conv_wgrad_inl with the fold, 3x3) against float64 on
-    relu(raw scale + shift): even-integer raw values, scale in {1/2, 1}, integer shift, per group"""
+@pytest.mark.parametrize('M,Cin,Cout', [(64, 512, 256), (200, 256, 192), (8, 1024, 128),
+                                        (40, 512, 512)])      # ragged M, eight K-steps in both directions
+def test_splitk_equals_plain_kernel_and_float64(backend, regime, M, Cin, Cout):
+    """exact partial tiles: the split-K forward / dgrad must equal the plain kernel element for element, statistics rows
+    included, and both the float64 result; the tickets come back to zero (second launch).  The forward splits on every
+    shape.  The dgrad's K is Cout: the planner splits only from four 64-channel K-steps on, so conv_dgrad_splitk runs on
+    (64, 512, 256) and (40, 512, 512); with Cout = 192 and 128 the plan is one slice and the plain dgrad is all there is."""
+    run_splitk(backend, regime, M, Cin, Cout)
+
+
+# ---------------------------------------------------------------------------------------------- folded input BatchNorm
+def run_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
     lib, d, dev = backend.lib, backend.d, backend.dev
     g = torch.Generator().manual_seed(N + H + Cin + k)
     pad = k // 2
@@ -577,6 +574,25 @@ def test_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
         lib.conv_wgrad_inl(d(nhwc(dy)), rawd, bnpd, npg, wsi, grad, tickets, N, H, W, Cin, H, W, Cout, 3, 3, 1, 1, nsplit, pps, None)
         assert_bits(grad, wantg, 'conv_wgrad_inl with the folded input BatchNorm', pixels=False)
         assert int(tickets.cpu().abs().sum()) == 0
+
+
+@pytest.mark.parametrize('regime', REGIMES)
+@pytest.mark.parametrize('N,H,W,Cin,Cout,G,k', [
+    (2, 16, 32, 128, 128, 2, 3),     # 8x16 tiles, two channel chunks, two groups
+    (2, 32, 32, 64, 64, 2, 3),       # 16x16 tiles (64 output channels)
+    (4, 8, 8, 64, 128, 2, 3),        # whole 8x8 images, two per tile
+    (2, 14, 14, 64, 128, 2, 3),      # ragged 8x16 tiles
+    (4, 7, 7, 64, 128, 2, 3),        # whole 7x7 images, two per tile
+    (2, 28, 28, 64, 64, 1, 3),       # ragged 16x16 tiles (forward) / 8x16 tiles (weight gradient)
+    (2, 8, 16, 64, 256, 2, 1),       # 1x1: one K-step (the single-buffer pipeline), four 64-channel tiles by default, two groups
+    (4, 8, 8, 128, 512, 2, 1),       # 1x1: two K-steps, two groups of 128 pixels
+    (2, 16, 16, 256, 128, 1, 1),     # 1x1: four K-steps
+    (2, 8, 8, 64, 64, 1, 1),         # 1x1: 64-channel tile
+])
+def test_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k):
+    """vfs_conv_fwd_bnin / vfs_conv_wgrad_bnin (/ vfs_conv_wgrad_inl with the fold, 3x3) against float64 on
+    relu(raw scale + shift): even-integer raw values, scale in {1/2, 1}, integer shift, per group"""
+    run_folded_input_batchnorm(backend, regime, N, H, W, Cin, Cout, G, k)
 
 
 # ---------------------------------------------------------------------------------------------- opt-in pointwise kernels
@@ -674,11 +690,7 @@ def tie_block(K, N=3, H=7, W=7, C=256):
     return xm.reshape(N, H, W, K).permute(0, 3, 1, 2).contiguous(), w.reshape(C, K, 1, 1), ref
 
 
-@pytest.mark.parametrize('K', [64, 256])        # one K-step; four K-steps (the DMA-ring variant)
-@pytest.mark.parametrize('half', [0.0, 0.5, -0.5])
-def test_tie_block(backend, K, half):
-    """every output an exact tie (half = 0): RNE alone passes.  half = +-0.5 as bias (forward) / residual (dgrad): no ties
-    any more - the fp32 add must happen before the rounding (257 + 0.5 -> 258, rne(257) + 0.5 -> 256)"""
+def run_tie_block(backend, K, half):
     lib, d, dev = backend.lib, backend.d, backend.dev
     N, H, W, C = 3, 7, 7, 256
     x, w, ref = tie_block(K)
@@ -695,6 +707,14 @@ def test_tie_block(backend, K, half):
     add = d(torch.full((N, H, W, C), half, dtype=BF16)) if half else None
     lib.conv_dgrad(d(nhwc(x)), wd, dx, add, N, H, W, C, H, W, K, 1, 1, 1, 0, None)
     assert_bits(dx, want, f'tie block dgrad, residual {half}')
+
+
+@pytest.mark.parametrize('K', [64, 256])        # one K-step; four K-steps (the DMA-ring variant)
+@pytest.mark.parametrize('half', [0.0, 0.5, -0.5])
+def test_tie_block(backend, K, half):
+    """every output an exact tie (half = 0): RNE alone passes.  half = +-0.5 as bias (forward) / residual (dgrad): no ties
+    any more - the fp32 add must happen before the rounding (257 + 0.5 -> 258, rne(257) + 0.5 -> 256)"""
+    run_tie_block(backend, K, half)
 
 
 # ---------------------------------------------------------------------------------------------- self-check of the comparison

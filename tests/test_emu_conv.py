@@ -92,9 +92,9 @@ CASES = [  # N, H, W, Cin, Cout, k, stride, pad
     (3, 7, 7, 128, 64, 1, 1, 0),
     (2, 8, 8, 64, 128, 1, 2, 0),
     (2, 8, 8, 64, 64, 1, 1, 0),       # one K-step (Ktot == 64): single-buffer variant, 64-channel tile
-    (1, 12, 12, 64, 256, 1, 1, 0),    # one K-step, two 128-channel tiles, ragged M = 144
+    (1, 12, 12, 64, 256, 1, 1, 0),    # one K-step, Cout = 256 (four 64-channel tiles by default: few tiles), ragged M = 144
     (3, 7, 7, 512, 64, 1, 1, 0),      # DMA-ring variant (1x1, K >= 256): 8 K-steps, 64-channel tile, ragged M = 147
-    (2, 8, 8, 256, 256, 1, 1, 0),     # DMA-ring variant: 4 K-steps forward and dgrad, two 128-channel tiles
+    (2, 8, 8, 256, 256, 1, 1, 0),     # DMA-ring variant: 4 K-steps forward and dgrad, Cout = 256 (four 64-channel tiles by default)
     (1, 5, 5, 320, 128, 1, 1, 0),     # DMA-ring variant: odd number of K-steps (5), one ragged tile
     (2, 9, 11, 64, 64, 3, 2, 1),      # odd sizes: unequal parity classes in the stride-2 dgrad
     (1, 16, 32, 128, 64, 3, 1, 1),    # halo-tile kernel: 8x16 spatial tiles, two channel chunks
@@ -113,7 +113,7 @@ CASES = [  # N, H, W, Cin, Cout, k, stride, pad
 @pytest.mark.parametrize('N,H,W,Cin,Cout,k,stride', [
     (3, 7, 7, 512, 64, 1, 1),       # DMA ring, ragged M = 147 (rows past M are computed from a re-fetched row)
     (2, 2, 2, 1024, 256, 1, 1),     # DMA ring, 8 rows only (ResNet-50 layer4 on a 64 x 64 input)
-    (1, 12, 12, 64, 256, 1, 1),     # one K-step, two 128-channel tiles, ragged M = 144
+    (1, 12, 12, 64, 256, 1, 1),     # one K-step, Cout = 256 (four 64-channel tiles by default), ragged M = 144
     (3, 7, 7, 128, 72, 1, 1),       # ragged channel tile (72 = 64 + 8)
     (2, 9, 11, 64, 64, 3, 2),       # 3x3 stride 2 through the implicit-GEMM kernel
 ])
@@ -307,7 +307,7 @@ def test_dgrad_fused_bn_backward_statistics(backend, N, H, W, Cin, Cout, k, G, m
 
 
 @pytest.mark.parametrize('N,H,W,Cin,Cout,k', [
-    (2, 8, 16, 128, 64, 1),      # implicit-GEMM dgrad, one 128-channel tile (64-channel waves)
+    (2, 8, 16, 128, 64, 1),      # implicit-GEMM dgrad, 128 produced channels: two 64-channel tiles by default
     (3, 7, 7, 64, 256, 1),       # implicit-GEMM dgrad, 64-channel tile (32-channel waves), DMA ring, ragged M
     (2, 16, 32, 128, 64, 3),     # halo dgrad, 128 output channels
     (2, 32, 32, 64, 64, 3),      # halo dgrad, 64 output channels (16x16 tiles)
@@ -394,7 +394,7 @@ def test_conv_with_folded_input_batchnorm(backend, N, H, W, Cin, Cout, G):
 
 
 @pytest.mark.parametrize('N,H,W,Cin,Cout,G', [
-    (2, 8, 16, 64, 256, 2),       # one K-step (the single-buffer pipeline), 128-channel tiles, two groups
+    (2, 8, 16, 64, 256, 2),       # one K-step (the single-buffer pipeline), four 64-channel tiles by default, two groups
     (4, 8, 8, 128, 512, 2),       # two K-steps, two groups of 128 pixels
     (2, 16, 16, 256, 128, 1),     # four K-steps on the double-buffer pipeline
     (2, 8, 8, 64, 64, 1),         # 64-channel tile
@@ -656,7 +656,7 @@ def test_halo_deep_schedule_matches_two_stage(backend, N, H, W, Cin, Cout):
 
 
 @pytest.mark.parametrize('N,H,W,Cin,Cout,k,L', [
-    (4, 16, 32, 64, 128, 1, 2),       # implicit-GEMM kernel: 16 rows, groups of 4, one 128-channel tile
+    (4, 16, 32, 64, 128, 1, 2),       # implicit-GEMM kernel: 16 rows, groups of 4, Cout = 128 (two 64-channel tiles by default)
     (3, 16, 16, 64, 192, 1, 1),       # 6 rows in groups of 2, three 64-channel tiles
     (5, 16, 16, 128, 64, 1, 3),       # 10 rows, groups of 8: the last group holds two rows
     (4, 16, 32, 64, 128, 3, 2),       # halo kernel, 8x16 tiles (one row per workgroup): 16 rows, groups of 4

@@ -234,19 +234,19 @@ OPTION_DEFAULTS = dict(
     halo=1, halo_min_fill=70, halo_deep_max=256, halo_xcd=1, stem_direct=1, stem_blocks=0,
     bn_ticket=1, bn_chunk_rows=64, bn_wide=1, bn_wide_min_mb=8,
     igemm_bc=0, igemm_xcd=1, igemm_mfma_stats=1, igemm_narrow_below=513, igemm_onek=3, igemm_ring_tiles=512, igemm_ring_fbn=1,
-    igemm_ring_mfma32=1, igemm_ring_gather=0, igemm_ring_upfront=0, igemm_skinny=1, igemm_pw=0, igemm_pw_min_tiles=192,
+    igemm_ring_mfma32=1, igemm_ring_gather=0, igemm_ring_upfront=0, igemm_ds_quarter=1, igemm_skinny=1, igemm_pw=0, igemm_pw_min_tiles=192,
     wgrad_lin=1, wgrad_lin2=1, wgrad_ring=1, wgrad_xcd=1,
     lpx_target=0, lpx_wgs=0, lpx_minb=4, lp2=1, lp2_fpb=0, lp2_trim=1, lp2_xcd=-1, lp2_dbg=0, lp2_cap=0,
     conv_f32_variant=0, conv_f32_dbg=0)
 
 
 def test_option_switchboard_names_defaults_and_setters():
-    """vfs_set_option: each of the 38 names is accepted and writes the global `vfs_option_<name>` (set to its default here, so
+    """vfs_set_option: each of the 39 names is accepted and writes the global `vfs_option_<name>` (set to its default here, so
     nothing leaks into other tests), the two normalising setters keep their rules, an unknown name is an argument error"""
     import ctypes
     from tests.emu_util import emu_lib
     lib = emu_lib()
-    assert len(OPTION_DEFAULTS) == 38
+    assert len(OPTION_DEFAULTS) == 39
     var = lambda name: ctypes.c_int.in_dll(lib.dll, 'vfs_option_' + name).value
     for name, default in OPTION_DEFAULTS.items():
         lib.set_option(name.encode(), default)
