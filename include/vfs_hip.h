@@ -580,6 +580,42 @@ int vfs_bilinear_resize_f32(const float* src, float* dst, int C, int H, int W, i
 /* vfs_seg_postprocess with every step a single fp32 operation (no contraction) */
 int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                               vfs_stream_t stream);
+/* ---- label propagation of a BATCH of videos in lock-step (VanillaTracker.forward_test_batch) ----
+ * Up to 64 slots of one frame size advance together: one call of vfs_labelprop_f32_batch / vfs_labelprop_f32_2pass_batch is one
+ * propagation step of EVERY slot in the launches one video takes (the grids carry a slot dimension), each slot at its own query
+ * frame with its own key list and class count, and every slot's output has the bits of the single-video call.
+ *   banks     fbank [nslots][Tcap][H*W][C] fp32, hlbank [nslots][Tcap][H*W][2C] (vfs_split_rows_bf16x2 of fbank),
+ *             sbank [nslots][Tcap][H*W][COcap] fp32: slot n starts at n * Tcap * H*W * COcap and holds its label rows PACKED with
+ *             its own class count, [frame][H*W][CO_n].  The output of a step is frame `qframe` of the slot's label rows.
+ *   desc      device pointer to the rows of THIS step, int32 [nslots][VFS_LPB_DESC_INTS]: [0] active (0: the slot's workgroups
+ *             leave at once, nothing of the slot is read or written), [1] qframe, [2] nkeys, [3] non_mask_len, [4] CO_n,
+ *             [5..7] reserved (0), [8..71] key frames (frame indices inside the slot, reference order).  A caller that knows every
+ *             clip's length writes the rows of all steps once ([steps][nslots][VFS_LPB_DESC_INTS]) and passes row block `step`:
+ *             nothing is copied to the device inside the step loop.  A row outside the single-video ranges (qframe / key frames
+ *             < Tcap, 1 <= nkeys <= max_nkeys, 0 <= non_mask_len < nkeys, 1 <= CO_n <= COcap) is treated as inactive.
+ *   host side nactive = active rows of this step (the key-frame splits are chosen for that many videos sharing the chip),
+ *             max_nkeys >= every active row's nkeys (sizes the grids).
+ *   workspace per slot, as the single-video calls: vfs_labelprop_f32_batch_workspace_bytes(H, W, nslots);
+ *             vfs_labelprop_f32_2pass_batch_workspace_bytes(H, W, entries_per_query, nslots) (0 = the full list capacity) =
+ *             256 bytes of per-slot overflow words (int32 [nslots]: 1 = the slot's lists overflowed and the dense kernels redid THAT
+ *             slot, decided on the device; the other slots are not touched) + nslots regions in the single-video layout.
+ *   vfs_labelprop_f32_2pass_batch runs the dense kernels for every slot when hlbank = NULL, unit_rows = 0 or C is not 256 / 512 / 1024.
+ * vfs_seg_postprocess_exact_batch / vfs_bilinear_resize_f32_batch: the per-step post-processing of every active slot in one launch
+ * set, from frame qframe of the slot's label rows into frame qframe of preds: uint8 [nslots][Tcap][Ho*Wo] label maps (partial: fp32
+ * [nslots][64][COcap][2]), or fp32 soft maps, slot n at n * Tcap * COcap * Ho*Wo holding [frame][CO_n][Ho][Wo] packed. */
+#define VFS_LPB_DESC_INTS 72
+int vfs_labelprop_f32_batch_workspace_bytes(int H, int W, int nslots, long long* bytes);
+int vfs_labelprop_f32_batch(const float* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots,
+                            int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk,
+                            float temperature, vfs_stream_t stream);
+int vfs_labelprop_f32_2pass_batch_workspace_bytes(int H, int W, int entries_per_query, int nslots, long long* bytes);
+int vfs_labelprop_f32_2pass_batch(const float* fbank, const vfs_bf16* hlbank, float* sbank, void* workspace, long long workspace_bytes,
+                                  const int* desc, int nslots, int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap,
+                                  int radius, int topk, float temperature, int unit_rows, vfs_stream_t stream);
+int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H,
+                                    int W, int COcap, int Ho, int Wo, vfs_stream_t stream);
+int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap,
+                                  int Ho, int Wo, vfs_stream_t stream);
 
 /* ---- DAVIS-2017 semi-supervised J&F (datasets/davis_dataset.py:68-140 -> davis2017.evaluation) -----
  * pred / gt: uint8 label maps [T][H][W]; frames 1..T-2 are evaluated (first = given, last excluded);

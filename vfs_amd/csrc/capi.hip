@@ -998,6 +998,89 @@ int vfs_labelprop_f32_2pass(const float* fbank, const vfs_bf16* hlbank, const fl
   a.run_flag = p.flags;
   return vfs_labelprop_f32_launch(a, stream_of(stream));
 }
+// ---- a batch of videos in lock-step: one call = one step of every slot (include/vfs_hip.h: banks, descriptor rows, workspace) ----
+static long long lpb_round(long long bytes) { return (bytes + 255) / 256 * 256; }
+static int lpb_check(const char* who, const void* fbank, const void* sbank, const void* workspace, const int* desc, int nslots, int nactive,
+                     int max_nkeys, int Tcap, int H, int W, int C, int COcap, int topk) {
+  if (H < 1 || W < 1 || C < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1) return fail(VFS_ERR_SHAPE, who, "H, W, C, Tcap >= 1, 1 <= COcap <= 256");
+  if (nslots < 1 || nslots > LPB_MAX_SLOTS || nactive < 0 || nactive > nslots) return fail(VFS_ERR_SHAPE, who, "1 <= nslots <= 64, 0 <= nactive <= nslots");
+  if (max_nkeys < 1 || max_nkeys > LP_MAX_KEYS) return fail(VFS_ERR_SHAPE, who, "1 <= max_nkeys <= 64");
+  if (topk < 1 || topk > 10) return fail(VFS_ERR_SHAPE, who, "1 <= topk <= 10");
+  if (!fbank || !sbank || !workspace || !desc) return fail(VFS_ERR_ARG, who, "null buffer");
+  return VFS_OK;
+}
+static LpBatchArgs lpb_args(const float* fbank, const vfs_bf16* hl, float* sbank, char* ws, long long ws_stride, int* flags, const int* desc,
+                            int nslots, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk, float temperature) {
+  LpBatchArgs b{};
+  b.fbank = fbank; b.hl = hl; b.sbank = sbank; b.ws = ws; b.ws_stride = ws_stride; b.flags = flags; b.desc = desc;
+  b.nslots = nslots; b.max_nkeys = max_nkeys; b.Tcap = Tcap; b.H = H; b.W = W; b.C = C; b.COcap = COcap;
+  b.radius = radius; b.topk = topk; b.temperature = temperature;
+  return b;
+}
+int vfs_labelprop_f32_batch_workspace_bytes(int H, int W, int nslots, long long* bytes) {
+  if (!bytes || H <= 0 || W <= 0 || nslots < 1 || nslots > LPB_MAX_SLOTS)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_batch_workspace_bytes: bad argument");
+  *bytes = nslots * lpb_round(lp_workspace_need(H, W));
+  return VFS_OK;
+}
+int vfs_labelprop_f32_batch(const float* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots,
+                            int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk, float temperature,
+                            vfs_stream_t stream) {
+  if (int rc = lpb_check("labelprop_f32_batch", fbank, sbank, workspace, desc, nslots, nactive, max_nkeys, Tcap, H, W, C, COcap, topk)) return rc;
+  const long long stride = lpb_round(lp_workspace_need(H, W));
+  if (workspace_bytes < nslots * stride)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_batch: workspace smaller than vfs_labelprop_f32_batch_workspace_bytes(H, W, nslots)");
+  if (nactive == 0) return VFS_OK;
+  const LpBatchArgs b = lpb_args(fbank, nullptr, sbank, (char*)workspace, stride, nullptr, desc, nslots, max_nkeys, Tcap, H, W, C, COcap, radius,
+                                 topk, temperature);
+  return vfs_labelprop_f32_batch_launch(b, nactive, stream_of(stream));
+}
+int vfs_labelprop_f32_2pass_batch_workspace_bytes(int H, int W, int entries_per_query, int nslots, long long* bytes) {
+  long long one = 0;
+  if (!bytes || nslots < 1 || nslots > LPB_MAX_SLOTS ||
+      vfs_labelprop_f32_2pass_workspace_bytes_for(H, W, entries_per_query > 0 ? entries_per_query : LP2_MAX_SPLIT * LP2_MAX_CAP, &one) != VFS_OK)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch_workspace_bytes: bad argument (0 or at least 16 list entries per query, 1 <= nslots <= 64)");
+  *bytes = LPB_FLAG_BYTES + nslots * lpb_round(one);
+  return VFS_OK;
+}
+int vfs_labelprop_f32_2pass_batch(const float* fbank, const vfs_bf16* hlbank, float* sbank, void* workspace, long long workspace_bytes,
+                                  const int* desc, int nslots, int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius,
+                                  int topk, float temperature, int unit_rows, vfs_stream_t stream) {
+  if (int rc = lpb_check("labelprop_f32_2pass_batch", fbank, sbank, workspace, desc, nslots, nactive, max_nkeys, Tcap, H, W, C, COcap, topk)) return rc;
+  long long need = 0, dense = 0;
+  if (vfs_labelprop_f32_2pass_batch_workspace_bytes(H, W, 16, nslots, &need) != VFS_OK || vfs_labelprop_workspace_bytes(H, W, &dense) != VFS_OK ||
+      workspace_bytes < need)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch: workspace smaller than vfs_labelprop_f32_2pass_batch_workspace_bytes(H, W, 16, nslots)");
+  if (nactive == 0) return VFS_OK;
+  // [overflow words of the slots][slot 0: the single-video layout][slot 1] ...; the list capacity follows the bytes per slot
+  const long long stride = (workspace_bytes - LPB_FLAG_BYTES) / nslots / 256 * 256;
+  char* ws = (char*)workspace + LPB_FLAG_BYTES;
+  LpBatchArgs b = lpb_args(fbank, hlbank, sbank, ws, stride, nullptr, desc, nslots, max_nkeys, Tcap, H, W, C, COcap, radius, topk, temperature);
+  if (!hlbank || !unit_rows || !vfs_lp2_eligible(C) || (long long)H * W >= (1 << 21))      // as vfs_labelprop_f32_2pass: the dense kernels
+    return vfs_labelprop_f32_batch_launch(b, nactive, stream_of(stream));
+  const long long entries = (stride - dense - lp2_counts_bytes(H, W) - 16) / ((long long)H * W * 8);
+  b.entries = (int)(entries > LP2_MAX_SPLIT * LP2_MAX_CAP ? LP2_MAX_SPLIT * LP2_MAX_CAP : entries);
+  b.lists_bytes = lp2_lists_bytes(H, W, b.entries);
+  b.flags = (int*)workspace;
+  if (int rc = vfs_labelprop_f32_2pass_batch_launch(b, nactive, stream_of(stream))) return rc;
+  // the dense kernels behind them: a slot whose lists overflowed is redone, the workgroups of the others leave at once
+  return vfs_labelprop_f32_batch_launch(b, nactive, stream_of(stream));
+}
+int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                                    int COcap, int Ho, int Wo, vfs_stream_t stream) {
+  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
+    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: H, W, Ho, Wo, Tcap >= 1, 1 <= classes <= 256, 1 <= nslots <= 64");
+  if ((long long)Ho * Wo > 0x7fffffff - 255 || (long long)H * W * COcap > 0x7fffffff)
+    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: Ho * Wo and H * W * classes must fit an int");
+  if (!sbank || !partial || !preds || !desc) return vfs_set_error(VFS_ERR_ARG, "seg_postprocess_exact_batch: null buffer");
+  return vfs_seg_postprocess_exact_batch_launch(sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+}
+int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
+                                  int Wo, vfs_stream_t stream) {
+  if (Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS) return vfs_set_error(VFS_ERR_SHAPE, "bilinear_resize_f32_batch: Tcap >= 1, 1 <= nslots <= 64");
+  if (!sbank || !preds || !desc) return vfs_set_error(VFS_ERR_ARG, "bilinear_resize_f32_batch: null buffer");
+  return vfs_bilinear_resize_f32_batch_launch(sbank, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+}
 int vfs_bilinear_resize_f32(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
                             vfs_stream_t stream) {
   if (!src || !dst) return vfs_set_error(VFS_ERR_ARG, "bilinear_resize_f32: null buffer");

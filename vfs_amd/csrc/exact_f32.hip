@@ -495,6 +495,7 @@ int vfs_l2norm_rows_f32_launch(const float* x, float* y, long long P, int C, hip
 }
 
 #include "vfs_lpx.h"
+#include "vfs_lpb.h"
 
 // one workgroup = an 8x8 tile of queries x the key frames [f_begin, f_end) of its split; per key frame only the
 // (8 + 2(r-1))^2 window that can lie inside the circle, 64 keys per block, channels in stages of 32.
@@ -503,8 +504,9 @@ int vfs_l2norm_rows_f32_launch(const float* x, float* y, long long P, int C, hip
 // RAGGED = C % 32 != 0: the last channel stage is zero-filled lane by lane.  Otherwise every load is UNCONDITIONAL - rows past the
 // window / the map read a clamped (valid) row and their scores are masked below: the exec-mask branches and zero fills around
 // predicated loads cost 12-16 % of the stage loop (tools/probe_lp_stage.hip, V0 vs V2 at equal occupancy)
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void labelprop_f32_kernel(LabelPropF32Args a, int nsub) {
+// ny = the (key-frame split, sub-split) workgroups per tile of THIS video (one video: gridDim.y)
+template <bool RAGGED, class A>
+__device__ __forceinline__ void labelprop_f32_body(const A& a, int nsub, int ny) {
   constexpr int BQ = 64, BKEY = 64, BC = 32;
   if (a.run_flag && *a.run_flag == 0) return;      // fallback launch of the two-pass path (labelprop2.hip): nothing overflowed
   __shared__ __attribute__((aligned(16))) float sK[BC / 2][BKEY][2];
@@ -553,7 +555,7 @@ __global__ __launch_bounds__(256) void labelprop_f32_kernel(LabelPropF32Args a, 
   };
 
   // blockIdx.y = (key-frame split, sub-split): the 64-key blocks of a frame's window are dealt to nsub workgroups in contiguous runs
-  const int nfs = (int)gridDim.y / nsub, fs = (int)blockIdx.y / nsub, sub = (int)blockIdx.y - fs * nsub;
+  const int nfs = ny / nsub, fs = (int)blockIdx.y / nsub, sub = (int)blockIdx.y - fs * nsub;
   const int fpb = (a.nkeys + nfs - 1) / nfs;
   const int f_begin = fs * fpb, f_end = min(a.nkeys, f_begin + fpb);
   for (int f = f_begin; f < f_end; ++f) {
@@ -669,7 +671,8 @@ __global__ __launch_bounds__(256) void labelprop_f32_kernel(LabelPropF32Args a, 
 }
 
 // merge the per-split lists (same total order), softmax over the top-k in sorted order, weighted sum of the values
-__global__ __launch_bounds__(256) void labelprop_f32_merge_kernel(LabelPropF32Args a, int nsplit) {
+template <class A>
+__device__ __forceinline__ void labelprop_f32_merge_body(const A& a, int nsplit) {
   const int HW = a.H * a.W;
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= HW) return;
@@ -707,6 +710,64 @@ __global__ __launch_bounds__(256) void labelprop_f32_merge_kernel(LabelPropF32Ar
   }
 }
 
+// ---- the kernels: one video, or slot blockIdx.z of a lock-step batch (arguments built from the slot's descriptor row, as labelprop2.hip)
+struct LabelPropF32SlotArgs {      // LabelPropF32Args of one slot; the key list stays in the table
+  const float* fbank; const float* sbank; float* out; float* pval; int* pidx;
+  int qframe, nkeys;
+  const int* kslot;
+  int H, W, C, CO, radius, topk, non_mask_len;
+  float temperature;
+  const int* run_flag;
+};
+__device__ __forceinline__ bool lpx_slot_args(const LpBatchArgs& b, LabelPropF32SlotArgs& a, int& ny, int& nsub) {
+  const int n = blockIdx.z;
+  if (b.flags && b.flags[n] == 0) return false;      // fallback launch of the two-pass path: this slot did not overflow
+  LpbRow r;
+  if (!lpb_row(b.desc, n, b.Tcap, b.max_nkeys, b.COcap, b.radius, r)) return false;
+  const size_t HW = (size_t)b.H * b.W, frames = (size_t)n * b.Tcap * HW;
+  a.fbank = b.fbank + frames * b.C;
+  float* sb = b.sbank + frames * b.COcap;
+  a.sbank = sb;
+  a.out = sb + (size_t)r.qframe * HW * r.CO;
+  a.pval = reinterpret_cast<float*>(b.ws + (size_t)n * b.ws_stride);
+  a.pidx = reinterpret_cast<int*>(a.pval + (size_t)LP_MAX_SPLIT * HW * LPX_TOPK);
+  a.qframe = r.qframe; a.nkeys = r.nkeys; a.kslot = r.kslot;
+  a.H = b.H; a.W = b.W; a.C = b.C; a.CO = r.CO; a.radius = b.radius; a.topk = b.topk; a.non_mask_len = r.non_mask_len;
+  a.temperature = b.temperature;
+  a.run_flag = nullptr;      // (decided above)
+  ny = lpx_splits_for(r.nkeys, ((b.H + 7) >> 3) * ((b.W + 7) >> 3), b.target, b.wgs, b.minb, b.H, b.W, b.radius, &nsub);
+  return true;
+}
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void labelprop_f32_kernel(LabelPropF32Args a, int nsub) { labelprop_f32_body<RAGGED>(a, nsub, (int)gridDim.y); }
+__global__ __launch_bounds__(256) void labelprop_f32_merge_kernel(LabelPropF32Args a, int nsplit) { labelprop_f32_merge_body(a, nsplit); }
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void labelprop_f32_batch_kernel(LpBatchArgs b) {
+  LabelPropF32SlotArgs a;
+  int ny, nsub;
+  if (!lpx_slot_args(b, a, ny, nsub) || (int)blockIdx.y >= ny) return;      // the grid is sized for the slot with the most splits
+  labelprop_f32_body<RAGGED>(a, nsub, ny);
+}
+__global__ __launch_bounds__(256) void labelprop_f32_merge_batch_kernel(LpBatchArgs b) {
+  LabelPropF32SlotArgs a;
+  int ny, nsub;
+  if (lpx_slot_args(b, a, ny, nsub)) labelprop_f32_merge_body(a, ny);
+}
+
+// workgroups wanted per launch and video (the key-frame splits and the sub-splits of a window follow from them: lpx_splits_for)
+static void lpx_targets(int C, int nactive, int* target, int* wgs) {
+  // long channel loops (ResNet-50 res4: C = 1024) balance better with one or two key frames per workgroup (A/B on MI355X:
+  // 5.22 -> 5.05 ms per frame), short ones (ResNet-18: C = 256) with fewer, longer workgroups (1.46 vs 1.51)
+  *target = vfs_option_lpx_target > 0 ? vfs_option_lpx_target : (C >= 512 ? 2400 : 768);
+  // a workgroup of one key frame runs ~1 ms (R50, radius 18) and a launch has only 1-3 of them per slot (the first frames of
+  // a clip: fewer workgroups than CUs): the window's 64-key blocks are dealt to nsub workgroups as well
+  *wgs = vfs_option_lpx_wgs > 0 ? vfs_option_lpx_wgs : (vfs_option_lpx_wgs == 0 && C >= 512 ? 3072 : 0);
+  if (nactive > 1) {      // the slots of a lock-step batch share the chip
+    *target = (*target + nactive - 1) / nactive;
+    if (*wgs > 0) *wgs = (*wgs + nactive - 1) / nactive;
+  }
+}
+
 int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
   if (a.C % 4) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: C % 4");
   if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: 1 <= nkeys <= 64");
@@ -716,26 +777,9 @@ int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
   if (!(a.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: temperature > 0");
   if (a.pval == nullptr || a.pidx == nullptr) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: partial workspace missing");
   const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
-  // long channel loops (ResNet-50 res4: C = 1024) balance better with one or two key frames per workgroup (A/B on MI355X:
-  // 5.22 -> 5.05 ms per frame), short ones (ResNet-18: C = 256) with fewer, longer workgroups (1.46 vs 1.51)
-  const int target = vfs_option_lpx_target > 0 ? vfs_option_lpx_target : (a.C >= 512 ? 2400 : 768);
-  int nsplit = (target + tiles - 1) / tiles;
-  if (nsplit > a.nkeys) nsplit = a.nkeys;
-  if (nsplit > LP_MAX_FSPLIT) nsplit = LP_MAX_FSPLIT;
-  const int fpb = (a.nkeys + nsplit - 1) / nsplit;
-  nsplit = (a.nkeys + fpb - 1) / fpb;
-  // a workgroup of one key frame runs ~1 ms (R50, radius 18) and a launch has only 1-3 of them per slot (the first frames of
-  // a clip: fewer workgroups than CUs): the window's 64-key blocks are dealt to nsub workgroups as well
-  int nsub = 1;
-  const int wgs = vfs_option_lpx_wgs > 0 ? vfs_option_lpx_wgs : (vfs_option_lpx_wgs == 0 && a.C >= 512 ? 3072 : 0);
-  if (wgs > 0) {
-    const int wh = a.radius > 0 ? min(a.H, 8 + 2 * (a.radius - 1)) : a.H, ww = a.radius > 0 ? min(a.W, 8 + 2 * (a.radius - 1)) : a.W;
-    const int blocks = (wh * ww + 63) / 64;
-    nsub = (wgs + tiles * nsplit - 1) / (tiles * nsplit);
-    nsub = min(nsub, max(1, blocks / max(1, vfs_option_lpx_minb)));
-    nsub = max(1, min(nsub, LP_MAX_SPLIT / nsplit));
-  }
-  nsplit *= nsub;
+  int target, wgs, nsub;
+  lpx_targets(a.C, 1, &target, &wgs);
+  const int nsplit = lpx_splits_for(a.nkeys, tiles, target, wgs, vfs_option_lpx_minb, a.H, a.W, a.radius, &nsub);
   if (a.C % 32)
     hipLaunchKernelGGL(labelprop_f32_kernel<true>, dim3(tiles, nsplit), dim3(256), 0, s, a, nsub);
   else
@@ -744,6 +788,29 @@ int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
   if (rc) return rc;
   hipLaunchKernelGGL(labelprop_f32_merge_kernel, dim3((a.H * a.W + 255) / 256), dim3(256), 0, s, a, nsplit);
   return vfs_check_launch("labelprop_f32_merge");
+}
+
+// every slot of one lock-step: the two launches of one video.  b.flags given: the fallback of the two-pass path, per slot
+int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
+  if (b.C % 4) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: C % 4");
+  if (b.topk < 1 || b.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: 1 <= topk <= 10");
+  if (b.H >= 32768 || b.W >= 65536 || (long long)b.max_nkeys * b.H * b.W >= 0x7fffffffLL)
+    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: map too large for the packed candidate ids");
+  if (!(b.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_batch: temperature > 0");
+  const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8);
+  lpx_targets(b.C, nactive, &b.target, &b.wgs);
+  b.minb = vfs_option_lpx_minb;
+  int most = 1, nsub;
+  for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lpx_splits_for(nk, tiles, b.target, b.wgs, b.minb, b.H, b.W, b.radius, &nsub));
+  const dim3 grid(tiles, most, b.nslots);
+  if (b.C % 32)
+    hipLaunchKernelGGL(labelprop_f32_batch_kernel<true>, grid, dim3(256), 0, s, b);
+  else
+    hipLaunchKernelGGL(labelprop_f32_batch_kernel<false>, grid, dim3(256), 0, s, b);
+  int rc = vfs_check_launch("labelprop_f32_batch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(labelprop_f32_merge_batch_kernel, dim3((b.H * b.W + 255) / 256, 1, b.nslots), dim3(256), 0, s, b);
+  return vfs_check_launch("labelprop_f32_merge_batch");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -764,8 +831,8 @@ __device__ __forceinline__ float bilerp_exact(const float* __restrict__ seg, int
 
 // grid (LP_POST_BLOCKS, CO): one class per workgroup (round 6: the 64 workgroups of the first version walked the classes one after
 // the other - a quarter of the CUs, 37 us per 480 x 854 frame with four classes).  min / max do not depend on the order: same bits.
-__global__ __launch_bounds__(256) void seg_minmax_exact_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
-                                                               int CO, int Ho, int Wo) {
+__device__ __forceinline__ void seg_minmax_exact_body(const float* __restrict__ seg, float* __restrict__ partial, int H, int W, int CO, int Ho,
+                                                      int Wo) {
   __shared__ float smn[256], smx[256];
   const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
   const int total = Ho * Wo, c = blockIdx.y;
@@ -794,8 +861,8 @@ __global__ __launch_bounds__(256) void seg_minmax_exact_kernel(const float* __re
   }
 }
 
-__global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
-                                                               uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
+__device__ __forceinline__ void seg_argmax_exact_body(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
+                                                      uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
   __shared__ float smn[LP_MAX_CLASSES], smx[LP_MAX_CLASSES];
   if ((int)threadIdx.x < CO) {
     float mn = INFINITY, mx = -INFINITY;
@@ -821,6 +888,56 @@ __global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __re
   }
 }
 
+__global__ __launch_bounds__(256) void seg_minmax_exact_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
+                                                               int CO, int Ho, int Wo) {
+  seg_minmax_exact_body(seg, partial, H, W, CO, Ho, Wo);
+}
+__global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
+                                                               uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
+  seg_argmax_exact_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
+}
+// lock-step batch: slot blockIdx.z post-processes ITS propagated frame (frame qframe of its label rows [frame][H*W][CO_n]) with its own
+// class count into frame qframe of its label maps; the class dimension of the min / max grid is sized for COcap
+struct SegPostBatchArgs {
+  const float* sbank;      // [nslots][Tcap][H*W][COcap]
+  float* partial;          // [nslots][LP_POST_BLOCKS][COcap][2]
+  uint8_t* preds;          // [nslots][Tcap][Ho*Wo]
+  const int* desc;
+  int Tcap, COcap, H, W, Ho, Wo;
+};
+__device__ __forceinline__ bool seg_post_slot(const SegPostBatchArgs& b, const float*& seg, float*& partial, uint8_t*& label, int& CO) {
+  const int n = blockIdx.z;
+  int qframe;
+  if (!lpb_row_post(b.desc, n, b.Tcap, b.COcap, qframe, CO)) return false;
+  const size_t HW = (size_t)b.H * b.W;
+  seg = b.sbank + (size_t)n * b.Tcap * HW * b.COcap + (size_t)qframe * HW * CO;
+  partial = b.partial + (size_t)n * LP_POST_BLOCKS * b.COcap * 2;
+  label = b.preds + ((size_t)n * b.Tcap + qframe) * b.Ho * b.Wo;
+  return true;
+}
+__global__ __launch_bounds__(256) void seg_minmax_exact_batch_kernel(SegPostBatchArgs b) {
+  const float* seg; float* partial; uint8_t* label; int CO;
+  if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;
+  seg_minmax_exact_body(seg, partial, b.H, b.W, CO, b.Ho, b.Wo);
+}
+__global__ __launch_bounds__(256) void seg_argmax_exact_batch_kernel(SegPostBatchArgs b) {
+  const float* seg; float* partial; uint8_t* label; int CO;
+  if (!seg_post_slot(b, seg, partial, label, CO)) return;
+  seg_argmax_exact_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
+}
+int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                                           int COcap, int Ho, int Wo, hipStream_t s) {
+  if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: 1 <= classes <= 256");
+  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, COcap, H, W, Ho, Wo};
+  hipLaunchKernelGGL(seg_minmax_exact_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
+  int rc = vfs_check_launch("seg_minmax_exact_batch");
+  if (rc) return rc;
+  int blocks = (Ho * Wo + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(seg_argmax_exact_batch_kernel, dim3(blocks, 1, nslots), dim3(256), 0, s, b);
+  return vfs_check_launch("seg_argmax_exact_batch");
+}
+
 int vfs_seg_postprocess_exact_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                                      hipStream_t s) {
   if (CO < 1 || CO > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact: 1 <= classes <= 256");
@@ -837,9 +954,9 @@ int vfs_seg_postprocess_exact_launch(const float* seg, float* partial, uint8_t* 
 // F.interpolate(mode='bilinear', align_corners=False) between arbitrary layouts (element (c, y, x) of a map at
 // c*sc + y*sy + x*sx): the one-hot reference map -> feature resolution, soft label maps -> original resolution
 // (vanilla_tracker.py:101-111,162-166 with a 4-D ref_seg_map)
-__global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int H, int W,
-                                                                  int Ho, int Wo, long long ssc, long long ssy, long long ssx, long long dsc,
-                                                                  long long dsy, long long dsx) {
+__device__ __forceinline__ void bilinear_resize_f32_body(const float* __restrict__ src, float* __restrict__ dst, int C, int H, int W, int Ho,
+                                                         int Wo, long long ssc, long long ssy, long long ssx, long long dsc, long long dsy,
+                                                         long long dsx) {
   const long long total = (long long)C * Ho * Wo;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -858,6 +975,32 @@ __global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* _
   const float v10 = s[y1 * ssy + x0 * ssx], v11 = s[y1 * ssy + x1 * ssx];
   const float top = hx * v00 + lx * v01, bot = hx * v10 + lx * v11;
   dst[(size_t)c * dsc + (size_t)oy * dsy + (size_t)ox * dsx] = hy * top + ly * bot;
+}
+__global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int H, int W,
+                                                                  int Ho, int Wo, long long ssc, long long ssy, long long ssx, long long dsc,
+                                                                  long long dsy, long long dsx) {
+  bilinear_resize_f32_body(src, dst, C, H, W, Ho, Wo, ssc, ssy, ssx, dsc, dsy, dsx);
+}
+// lock-step batch, soft maps: slot blockIdx.z resizes ITS propagated frame [H*W][CO_n] into frame qframe of its maps [Tcap][CO_n][Ho][Wo]
+// (packed with the slot's own channel count inside a region sized for COcap)
+__global__ __launch_bounds__(256) void bilinear_resize_f32_batch_kernel(const float* __restrict__ sbank, float* __restrict__ preds,
+                                                                        const int* __restrict__ desc, int Tcap, int COcap, int H, int W, int Ho,
+                                                                        int Wo) {
+  const int n = blockIdx.z;
+  int qframe, CO;
+  if (!lpb_row_post(desc, n, Tcap, COcap, qframe, CO)) return;
+  const size_t HW = (size_t)H * W, HWo = (size_t)Ho * Wo;
+  const float* src = sbank + (size_t)n * Tcap * HW * COcap + (size_t)qframe * HW * CO;
+  float* dst = preds + (size_t)n * Tcap * HWo * COcap + (size_t)qframe * HWo * CO;
+  bilinear_resize_f32_body(src, dst, CO, H, W, Ho, Wo, 1, (long long)W * CO, CO, (long long)HWo, Wo, 1);
+}
+int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
+                                         int Wo, hipStream_t s) {
+  if (COcap < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return vfs_set_error(VFS_ERR_SHAPE, "bilinear_resize_f32_batch: geometry");
+  const long long total = (long long)COcap * Ho * Wo;
+  hipLaunchKernelGGL(bilinear_resize_f32_batch_kernel, dim3((unsigned)((total + 255) / 256), 1, nslots), dim3(256), 0, s, sbank, preds, desc, Tcap,
+                     COcap, H, W, Ho, Wo);
+  return vfs_check_launch("bilinear_resize_f32_batch");
 }
 int vfs_bilinear_resize_f32_launch(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
                                    hipStream_t s) {

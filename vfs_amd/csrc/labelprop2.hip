@@ -28,6 +28,7 @@
 // three-stage LDS ring by LDS-DMA (buffer_load ... lds, whole 128-byte lines: the split bank interleaves hi / lo per 16 channels),
 // no barrier and no cross-wave traffic inside the channel loop; the four partial 64x64 score tiles meet in LDS once per key block.
 #include "vfs_lpx.h"
+#include "vfs_lpb.h"
 
 #pragma clang fp contract(off)
 
@@ -103,7 +104,8 @@ __device__ __forceinline__ int lp2_row_reach(int dmin, int r) {      // dx(y) ab
   while (dx * dx > lim) --dx;
   return dx;
 }
-__device__ __forceinline__ Lp2Window lp2_window(const Lp2Args& a, int f, int qy0, int qx0, int tab_nwin = 0) {
+template <class A>
+__device__ __forceinline__ Lp2Window lp2_window(const A& a, int f, int qy0, int qx0, int tab_nwin = 0) {
   Lp2Window w;
   w.slot = a.kslot[f];
   w.r = f < a.non_mask_len ? 0 : a.radius;
@@ -132,7 +134,8 @@ __device__ __forceinline__ int lp2_block_of(int i, int nkb, int stagger = 0) {  
 // there are fewer than ten key frames) with an fp32 dot product; gthr[q] = (10th best - EPS) is a valid lower bound of the 10th
 // best s~ pass 1 will see (|dot - s~| <= EPS for every candidate, and the 10th best over a subset never exceeds the 10th best
 // over all).  -inf when fewer than ten seeds exist.
-__global__ __launch_bounds__(256) void lp2_seed_kernel(Lp2Args a) {
+template <class A>
+__device__ __forceinline__ void lp2_seed_body(const A& a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int H = a.H, W = a.W, C = a.C, HW = H * W;
   const int q = blockIdx.x * 4 + wave;
@@ -259,8 +262,8 @@ __device__ __forceinline__ void lp2_park(float* dst, const f32x16& v, int r0) { 
 }
 
 // NG = 16-channel groups per wave = C / 64 (4: C = 256, 8: 512, 16: 1024)
-template <int NG>
-__global__ __launch_bounds__(256, 1) void lp2_score_kernel(Lp2Args a) {
+template <int NG, class A>
+__device__ __forceinline__ void lp2_score_body(const A& a) {
   // (a fourth stage - three in flight, the reduction in two rounds to make room - measured the same 2.28 ms: kept at three)
   constexpr int RING = LP2_RING, NST = NG / 2, SBYTES = 64 * 128;
   constexpr int RH = RING == 4 ? 8 : 16;      // accumulator registers parked per reduction round (4 stages of ring: LDS for half a tile)
@@ -667,7 +670,8 @@ __device__ __forceinline__ void lp2_wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-__global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) {
+template <class A>
+__device__ __forceinline__ void lp2_refine_body(const A& a) {
   __shared__ __attribute__((aligned(16))) float sQ[4][1024];      // the query row (C <= 1024)
   __shared__ unsigned long long sSurv[4][LP2_SURV_CAP];      // the query's survivors
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -815,25 +819,90 @@ __global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) {
   }
 }
 
+// ---- the kernels: one video (the arguments are the kernel's), or slot blockIdx.z of a lock-step batch (the arguments are built from
+// the slot's descriptor row; the key list stays in the table).  Same bodies: the per-query arithmetic has one copy.
+struct Lp2SlotArgs {      // Lp2Args of one slot
+  const float* fbank; const bf16_t* hl; const float* sbank; float* out;
+  unsigned long long* lists; int* counts; int* flags; int* gthr;
+  int qframe, nkeys;
+  const int* kslot;
+  int H, W, C, CO, radius, topk, non_mask_len;
+  float temperature, margin;
+  int cap, nsplit, xcd_order, dbg, trim, entries;
+};
+__device__ __forceinline__ bool lp2_slot_args(const LpBatchArgs& b, Lp2SlotArgs& a) {
+  const int n = blockIdx.z;
+  LpbRow r;
+  if (!lpb_row(b.desc, n, b.Tcap, b.max_nkeys, b.COcap, b.radius, r)) return false;
+  const size_t HW = (size_t)b.H * b.W, frames = (size_t)n * b.Tcap * HW;
+  a.fbank = b.fbank + frames * b.C;
+  a.hl = b.hl + frames * 2 * b.C;
+  float* sb = b.sbank + frames * b.COcap;
+  a.sbank = sb;
+  a.out = sb + (size_t)r.qframe * HW * r.CO;
+  char* ws = b.ws + (size_t)n * b.ws_stride + (size_t)LP_MAX_SPLIT * HW * LPX_TOPK * 8;      // behind the dense kernels' partial lists
+  a.lists = reinterpret_cast<unsigned long long*>(ws);
+  a.counts = reinterpret_cast<int*>(ws + b.lists_bytes);
+  a.gthr = a.counts + (size_t)LP2_MAX_SPLIT * HW;
+  a.flags = b.flags + n;
+  a.qframe = r.qframe; a.nkeys = r.nkeys; a.kslot = r.kslot;
+  a.H = b.H; a.W = b.W; a.C = b.C; a.CO = r.CO; a.radius = b.radius; a.topk = b.topk; a.non_mask_len = r.non_mask_len;
+  a.temperature = b.temperature; a.margin = b.margin;
+  a.nsplit = lp2_splits_for(b.want_splits, r.nkeys, b.fpb_opt);
+  a.cap = min(b.cap_opt > 0 ? b.cap_opt : LP2_LIST_MAX, min(LP2_LIST_MAX, b.entries / a.nsplit));      // >= 1: checked by the launcher for the most splits a slot can have
+  a.xcd_order = 0;      // (the XCD-aware order is defined on a one-video grid)
+  a.dbg = b.dbg; a.trim = b.trim; a.entries = b.entries;
+  return true;
+}
+__global__ __launch_bounds__(256) void lp2_seed_kernel(Lp2Args a) { lp2_seed_body(a); }
+template <int NG>
+__global__ __launch_bounds__(256, 1) void lp2_score_kernel(Lp2Args a) { lp2_score_body<NG>(a); }
+__global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) { lp2_refine_body(a); }
+
+__global__ __launch_bounds__(256) void lp2_seed_batch_kernel(LpBatchArgs b) {
+  Lp2SlotArgs a;
+  if (lp2_slot_args(b, a)) lp2_seed_body(a);
+}
+template <int NG>
+__global__ __launch_bounds__(256, 1) void lp2_score_batch_kernel(LpBatchArgs b) {
+  Lp2SlotArgs a;
+  if (!lp2_slot_args(b, a)) return;
+  if ((int)blockIdx.x >= ((b.H + 7) >> 3) * ((b.W + 7) >> 3) * a.nsplit) return;      // the grid is sized for the slot with the most key frames
+  lp2_score_body<NG>(a);
+}
+__global__ __launch_bounds__(256) void lp2_refine_batch_kernel(LpBatchArgs b) {
+  Lp2SlotArgs a;
+  if (lp2_slot_args(b, a)) lp2_refine_body(a);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Key frames per workgroup: about four workgroups per CU and launch (pass 1 runs ONE workgroup per CU at a time: the query tile fills
 // the register file).  Measured on the MI355X, 21 key frames: 1 / 2 / 3 frames per workgroup = 2.21 / 2.24 / 2.27 ms (ResNet-50) and
 // 0.78 / 0.75 / 0.77 (ResNet-18) - flat; two workgroups of 11 frames per tile: 0.92.
-int vfs_lp2_splits(int H, int W, int nkeys) {
+// nactive: the slots of a lock-step batch that run in the same launch share the chip (a batch must not over-split).
+int vfs_lp2_wanted_splits(int H, int W, int nactive) {
   const int tiles = ((H + 7) / 8) * ((W + 7) / 8);
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
   }
-  int nsplit = (4 * cus + tiles - 1) / tiles;
-  nsplit = max(1, min(nsplit, min(nkeys, LP2_MAX_SPLIT)));
-  int fpb = (nkeys + nsplit - 1) / nsplit;
-  if (vfs_option_lp2_fpb > 0) fpb = min(nkeys, max(vfs_option_lp2_fpb, (nkeys + LP2_MAX_SPLIT - 1) / LP2_MAX_SPLIT));
-  return (nkeys + fpb - 1) / fpb;
+  const long long all_tiles = (long long)tiles * max(1, nactive);
+  return (int)((4 * cus + all_tiles - 1) / all_tiles);
 }
+int vfs_lp2_splits(int H, int W, int nkeys, int nactive) { return lp2_splits_for(vfs_lp2_wanted_splits(H, W, nactive), nkeys, vfs_option_lp2_fpb); }
 
 bool vfs_lp2_eligible(int C) { return vfs_option_lp2 && (C == 256 || C == 512 || C == 1024); }
+
+static float lp2_margin(int C) {
+  // |s~ - s| <= EPS for unit rows: 3 * 2^-16 (the dropped lo.lo product and the two representation remainders, Cauchy-Schwarz) +
+  // 4 * C * 2^-24 (C roundings of the exact chain, <= 3 C of the matrix unit's partial sums); margin = 2 EPS
+  // + 2^-21: the total order is applied to fl(s / temperature), and a correctly rounded division keeps a STRICT order only across a
+  // gap of more than one ulp of the quotient (2^-23 relative): with the extra 2^-21 (|s| <= 1) a pruned candidate's exact score
+  // lies more than four ulps below each of its ten betters, so it cannot tie with one of them after the division either
+  // (round 4 advisor finding: the proof was stated on s, the order on s / temperature)
+  return 2.0f * (3.0f / 65536.0f + 4.0f * (float)C / 16777216.0f) + 1.0f / 2097152.0f;
+}
 
 int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
   if (!vfs_lp2_eligible(a.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: C must be 256, 512 or 1024");
@@ -842,13 +911,7 @@ int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
   if (a.H >= 32768 || a.W >= 65536 || (long long)a.nkeys * a.H * a.W >= 0x7fffffffLL || (long long)a.H * a.W * a.C * 4 >= 0xFFFFFFF0LL)
     return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: map too large");
   if (!(a.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass: temperature > 0");
-  // |s~ - s| <= EPS for unit rows: 3 * 2^-16 (the dropped lo.lo product and the two representation remainders, Cauchy-Schwarz) +
-  // 4 * C * 2^-24 (C roundings of the exact chain, <= 3 C of the matrix unit's partial sums); margin = 2 EPS
-  // + 2^-21: the total order is applied to fl(s / temperature), and a correctly rounded division keeps a STRICT order only across a
-  // gap of more than one ulp of the quotient (2^-23 relative): with the extra 2^-21 (|s| <= 1) a pruned candidate's exact score
-  // lies more than four ulps below each of its ten betters, so it cannot tie with one of them after the division either
-  // (round 4 advisor finding: the proof was stated on s, the order on s / temperature)
-  a.margin = 2.0f * (3.0f / 65536.0f + 4.0f * (float)a.C / 16777216.0f) + 1.0f / 2097152.0f;
+  a.margin = lp2_margin(a.C);
   a.nsplit = vfs_lp2_splits(a.H, a.W, a.nkeys);
   // the list workspace (LP2_MAX_SPLIT x LP2_MAX_CAP entries per query) is shared out among the splits in use: the first steps of a
   // clip have few key frames (few splits) and cold thresholds (long lists)
@@ -869,4 +932,36 @@ int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
   if (rc) return rc;
   hipLaunchKernelGGL(lp2_refine_kernel, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
   return vfs_check_launch("lp2_refine");
+}
+
+// every slot of one lock-step: memset of the slots' overflow words, seed, score, refine - the launches of one video
+int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
+  if (!vfs_lp2_eligible(b.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: C must be 256, 512 or 1024");
+  if (b.topk < 1 || b.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: 1 <= topk <= 10");
+  if (b.H >= 32768 || b.W >= 65536 || (long long)b.max_nkeys * b.H * b.W >= 0x7fffffffLL || (long long)b.H * b.W * b.C * 4 >= 0xFFFFFFF0LL)
+    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: map too large");
+  if (!(b.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch: temperature > 0");
+  b.margin = lp2_margin(b.C);
+  b.want_splits = vfs_lp2_wanted_splits(b.H, b.W, nactive);
+  b.fpb_opt = vfs_option_lp2_fpb;
+  b.cap_opt = vfs_option_lp2_cap;
+  b.trim = vfs_option_lp2_trim;
+  b.dbg = vfs_option_lp2_dbg;
+  int most = 1;      // the most key-frame splits a slot of this step can have: the grid, and the least list capacity
+  for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lp2_splits_for(b.want_splits, nk, b.fpb_opt));
+  if (b.entries / most < 1)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch: the workspace holds less than one list entry per (key-frame split, query)");
+  const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8), HW = b.H * b.W;
+  if (hipMemsetAsync(b.flags, 0, sizeof(int) * b.nslots, s) != hipSuccess) return vfs_set_error(VFS_ERR_LAUNCH, "labelprop_f32_2pass_batch: hipMemsetAsync");
+  hipLaunchKernelGGL(lp2_seed_batch_kernel, dim3((HW + 3) / 4, 1, b.nslots), dim3(256), 0, s, b);
+  int rc = vfs_check_launch("lp2_seed_batch");
+  if (rc) return rc;
+  const dim3 grid(tiles * most, 1, b.nslots);
+  if (b.C == 256) hipLaunchKernelGGL(lp2_score_batch_kernel<4>, grid, dim3(256), 0, s, b);
+  else if (b.C == 512) hipLaunchKernelGGL(lp2_score_batch_kernel<8>, grid, dim3(256), 0, s, b);
+  else hipLaunchKernelGGL(lp2_score_batch_kernel<16>, grid, dim3(256), 0, s, b);
+  rc = vfs_check_launch("lp2_score_batch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(lp2_refine_batch_kernel, dim3((HW + 3) / 4, 1, b.nslots), dim3(256), 0, s, b);
+  return vfs_check_launch("lp2_refine_batch");
 }

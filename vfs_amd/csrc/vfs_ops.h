@@ -428,6 +428,71 @@ int vfs_split_rows_bf16x2_launch(const float* x, bf16_t* hl, long long P, int C,
 int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s);
 bool vfs_lp2_eligible(int C);
 
+// ---- label propagation of a batch of videos in lock-step (labelprop2.hip, exact_f32.hip) --------------------
+// One launch set serves every slot of a step: the grids get a slot dimension (blockIdx.z), every workgroup builds the arguments of
+// ITS slot from the slot's descriptor row (layout: include/vfs_hip.h) and runs the single-video kernel body on them - the
+// per-query arithmetic is the same code.  Slot n of the banks starts at base + n * stride; its label rows are packed [frame][H*W][CO_n].
+#define LPB_DESC_INTS 72      // = VFS_LPB_DESC_INTS
+#define LPB_MAX_SLOTS 64
+#define LPB_FLAG_BYTES 256    // the per-slot overflow words at the head of the two-pass workspace
+struct LpBatchArgs {
+  const float* fbank;         // [nslots][Tcap][H*W][C]
+  const bf16_t* hl;           // [nslots][Tcap][H*W][2C] (two-pass only)
+  float* sbank;               // [nslots][Tcap][H*W][COcap]: values, and the output (frame qframe of every active slot)
+  char* ws;                   // slot n's workspace = ws + n * ws_stride: [dense partial lists][candidate lists][counts + thresholds]
+  int* flags;                 // [nslots] overflow words (two-pass: != 0 -> the dense kernels redo THAT slot); null: dense kernels run every active slot
+  const int* desc;            // [nslots][LPB_DESC_INTS], the rows of this step
+  long long ws_stride, lists_bytes;
+  int Tcap, nslots, max_nkeys, COcap;
+  int H, W, C, radius, topk;
+  float temperature, margin;
+  int want_splits, fpb_opt, cap_opt, entries, dbg, trim;      // two-pass: key-frame splits wanted per slot (the active slots share the chip)
+  int target, wgs, minb;                                      // dense: workgroups wanted per slot, as vfs_labelprop_f32_launch counts them
+};
+// key-frame splits of pass 1 for nkeys key frames when `want` are wanted (vfs_lp2_splits: want = 4 workgroups per CU over the tiles
+// of every active slot)
+__host__ __device__ inline int lp2_splits_for(int want, int nkeys, int fpb_opt) {
+  int nsplit = want < nkeys ? want : nkeys;
+  nsplit = nsplit < LP2_MAX_SPLIT ? nsplit : LP2_MAX_SPLIT;
+  nsplit = nsplit > 1 ? nsplit : 1;
+  int fpb = (nkeys + nsplit - 1) / nsplit;
+  if (fpb_opt > 0) {
+    const int least = (nkeys + LP2_MAX_SPLIT - 1) / LP2_MAX_SPLIT;
+    fpb = fpb_opt > least ? fpb_opt : least;
+    fpb = fpb < nkeys ? fpb : nkeys;
+  }
+  return (nkeys + fpb - 1) / fpb;
+}
+// dense kernel: key-frame splits x window sub-splits (blockIdx.y) for nkeys key frames; returns the product, *nsub_out the sub-splits
+__host__ __device__ inline int lpx_splits_for(int nkeys, int tiles, int target, int wgs, int minb, int H, int W, int radius, int* nsub_out) {
+  int nsplit = (target + tiles - 1) / tiles;
+  if (nsplit > nkeys) nsplit = nkeys;
+  if (nsplit > LP_MAX_FSPLIT) nsplit = LP_MAX_FSPLIT;
+  if (nsplit < 1) nsplit = 1;
+  const int fpb = (nkeys + nsplit - 1) / nsplit;
+  nsplit = (nkeys + fpb - 1) / fpb;
+  int nsub = 1;
+  if (wgs > 0) {
+    const int side = 8 + 2 * (radius - 1);
+    const int wh = radius > 0 ? (H < side ? H : side) : H, ww = radius > 0 ? (W < side ? W : side) : W;
+    const int blocks = (wh * ww + 63) / 64;
+    nsub = (wgs + tiles * nsplit - 1) / (tiles * nsplit);
+    const int byb = blocks / (minb > 1 ? minb : 1);
+    nsub = nsub < (byb > 1 ? byb : 1) ? nsub : (byb > 1 ? byb : 1);
+    nsub = nsub < LP_MAX_SPLIT / nsplit ? nsub : LP_MAX_SPLIT / nsplit;
+    nsub = nsub > 1 ? nsub : 1;
+  }
+  *nsub_out = nsub;
+  return nsplit * nsub;
+}
+int vfs_lp2_splits(int H, int W, int nkeys, int nactive = 1);
+int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
+int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
+int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                                           int COcap, int Ho, int Wo, hipStream_t s);
+int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
+                                         int Wo, hipStream_t s);
+
 // ---- davis.hip: DAVIS J&F ingredients ---------------------------------------------------------------------
 struct DavisArgs {
   const uint8_t* pred;   // [T][H][W] predicted labels

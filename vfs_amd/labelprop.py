@@ -83,11 +83,12 @@ def two_pass_ok(precision, with_norm, C):
     return precision == 'fp32' and with_norm and C in (256, 512, 1024) and knobs.flag('VFS_LP_TWO_PASS')
 
 
-def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, split_banks=None):
+def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, split_banks=None, alloc=None):
     """imgs [1,3,T,H,W] fp32 -> feature bank [T, h*w, C] of the evaluated stage, L2-normalised over the
     channels unless with_norm=False (bf16 or fp32 by `precision`); with all_blocks (vanilla_tracker.py:32-45,
     README.md:76) a LIST of banks, one per residual block of every stage in test_cfg.out_indices.
-    split_banks: a list that receives, per bank, its bf16 hi / lo split copy [T, h*w, 2C] (or None) for the two-pass kernels."""
+    split_banks: a list that receives, per bank, its bf16 hi / lo split copy [T, h*w, 2C] (or None) for the two-pass kernels.
+    alloc(T, rows, channels, dtype): where a bank lives (forward_test_batch: the slot's region of the stacked banks); default: its own tensor."""
     bb = tracker.backbone
     dev = frames_ncthw.device
     _, _, T, H, W = frames_ncthw.shape
@@ -121,9 +122,12 @@ def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, p
         else:
             feats = [outs[stage]]
         if banks is None:
-            banks = [torch.empty(T, h * w, C, dtype=F32 if exact else BF16, device=dev) for (_, h, w, C) in feats]
+            if alloc is None:
+                def alloc(T, rows, channels, dtype):
+                    return torch.empty(T, rows, channels, dtype=dtype, device=dev)
+            banks = [alloc(T, h * w, C, F32 if exact else BF16) for (_, h, w, C) in feats]
             shapes = [(h, w, C) for (_, h, w, C) in feats]
-            hls = [torch.empty(T, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(precision, with_norm, C) else None
+            hls = [alloc(T, h * w, 2 * C, BF16) if two_pass_ok(precision, with_norm, C) else None
                    for (_, h, w, C) in feats]
             if split_banks is not None:
                 split_banks.extend(hls)
@@ -139,6 +143,17 @@ def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, p
     if all_blocks:
         return banks, shapes
     return banks[0], shapes[0][0], shapes[0][1], shapes[0][2]
+
+
+def _result(tracker, arr):
+    """the label maps of one feature level as forward_test hands them over: the array, or with test_cfg.save_np its .npy path"""
+    if not tracker.save_np:
+        return arr
+    os.makedirs('.eval', exist_ok=True)                             # vanilla_tracker.py:184-193
+    tmp = tempfile.NamedTemporaryFile(dir='.eval', suffix='.npy', delete=False)
+    tmp.close()
+    np.save(tmp.name, arr)
+    return tmp.name
 
 
 def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
@@ -233,17 +248,216 @@ def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
             else:
                 eng.timed('seg_postprocess', (0.0, 4.0 * h * w * CO + float(out_h * out_w)), dev, post, sbank[f], partial, preds[f],
                           h, w, CO, out_h, out_w, s)
-        arr = preds.cpu().numpy()
-        if tracker.save_np:                                         # vanilla_tracker.py:184-193
-            os.makedirs('.eval', exist_ok=True)
-            tmp = tempfile.NamedTemporaryFile(dir='.eval', suffix='.npy', delete=False)
-            tmp.close()
-            np.save(tmp.name, arr)
-            all_preds.append(tmp.name)
-        else:
-            all_preds.append(arr)
+        all_preds.append(_result(tracker, preds.cpu().numpy()))
     if tracker.save_np:
         return [all_preds] if len(all_preds) > 1 else [all_preds[0]]
     if len(all_preds) > 1:      # vanilla_tracker.py:199-205: [1, num_feats, T, ...] unravelled over the batch dim
         return [np.stack(all_preds, axis=0)]
     return [all_preds[0]]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# forward_test of a batch of videos in lock-step (csrc: vfs_labelprop_f32_batch / _2pass_batch and the batched post-processing).
+#
+# A JHMDB or VIP frame (30 x 40 features: 20 query tiles) does not fill the chip, and an evaluation is hundreds of such videos.  Here
+# up to `batch` videos of one frame size occupy SLOTS of stacked banks and advance together: one launch set per step serves every slot,
+# each at its own frame with its own key list and class count; a slot whose video ends is refilled with the next one.  All clip
+# lengths are known, so the schedule of the whole group - per step and slot: active, query frame, key frames, non_mask_len, class
+# count - is worked out on the host first and uploaded ONCE as the descriptor table the kernels read (include/vfs_hip.h); inside the
+# step loop nothing is read back and nothing but a newly admitted video's frames and first label map goes to the device.
+DESC_INTS = 72      # include/vfs_hip.h VFS_LPB_DESC_INTS
+
+
+def _key_frames(f, precede, with_first):
+    keys = list(range(max(0, f - precede), f))
+    return [0] + keys if with_first else keys      # frame 0 twice while f <= precede (as the reference)
+
+
+def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_len):
+    """the lock-step schedule of videos of `lengths` frames (each >= 2, admitted in this order) over `nslots` slots.
+    -> (table int32 [steps][nslots][DESC_INTS], steps) with steps[i] = (admitted [(slot, video)], retired [(slot, video)], active
+    slots, most key frames of a slot)"""
+    queue = list(range(len(lengths)))[::-1]
+    slots = [None] * nslots      # [video, next frame]
+    rows, steps = [], []
+    while True:
+        admitted = []
+        for n in range(nslots):
+            if slots[n] is None and queue:
+                slots[n] = [queue.pop(), 1]
+                admitted.append((n, slots[n][0]))
+        if all(sl is None for sl in slots):
+            break
+        row = np.zeros((nslots, DESC_INTS), np.int32)
+        retired, most = [], 0
+        for n, sl in enumerate(slots):
+            if sl is None:
+                continue
+            v, f = sl
+            keys = _key_frames(f, precede, with_first)
+            assert 0 <= non_mask_len < len(keys)                    # local_attention.py:272
+            row[n, :5] = (1, f, len(keys), non_mask_len, class_counts[v])
+            row[n, 8:8 + len(keys)] = keys
+            most = max(most, len(keys))
+            sl[1] += 1
+            if sl[1] == lengths[v]:
+                retired.append((n, v))
+                slots[n] = None
+        rows.append(row)
+        steps.append((admitted, retired, sum(int(r[0]) for r in row), most))
+    table = np.stack(rows) if rows else np.zeros((0, nslots, DESC_INTS), np.int32)
+    return table, steps
+
+
+def _first_maps(ref_seg_map, dev):
+    """the reference label map of a video as forward_test reads it: (4-D) the soft map on the device, (3-D) uint8 on the host"""
+    if ref_seg_map.ndim == 4:
+        return ref_seg_map[0].detach().to(dev, F32).contiguous()
+    return ref_seg_map[0].detach().cpu().numpy().astype(np.uint8)
+
+
+def _run_group(tracker, eng, cfg, vids, batch, outs):
+    """vids: [(index, imgs [1,3,T,H,W], ref_seg_map, out_h, out_w)] of ONE frame size, label-map kind and output size"""
+    lib = eng.lib
+    dev = vids[0][1].device
+    s = eng.stream(dev)
+    soft = vids[0][2].ndim == 4
+    out_h, out_w = vids[0][3], vids[0][4]
+    refs = [_first_maps(v[2], dev) for v in vids]
+    if soft and max(r.shape[0] for r in refs) > 256:
+        raise NotImplementedError('label propagation kernels: at most 256 classes')
+    single = [i for i, v in enumerate(vids) if v[1].size(2) == 1]
+    for i in single:      # a one-frame clip is its (resized) reference map
+        if soft:
+            first = torch.empty(1, refs[i].shape[0], out_h, out_w, dtype=F32, device=dev)
+            lib.bilinear_resize_f32(refs[i], first[0], refs[i].shape[0], refs[i].shape[1], refs[i].shape[2], out_h, out_w, 0, 0, s)
+            outs[vids[i][0]] = _result(tracker, first.cpu().numpy())
+        else:
+            outs[vids[i][0]] = _result(tracker, np.ascontiguousarray(torch_nearest_resize(refs[i], out_h, out_w))[None])
+    run = [i for i in range(len(vids)) if i not in set(single)]
+    if not run:
+        return
+    B = min(batch, len(run))
+    lengths = [int(vids[i][1].size(2)) for i in run]
+    Tcap = max(lengths)
+    g = {}      # the group's banks: allocated when the first video's feature map is known
+    cur = [0]   # the slot being admitted
+
+    def alloc(T, rows, channels, dtype):
+        key = 'hl' if dtype == BF16 else 'fb'
+        if key not in g:
+            g[key] = torch.empty(B, Tcap, rows, channels, dtype=dtype, device=dev)
+        return g[key][cur[0], :T]
+
+    def features(n, i):
+        cur[0] = n
+        return extract_features(tracker, eng, vids[i][1], cfg['batch_step'], False, 'fp32', cfg['with_norm'], [], alloc)[1:]
+
+    def set_up(h, w, C):
+        """everything that needs the feature-map size: class counts, label / prediction banks, workspace, the schedule"""
+        hw = h * w
+        g['small'] = [None if soft else pil_nearest_resize(refs[i], h, w) for i in run]
+        cos = [refs[i].shape[0] if soft else int(sm.max()) + 1 for i, sm in zip(run, g['small'])]      # F.one_hot infers max+1 classes
+        COcap = max(cos)
+        g.update(h=h, w=w, C=C, cos=cos, COcap=COcap)
+        g['sb'] = torch.empty(B, Tcap * hw * COcap, dtype=F32, device=dev)
+        if soft:
+            g['preds'] = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
+        else:
+            g['preds'] = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
+            g['partial'] = eng.ws('ws.segpost_batch', B * 64 * COcap * 2, F32, dev)
+        nbytes = torch.zeros(1, dtype=torch.int64)
+        if 'hl' in g:
+            lib.labelprop_f32_2pass_batch_workspace_bytes(h, w, max(0, cfg['entries']), B, nbytes)
+        else:
+            lib.labelprop_f32_batch_workspace_bytes(h, w, B, nbytes)
+        g['ws'] = torch.empty((int(nbytes.item()) + 3) // 4, dtype=F32, device=dev)      # (per group: released with it)
+        table, steps = batch_schedule(lengths, cos, B, cfg['precede'], cfg['with_first'], cfg['non_mask_len'])
+        g['table'] = torch.from_numpy(table).to(dev)      # the ONE upload of the schedule
+        return steps
+
+    def first_frame(n, k):
+        """the video's reference map -> frame 0 of the slot's label rows (feature size) and of its predictions (original size)"""
+        i, h, w, CO = run[k], g['h'], g['w'], g['cos'][k]
+        hw = h * w
+        rows0 = g['sb'][n, :hw * CO]
+        if soft:
+            ref = refs[i]
+            lib.bilinear_resize_f32(ref, rows0, CO, ref.shape[1], ref.shape[2], h, w, 0, 1, s)
+            lib.bilinear_resize_f32(ref, g['preds'][n, :CO * out_h * out_w], CO, ref.shape[1], ref.shape[2], out_h, out_w, 0, 0, s)
+        else:
+            lib.onehot(torch.from_numpy(np.ascontiguousarray(g['small'][k])).to(dev), rows0, hw, CO, s)
+            g['preds'][n, 0] = torch.from_numpy(np.ascontiguousarray(torch_nearest_resize(refs[i], out_h, out_w))).to(dev).reshape(-1)
+
+    # the first video's features give the feature-map size; from there on the schedule is fixed
+    h, w, C = features(0, run[0])
+    steps = set_up(h, w, C)
+    hl, ws, table = g.get('hl'), g['ws'], g['table']
+    for step, (admitted, retired, nactive, most) in enumerate(steps):
+        for n, k in admitted:
+            if (step, n) != (0, 0):
+                features(n, run[k])
+            first_frame(n, k)
+        if hl is not None:
+            lib.labelprop_f32_2pass_batch(g['fb'], hl, g['sb'], ws, ws.numel() * 4, table[step], B, nactive, most, Tcap, h, w, C, g['COcap'],
+                                          cfg['radius'], cfg['topk'], cfg['temp'], 1, s)
+        else:
+            lib.labelprop_f32_batch(g['fb'], g['sb'], ws, ws.numel() * 4, table[step], B, nactive, most, Tcap, h, w, C, g['COcap'], cfg['radius'],
+                                    cfg['topk'], cfg['temp'], s)
+        if soft:
+            lib.bilinear_resize_f32_batch(g['sb'], g['preds'], table[step], B, Tcap, h, w, g['COcap'], out_h, out_w, s)
+        else:
+            lib.seg_postprocess_exact_batch(g['sb'], g['partial'], g['preds'], table[step], B, Tcap, h, w, g['COcap'], out_h, out_w, s)
+        for n, k in retired:      # the video's maps leave the device now; its slot is refilled at the next step
+            T, CO = lengths[k], g['cos'][k]
+            if soft:
+                arr = g['preds'][n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
+            else:
+                arr = g['preds'][n, :T].reshape(T, out_h, out_w)
+            arr = arr.cpu().numpy() if dev.type != 'cpu' else arr.numpy().copy()      # (the slot's maps are overwritten by the next video)
+            outs[vids[run[k]][0]] = _result(tracker, arr)
+
+
+def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8):
+    """out[i] == forward_test(imgs_list[i], ref_seg_maps[i], img_metas[i])[0] for every video, in input order.
+    Videos are grouped by frame size, kind of label map (3-D labels / 4-D soft maps) and output size; a group runs in lock-step
+    (above) with precision 'fp32' and one feature level.  precision='bf16' and all_blocks=True have no batched kernels: they are
+    served by forward_test, video by video - same results."""
+    n = len(imgs_list)
+    if len(ref_seg_maps) != n or len(img_metas) != n:
+        raise ValueError(f'forward_test_batch: {n} videos, {len(ref_seg_maps)} label maps, {len(img_metas)} img_metas')
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= 64:
+        raise ValueError(f'forward_test_batch: 1 <= batch <= 64, got {batch!r}')
+    if n == 0:
+        return []
+    for i, imgs in enumerate(imgs_list):
+        if imgs is None or not hasattr(imgs, 'numel') or imgs.numel() == 0:
+            raise ValueError(f'forward_test_batch: video {i} has no frames')
+    tc = tracker.test_cfg
+    precision = eval_precision(tc)
+    if tracker.training:
+        raise RuntimeError('forward_test expects model.eval() (BatchNorm running statistics)')
+    nr = tc.get('neighbor_range', None)
+    with_first = bool(tc.get('with_first', True))
+    precede, topk = int(tc['precede_frames']), int(tc['topk'])
+    if topk > 10 or precede + (1 if with_first else 0) > 64:
+        raise NotImplementedError(f'label propagation kernels: topk <= 10 (got {topk}), precede_frames + first frame <= 64 '
+                                  f'(got {precede + (1 if with_first else 0)})')
+    if precision != 'fp32' or bool(tc.get('all_blocks', False)):
+        return [forward_test_hip(tracker, a, b, c)[0] for a, b, c in zip(imgs_list, ref_seg_maps, img_metas)]
+    cfg = dict(radius=int(nr) // 2 if nr is not None else 0, with_first=with_first, precede=precede, topk=topk, temp=float(tc['temperature']),
+               non_mask_len=0 if tc.get('with_first_neighbor', True) else 1, with_norm=bool(tc.get('with_norm', True)),
+               batch_step=int(tc.get('batch_step', 10)),
+               entries=int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES'))
+    groups = {}
+    for i, (imgs, ref, meta) in enumerate(zip(imgs_list, ref_seg_maps, img_metas)):
+        imgs = imgs.reshape((-1,) + tuple(imgs.shape[2:]))          # [1,3,T,H,W]
+        assert imgs.shape[0] == 1
+        out_h, out_w = meta[0]['original_shape'][:2]
+        key = (imgs.shape[3], imgs.shape[4], ref.ndim == 4, int(out_h), int(out_w), imgs.device)
+        groups.setdefault(key, []).append((i, imgs, ref, int(out_h), int(out_w)))
+    eng = shared_engine()
+    outs = [None] * n
+    for vids in groups.values():
+        _run_group(tracker, eng, cfg, vids, batch, outs)
+    return outs

@@ -681,3 +681,9 @@ class VanillaTracker(BaseTracker):
     def forward_test(self, imgs, ref_seg_map, img_meta):
         from .labelprop import forward_test_hip
         return forward_test_hip(self, imgs, ref_seg_map, img_meta)
+
+    def forward_test_batch(self, imgs_list, ref_seg_maps, img_metas, batch=8):
+        """forward_test of many videos, `batch` of them at a time in lock-step on the device (vfs_amd/labelprop.py):
+        out[i] == forward_test(imgs_list[i], ref_seg_maps[i], img_metas[i])[0]"""
+        from .labelprop import forward_test_batch_hip
+        return forward_test_batch_hip(self, imgs_list, ref_seg_maps, img_metas, batch)
