@@ -12,7 +12,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import vfs_amd                                       # noqa: E402
 from vfs_amd.engine import shared_engine             # noqa: E402
-from vfs_amd.labelprop import extract_features       # noqa: E402
+from vfs_amd.labelprop import extract_feature_levels # noqa: E402
 from vfs_amd.synthetic import synthetic_weights_     # noqa: E402
 
 model_name = sys.argv[1] if len(sys.argv) > 1 else 'r50'
@@ -33,9 +33,7 @@ T, H, W = 22, 480, 854
 g = torch.Generator(device=dev).manual_seed(1234)
 base = torch.randn(1, 3, 1, H, W, device=dev, generator=g)
 imgs = base + 0.15 * torch.randn(1, 3, T, H, W, device=dev, generator=g)       # bench.py's clip
-hls = []
-bank, h, w, C = extract_features(model, eng, imgs, 10, precision='fp32', split_banks=hls)
-hl = hls[0]
+(bank,), (hl,), ((h, w, C),) = extract_feature_levels(model, eng, imgs, 10, precision='fp32')
 CO = 4
 sbank = torch.rand(T, h * w, CO, device=dev)
 radius = int(tc['neighbor_range']) // 2

@@ -33,7 +33,7 @@ for _ in range(2):
     model(imgs, return_loss=False, ref_seg_map=seg_t, img_meta=meta)
 torch.cuda.synchronize()
 
-orig_extract = LP.extract_features
+orig_extract = LP.extract_feature_levels
 marks = {}
 
 
@@ -48,7 +48,7 @@ def timed_extract(*a, **k):
     return r
 
 
-LP.extract_features = timed_extract
+LP.extract_feature_levels = timed_extract
 orig_cpu = torch.Tensor.cpu
 
 

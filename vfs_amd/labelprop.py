@@ -16,6 +16,7 @@ Limits of the kernels (checked, errors raised): topk <= 10, at most 64 key frame
 import ctypes
 import os
 import tempfile
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -26,11 +27,29 @@ from .engine import BF16, shared_engine
 F32 = torch.float32
 
 
-def eval_precision(test_cfg):
-    p = resnet.eval_precision(None if test_cfg is None else test_cfg.get('precision', None))
-    if p not in ('fp32', 'bf16'):
-        raise ValueError(f"test_cfg.precision must be 'fp32' or 'bf16', got {p!r}")
-    return p
+LabelPropConfig = namedtuple('LabelPropConfig', 'precision radius with_first non_mask_len with_norm all_blocks precede topk temp batch_step entries')
+
+
+def labelprop_config(tracker):
+    """tracker.test_cfg as the label propagation reads it (vanilla_tracker.py:133-159), checked against the limits of the kernels"""
+    tc = tracker.test_cfg
+    precision = resnet.eval_precision(None if tc is None else tc.get('precision', None))
+    if precision not in ('fp32', 'bf16'):
+        raise ValueError(f"test_cfg.precision must be 'fp32' or 'bf16', got {precision!r}")
+    if tracker.training:
+        raise RuntimeError('forward_test expects model.eval() (BatchNorm running statistics)')
+    nr = tc.get('neighbor_range', None)
+    with_first = bool(tc.get('with_first', True))
+    precede, topk = int(tc['precede_frames']), int(tc['topk'])
+    if topk > 10 or precede + (1 if with_first else 0) > 64:
+        raise NotImplementedError(f'label propagation kernels: topk <= 10 (got {topk}), precede_frames + first frame <= 64 '
+                                  f'(got {precede + (1 if with_first else 0)})')
+    return LabelPropConfig(
+        precision=precision, radius=int(nr) // 2 if nr is not None else 0,      # radius 0: no spatial mask
+        with_first=with_first, non_mask_len=0 if tc.get('with_first_neighbor', True) else 1,      # vanilla_tracker.py:158-159
+        with_norm=bool(tc.get('with_norm', True)), all_blocks=bool(tc.get('all_blocks', False)), precede=precede, topk=topk,
+        temp=float(tc['temperature']), batch_step=int(tc.get('batch_step', 10)),
+        entries=int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES'))      # list entries per query of the two-pass kernels
 
 
 def pil_nearest_resize(label, out_h, out_w):
@@ -83,18 +102,17 @@ def two_pass_ok(precision, with_norm, C):
     return precision == 'fp32' and with_norm and C in (256, 512, 1024) and knobs.flag('VFS_LP_TWO_PASS')
 
 
-def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, split_banks=None, alloc=None):
-    """imgs [1,3,T,H,W] fp32 -> feature bank [T, h*w, C] of the evaluated stage, L2-normalised over the
-    channels unless with_norm=False (bf16 or fp32 by `precision`); with all_blocks (vanilla_tracker.py:32-45,
-    README.md:76) a LIST of banks, one per residual block of every stage in test_cfg.out_indices.
-    split_banks: a list that receives, per bank, its bf16 hi / lo split copy [T, h*w, 2C] (or None) for the two-pass kernels.
-    alloc(T, rows, channels, dtype): where a bank lives (forward_test_batch: the slot's region of the stacked banks); default: its own tensor."""
+def extract_feature_levels(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, banks=None, split_banks=None):
+    """imgs [1,3,T,H,W] fp32 -> (banks, split_banks, shapes), one entry per feature level: the evaluated stage, or with all_blocks
+    (vanilla_tracker.py:32-45, README.md:76) every residual block of every stage in test_cfg.out_indices.
+    banks[l]        [T, h*w, C], L2-normalised over the channels unless with_norm=False (bf16 or fp32 by `precision`);
+    split_banks[l]  its bf16 hi / lo split copy [T, h*w, 2C] for the two-pass kernels, or None where they do not apply;
+    shapes[l]       (h, w, C).  banks / split_banks: the destinations, if given (forward_test_batch: a slot's views of its stacked banks)"""
     bb = tracker.backbone
     dev = frames_ncthw.device
     _, _, T, H, W = frames_ncthw.shape
     s = eng.stream(dev)
     stages = tuple(tracker.test_cfg.get('out_indices', bb.out_indices))
-    stage = stages[0]
     exact = precision == 'fp32'
     if exact:
         from .exact import exact_state
@@ -103,7 +121,7 @@ def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, p
         bb.attach(eng)
         eng.pack_weights()
     Wp = W + (W & 1)
-    banks, shapes = None, None
+    shapes = None
     for t0 in range(0, T, batch_step):
         n = min(batch_step, T - t0)
         chunk = frames_ncthw[:, :, t0:t0 + n].contiguous().float()
@@ -120,18 +138,15 @@ def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, p
         if all_blocks:          # every block output of the listed stages, in network order
             feats = [block_feats[i] for i in _block_feats(bb, len(block_feats), stages)]
         else:
-            feats = [outs[stage]]
-        if banks is None:
-            if alloc is None:
-                def alloc(T, rows, channels, dtype):
-                    return torch.empty(T, rows, channels, dtype=dtype, device=dev)
-            banks = [alloc(T, h * w, C, F32 if exact else BF16) for (_, h, w, C) in feats]
+            feats = [outs[stages[0]]]
+        if shapes is None:
             shapes = [(h, w, C) for (_, h, w, C) in feats]
-            hls = [alloc(T, h * w, 2 * C, BF16) if two_pass_ok(precision, with_norm, C) else None
-                   for (_, h, w, C) in feats]
-            if split_banks is not None:
-                split_banks.extend(hls)
-        for bank, hl, (feat, h, w, C) in zip(banks, hls, feats):
+            if banks is None:
+                banks = [torch.empty(T, h * w, C, dtype=F32 if exact else BF16, device=dev) for (h, w, C) in shapes]
+                split_banks = [torch.empty(T, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(precision, with_norm, C) else None
+                               for (h, w, C) in shapes]
+            split_banks = split_banks or [None] * len(banks)      # destinations without split copies: the dense kernels
+        for bank, hl, (feat, h, w, C) in zip(banks, split_banks, feats):
             if not with_norm:
                 bank[t0:t0 + n].copy_(feat.reshape(n, h * w, C))
             elif exact:
@@ -140,9 +155,78 @@ def extract_features(tracker, eng, frames_ncthw, batch_step, all_blocks=False, p
                     eng.lib.split_rows_bf16x2(bank[t0:t0 + n], hl[t0:t0 + n], n * h * w, C, s)
             else:
                 eng.lib.l2norm_rows(feat, bank[t0:t0 + n], n * h * w, C, s)
-    if all_blocks:
-        return banks, shapes
-    return banks[0], shapes[0][0], shapes[0][1], shapes[0][2]
+    return banks, split_banks, shapes
+
+
+def extract_features(tracker, eng, frames_ncthw, batch_step, precision='bf16', with_norm=True):
+    """the one feature level of the evaluated stage: -> (bank [T, h*w, C], h, w, C)"""
+    (bank,), _, ((h, w, C),) = extract_feature_levels(tracker, eng, frames_ncthw, batch_step, False, precision, with_norm)
+    return bank, h, w, C
+
+
+def _key_frames(f, precede, with_first, non_mask_len=0):
+    """the key frames of query frame f: the `precede` frames before it, after frame 0 if with_first"""
+    keys = list(range(max(0, f - precede), f))
+    keys = [0] + keys if with_first else keys      # frame 0 twice while f <= precede (as the reference)
+    assert 0 <= non_mask_len < len(keys)           # local_attention.py:272
+    return keys
+
+
+def _first_maps(ref_seg_map, dev):
+    """the reference label map of a video as forward_test reads it (vanilla_tracker.py:94): (4-D) the soft / one-hot map
+    [CO, Hr, Wr] on the device, (3-D) the label map, uint8 on the host - either way of at most 256 classes"""
+    if ref_seg_map.ndim != 4:
+        return ref_seg_map[0].detach().cpu().numpy().astype(np.uint8)
+    if ref_seg_map.shape[1] > 256:
+        raise NotImplementedError('label propagation kernels: at most 256 classes')
+    return ref_seg_map[0].detach().to(dev, F32).contiguous()
+
+
+def _at_feature_size(ref, h, w):
+    """a video's reference map (_first_maps) at feature size -> (h, w, class count, the label map PIL-nearest resized / None for a soft map)"""
+    if torch.is_tensor(ref):
+        return h, w, ref.shape[0], None
+    small = pil_nearest_resize(ref, h, w)
+    return h, w, int(small.max()) + 1, small       # F.one_hot infers max+1 classes
+
+
+def _first_frame(eng, ref, feat, rows0, out_size, pred0):
+    """a video's reference map (_first_maps) -> frame 0 of its label rows `rows0` (feat: _at_feature_size; both None: not wanted) and of
+    its predictions `pred0` (original size `out_size`).  A soft map is resized bilinearly to both, and the soft maps of the later
+    frames are returned as they are, without min-max / argmax; a label map goes one-hot into the rows and torch-nearest into the
+    prediction (vanilla_tracker.py:101-111,167; pred0 None: only returned).  -> the map at the original size: pred0 (soft), on the host (labels)"""
+    out_h, out_w = out_size
+    if torch.is_tensor(ref):
+        s = eng.stream(pred0.device)
+        CO, hr, wr = ref.shape
+        if rows0 is not None:
+            eng.lib.bilinear_resize_f32(ref, rows0, CO, hr, wr, feat[0], feat[1], 0, 1, s)
+        eng.lib.bilinear_resize_f32(ref, pred0, CO, hr, wr, out_h, out_w, 0, 0, s)
+        return pred0
+    if rows0 is not None:
+        h, w, CO, small = feat
+        eng.lib.onehot(torch.from_numpy(np.ascontiguousarray(small)).to(rows0.device), rows0, h * w, CO, eng.stream(rows0.device))
+    big = np.ascontiguousarray(torch_nearest_resize(ref, out_h, out_w))
+    if pred0 is not None:
+        pred0.copy_(torch.from_numpy(big).to(pred0.device).reshape(pred0.shape))
+    return big
+
+
+def _workspace_bytes(lib, h, w, two_pass, entries, nslots=None):
+    """workspace bytes of the dense or the two-pass kernels (`entries` list entries per query, <= 0: the library's own), one video or `nslots` slots"""
+    nbytes = torch.zeros(1, dtype=torch.int64)
+    if nslots is None:
+        if not two_pass:
+            lib.labelprop_workspace_bytes(h, w, nbytes)
+        elif entries > 0:
+            lib.labelprop_f32_2pass_workspace_bytes_for(h, w, entries, nbytes)
+        else:
+            lib.labelprop_f32_2pass_workspace_bytes(h, w, nbytes)
+    elif two_pass:
+        lib.labelprop_f32_2pass_batch_workspace_bytes(h, w, max(0, entries), nslots, nbytes)
+    else:
+        lib.labelprop_f32_batch_workspace_bytes(h, w, nslots, nbytes)
+    return int(nbytes.item())
 
 
 def _result(tracker, arr):
@@ -157,103 +241,58 @@ def _result(tracker, arr):
 
 
 def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
-    tc = tracker.test_cfg
+    return _forward_test(tracker, labelprop_config(tracker), imgs, ref_seg_map, img_meta)
+
+
+def _forward_test(tracker, cfg, imgs, ref_seg_map, img_meta):
     eng = shared_engine()
-    precision = eval_precision(tc)
-    exact = precision == 'fp32'
+    exact = cfg.precision == 'fp32'
     imgs = imgs.reshape((-1,) + tuple(imgs.shape[2:]))          # [1,3,T,H,W]
     assert imgs.shape[0] == 1
     dev = imgs.device
     clip_len = imgs.size(2)
-    if tracker.training:
-        raise RuntimeError('forward_test expects model.eval() (BatchNorm running statistics)')
-    nr = tc.get('neighbor_range', None)
-    radius = int(nr) // 2 if nr is not None else 0
-    with_first = bool(tc.get('with_first', True))
-    non_mask_len = 0 if tc.get('with_first_neighbor', True) else 1      # vanilla_tracker.py:158-159
-    with_norm = bool(tc.get('with_norm', True))
-    all_blocks = bool(tc.get('all_blocks', False))
-    precede = int(tc['precede_frames'])
-    topk, temp = int(tc['topk']), float(tc['temperature'])
-    if topk > 10 or precede + (1 if with_first else 0) > 64:
-        raise NotImplementedError(f'label propagation kernels: topk <= 10 (got {topk}), precede_frames + first frame <= 64 '
-                                  f'(got {precede + (1 if with_first else 0)})')
-    hls = []
-    if all_blocks:
-        banks, shapes = extract_features(tracker, eng, imgs, int(tc.get('batch_step', 10)), True, precision, with_norm, hls)
-    else:
-        bank, h, w, C = extract_features(tracker, eng, imgs, int(tc.get('batch_step', 10)), False, precision, with_norm, hls)
-        banks, shapes = [bank], [(h, w, C)]
+    banks, hls, shapes = extract_feature_levels(tracker, eng, imgs, cfg.batch_step, cfg.all_blocks, cfg.precision, cfg.with_norm)
     s = eng.stream(dev)
     out_h, out_w = img_meta[0]['original_shape'][:2]
-    input_onehot = ref_seg_map.ndim == 4                         # vanilla_tracker.py:94
-    if input_onehot:
-        ref = ref_seg_map[0].detach().to(dev, F32).contiguous()  # [CO, Hr, Wr] soft / one-hot map
-    else:
-        ref = ref_seg_map[0].detach().cpu().numpy().astype(np.uint8)
+    ref = _first_maps(ref_seg_map, dev)
+    soft = torch.is_tensor(ref)
+    radius, non_mask_len, topk, temp = cfg.radius, cfg.non_mask_len, cfg.topk, cfg.temp
     lp = eng.lib.labelprop_f32 if exact else eng.lib.labelprop
     post = eng.lib.seg_postprocess_exact if exact else eng.lib.seg_postprocess
     all_preds = []
     for bank, hl, (h, w, C) in zip(banks, hls, shapes):
-        if input_onehot:
-            # bilinear to the feature size (values) and to the original size (frame 0 of the output); the soft maps of
-            # the later frames are returned as they are, without min-max / argmax (vanilla_tracker.py:101-111,167)
-            CO, hr, wr = ref.shape
-            sbank = torch.zeros(clip_len, h * w, CO, dtype=F32, device=dev)
-            eng.lib.bilinear_resize_f32(ref, sbank[0], CO, hr, wr, h, w, 0, 1, s)
-            preds = torch.empty(clip_len, CO, out_h, out_w, dtype=F32, device=dev)
-            eng.lib.bilinear_resize_f32(ref, preds[0], CO, hr, wr, out_h, out_w, 0, 0, s)
-            ref = preds[0].clone()            # the reference keeps the resized map for the next feature level
-        else:
-            small = pil_nearest_resize(ref, h, w)
-            CO = int(small.max()) + 1                                    # F.one_hot infers max+1 classes
-            sbank = torch.zeros(clip_len, h * w, CO, dtype=F32, device=dev)
-            eng.lib.onehot(torch.from_numpy(np.ascontiguousarray(small)).to(dev), sbank[0], h * w, CO, s)
-            preds = torch.empty(clip_len, out_h, out_w, dtype=torch.uint8, device=dev)
-            ref = np.ascontiguousarray(torch_nearest_resize(ref, out_h, out_w))    # vanilla_tracker.py:101-104 (kept, as there)
-            preds[0] = torch.from_numpy(ref).to(dev)
-        if CO > 256:
-            raise NotImplementedError('label propagation kernels: at most 256 classes')
+        _, _, CO, _ = feat = _at_feature_size(ref, h, w)
+        sbank = torch.zeros(clip_len, h * w, CO, dtype=F32, device=dev)
+        shape = (clip_len, CO, out_h, out_w) if soft else (clip_len, out_h, out_w)
+        preds = torch.empty(shape, dtype=F32 if soft else torch.uint8, device=dev)
+        first = _first_frame(eng, ref, feat, sbank[0], (out_h, out_w), preds[0])
+        ref = first.clone() if soft else first          # the reference keeps the resized map for the next feature level
         pairs = mask_pairs(h, w, radius)
         partial = eng.ws('ws.segpost', 64 * CO * 2, F32, dev)
-        nbytes = torch.zeros(1, dtype=torch.int64)
-        entries = int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES')      # list entries per query of the two-pass kernels
-        if hl is None:
-            eng.lib.labelprop_workspace_bytes(h, w, nbytes)
-        elif entries > 0:
-            eng.lib.labelprop_f32_2pass_workspace_bytes_for(h, w, entries, nbytes)
-        else:
-            eng.lib.labelprop_f32_2pass_workspace_bytes(h, w, nbytes)
-        lpws = eng.ws('ws.labelprop', (int(nbytes.item()) + 3) // 4, F32, dev)
+        lpws = eng.ws('ws.labelprop', (_workspace_bytes(eng.lib, h, w, hl is not None, cfg.entries) + 3) // 4, F32, dev)
         for f in range(1, clip_len):
-            key_start = max(0, f - precede)
-            slots = list(range(key_start, f))
-            if with_first:
-                slots = [0] + slots                                 # frame 0 twice while f <= precede (as the reference)
-            assert 0 <= non_mask_len < len(slots)                   # local_attention.py:272
-            ks = (ctypes.c_int * len(slots))(*slots)
-            nmask = len(slots) - non_mask_len
+            keys = _key_frames(f, cfg.precede, cfg.with_first, non_mask_len)
+            ks = (ctypes.c_int * len(keys))(*keys)
+            nmask = len(keys) - non_mask_len
             work = (2.0 * C * (nmask * pairs + non_mask_len * float(h * w) ** 2),          # in-mask affinity FLOP
-                    float(bank.element_size()) * (len(set(slots)) + 1) * h * w * C)         # every key / query row once
+                    float(bank.element_size()) * (len(set(keys)) + 1) * h * w * C)          # every key / query row once
             if hl is not None:      # same label maps, bit for bit (csrc/labelprop2.hip); algorithmic work as SURVEY section 8(d) counts it:
                 # ONE product per in-mask (query, key, channel) (the kernel EXECUTES three bf16 products for it - hi.hi + hi.lo + lo.hi:
                 # bench.py reports that as executed_frac) and every key / query row once in both copies (fp32 + split)
                 eng.timed('labelprop_2pass', (work[0], 2.0 * work[1]), dev, eng.lib.labelprop_f32_2pass, bank, hl, sbank, sbank[f], lpws, lpws.numel() * 4, f, ks,
-                          len(slots), h, w, C, CO, radius, non_mask_len, topk, temp, 1, s)
+                          len(keys), h, w, C, CO, radius, non_mask_len, topk, temp, 1, s)
             else:
-                eng.timed('labelprop_f32' if exact else 'labelprop', work, dev, lp, bank, sbank, sbank[f], lpws, lpws.numel() * 4, f, ks, len(slots), h, w,
+                eng.timed('labelprop_f32' if exact else 'labelprop', work, dev, lp, bank, sbank, sbank[f], lpws, lpws.numel() * 4, f, ks, len(keys), h, w,
                           C, CO, radius, non_mask_len, topk, temp, s)
-            if input_onehot:
+            if soft:
                 eng.lib.bilinear_resize_f32(sbank[f], preds[f], CO, h, w, out_h, out_w, 1, 0, s)
             else:
                 eng.timed('seg_postprocess', (0.0, 4.0 * h * w * CO + float(out_h * out_w)), dev, post, sbank[f], partial, preds[f],
                           h, w, CO, out_h, out_w, s)
         all_preds.append(_result(tracker, preds.cpu().numpy()))
-    if tracker.save_np:
-        return [all_preds] if len(all_preds) > 1 else [all_preds[0]]
-    if len(all_preds) > 1:      # vanilla_tracker.py:199-205: [1, num_feats, T, ...] unravelled over the batch dim
-        return [np.stack(all_preds, axis=0)]
-    return [all_preds[0]]
+    if len(all_preds) > 1:      # vanilla_tracker.py:199-205: [1, num_feats, T, ...] unravelled over the batch dim (save_np: the paths)
+        return [all_preds if tracker.save_np else np.stack(all_preds, axis=0)]
+    return all_preds
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -266,11 +305,6 @@ def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
 # count - is worked out on the host first and uploaded ONCE as the descriptor table the kernels read (include/vfs_hip.h); inside the
 # step loop nothing is read back and nothing but a newly admitted video's frames and first label map goes to the device.
 DESC_INTS = 72      # include/vfs_hip.h VFS_LPB_DESC_INTS
-
-
-def _key_frames(f, precede, with_first):
-    keys = list(range(max(0, f - precede), f))
-    return [0] + keys if with_first else keys      # frame 0 twice while f <= precede (as the reference)
 
 
 def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_len):
@@ -294,8 +328,7 @@ def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_
             if sl is None:
                 continue
             v, f = sl
-            keys = _key_frames(f, precede, with_first)
-            assert 0 <= non_mask_len < len(keys)                    # local_attention.py:272
+            keys = _key_frames(f, precede, with_first, non_mask_len)
             row[n, :5] = (1, f, len(keys), non_mask_len, class_counts[v])
             row[n, 8:8 + len(keys)] = keys
             most = max(most, len(keys))
@@ -309,113 +342,80 @@ def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_
     return table, steps
 
 
-def _first_maps(ref_seg_map, dev):
-    """the reference label map of a video as forward_test reads it: (4-D) the soft map on the device, (3-D) uint8 on the host"""
-    if ref_seg_map.ndim == 4:
-        return ref_seg_map[0].detach().to(dev, F32).contiguous()
-    return ref_seg_map[0].detach().cpu().numpy().astype(np.uint8)
+class _Group:
+    """videos of ONE frame size, label-map kind and output size (each of >= 2 frames) in lock-step: the stacked banks of B slots
+    (layout: include/vfs_hip.h), the workspace and the schedule with its descriptor table on the device"""
 
-
-def _run_group(tracker, eng, cfg, vids, batch, outs):
-    """vids: [(index, imgs [1,3,T,H,W], ref_seg_map, out_h, out_w)] of ONE frame size, label-map kind and output size"""
-    lib = eng.lib
-    dev = vids[0][1].device
-    s = eng.stream(dev)
-    soft = vids[0][2].ndim == 4
-    out_h, out_w = vids[0][3], vids[0][4]
-    refs = [_first_maps(v[2], dev) for v in vids]
-    if soft and max(r.shape[0] for r in refs) > 256:
-        raise NotImplementedError('label propagation kernels: at most 256 classes')
-    single = [i for i, v in enumerate(vids) if v[1].size(2) == 1]
-    for i in single:      # a one-frame clip is its (resized) reference map
-        if soft:
-            first = torch.empty(1, refs[i].shape[0], out_h, out_w, dtype=F32, device=dev)
-            lib.bilinear_resize_f32(refs[i], first[0], refs[i].shape[0], refs[i].shape[1], refs[i].shape[2], out_h, out_w, 0, 0, s)
-            outs[vids[i][0]] = _result(tracker, first.cpu().numpy())
+    def __init__(self, tracker, eng, cfg, videos, ref_seg_maps, out_size, batch):
+        """videos: [imgs [1,3,T,H,W]] in the order of admission"""
+        self.tracker, self.eng, self.cfg, self.videos, self.out_size = tracker, eng, cfg, videos, out_size
+        dev = videos[0].device
+        out_h, out_w = out_size
+        self.refs = [_first_maps(r, dev) for r in ref_seg_maps]
+        self.soft = torch.is_tensor(self.refs[0])
+        self.lengths = [int(v.size(2)) for v in videos]
+        B, Tcap = self.B, self.Tcap = min(batch, len(videos)), max(self.lengths)
+        # the stacked banks can be sized only when a feature map is known: video 0 is extracted into tensors of its own, which admit()
+        # copies into its slot - one device-to-device copy per group, the same launches as extracting into the slot
+        self.first = extract_feature_levels(tracker, eng, videos[0], cfg.batch_step, False, 'fp32', cfg.with_norm)
+        h, w, C = self.h, self.w, self.C = self.first[2][0]
+        self.fb = torch.empty(B, Tcap, h * w, C, dtype=F32, device=dev)
+        self.hl = torch.empty(B, Tcap, h * w, 2 * C, dtype=BF16, device=dev) if self.first[1][0] is not None else None
+        self.feats = [_at_feature_size(ref, h, w) for ref in self.refs]
+        self.cos = [feat[2] for feat in self.feats]
+        COcap = self.COcap = max(self.cos)
+        self.sb = torch.empty(B, Tcap * h * w * COcap, dtype=F32, device=dev)      # label rows, packed per slot with the slot's class count
+        if self.soft:
+            self.preds = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
         else:
-            outs[vids[i][0]] = _result(tracker, np.ascontiguousarray(torch_nearest_resize(refs[i], out_h, out_w))[None])
-    run = [i for i in range(len(vids)) if i not in set(single)]
-    if not run:
-        return
-    B = min(batch, len(run))
-    lengths = [int(vids[i][1].size(2)) for i in run]
-    Tcap = max(lengths)
-    g = {}      # the group's banks: allocated when the first video's feature map is known
-    cur = [0]   # the slot being admitted
+            self.preds = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
+            self.partial = eng.ws('ws.segpost_batch', B * 64 * COcap * 2, F32, dev)
+        nbytes = _workspace_bytes(eng.lib, h, w, self.hl is not None, cfg.entries, B)
+        self.ws = torch.empty((nbytes + 3) // 4, dtype=F32, device=dev)      # (per group: released with it)
+        table, self.steps = batch_schedule(self.lengths, self.cos, B, cfg.precede, cfg.with_first, cfg.non_mask_len)
+        self.table = torch.from_numpy(table).to(dev)      # the ONE upload of the schedule
 
-    def alloc(T, rows, channels, dtype):
-        key = 'hl' if dtype == BF16 else 'fb'
-        if key not in g:
-            g[key] = torch.empty(B, Tcap, rows, channels, dtype=dtype, device=dev)
-        return g[key][cur[0], :T]
+    def admit(self, n, k):
+        """video k enters slot n: its features, and frame 0 of its label rows and predictions"""
+        T, CO, cfg = self.lengths[k], self.cos[k], self.cfg
+        fb, hl = self.fb[n, :T], None if self.hl is None else self.hl[n, :T]
+        if self.first is not None:      # video 0 (always the first admitted)
+            fb.copy_(self.first[0][0])
+            if hl is not None:
+                hl.copy_(self.first[1][0])
+            self.first = None
+        else:
+            extract_feature_levels(self.tracker, self.eng, self.videos[k], cfg.batch_step, False, 'fp32', cfg.with_norm, [fb], [hl])
+        out_h, out_w = self.out_size
+        pred0 = self.preds[n, :CO * out_h * out_w] if self.soft else self.preds[n, 0]
+        _first_frame(self.eng, self.refs[k], self.feats[k], self.sb[n, :self.h * self.w * CO], self.out_size, pred0)
 
-    def features(n, i):
-        cur[0] = n
-        return extract_features(tracker, eng, vids[i][1], cfg['batch_step'], False, 'fp32', cfg['with_norm'], [], alloc)[1:]
+    def step(self, i):
+        """one launch set: every active slot propagates to and post-processes its frame of row i of the schedule"""
+        lib, cfg, ws, row = self.eng.lib, self.cfg, self.ws, self.table[i]
+        _, _, nactive, most = self.steps[i]
+        B, Tcap, h, w, C, COcap = self.B, self.Tcap, self.h, self.w, self.C, self.COcap
+        out_h, out_w = self.out_size
+        s = self.eng.stream(row.device)
+        if self.hl is not None:
+            lib.labelprop_f32_2pass_batch(self.fb, self.hl, self.sb, ws, ws.numel() * 4, row, B, nactive, most, Tcap, h, w, C, COcap,
+                                          cfg.radius, cfg.topk, cfg.temp, 1, s)
+        else:
+            lib.labelprop_f32_batch(self.fb, self.sb, ws, ws.numel() * 4, row, B, nactive, most, Tcap, h, w, C, COcap, cfg.radius,
+                                    cfg.topk, cfg.temp, s)
+        if self.soft:
+            lib.bilinear_resize_f32_batch(self.sb, self.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
+        else:
+            lib.seg_postprocess_exact_batch(self.sb, self.partial, self.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
 
-    def set_up(h, w, C):
-        """everything that needs the feature-map size: class counts, label / prediction banks, workspace, the schedule"""
-        hw = h * w
-        g['small'] = [None if soft else pil_nearest_resize(refs[i], h, w) for i in run]
-        cos = [refs[i].shape[0] if soft else int(sm.max()) + 1 for i, sm in zip(run, g['small'])]      # F.one_hot infers max+1 classes
-        COcap = max(cos)
-        g.update(h=h, w=w, C=C, cos=cos, COcap=COcap)
-        g['sb'] = torch.empty(B, Tcap * hw * COcap, dtype=F32, device=dev)
-        if soft:
-            g['preds'] = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
+    def retire(self, n, k):
+        """-> the maps of video k, which ended in slot n: they leave the device now, the slot is refilled at the next step"""
+        T, CO, (out_h, out_w) = self.lengths[k], self.cos[k], self.out_size
+        if self.soft:
+            arr = self.preds[n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
         else:
-            g['preds'] = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
-            g['partial'] = eng.ws('ws.segpost_batch', B * 64 * COcap * 2, F32, dev)
-        nbytes = torch.zeros(1, dtype=torch.int64)
-        if 'hl' in g:
-            lib.labelprop_f32_2pass_batch_workspace_bytes(h, w, max(0, cfg['entries']), B, nbytes)
-        else:
-            lib.labelprop_f32_batch_workspace_bytes(h, w, B, nbytes)
-        g['ws'] = torch.empty((int(nbytes.item()) + 3) // 4, dtype=F32, device=dev)      # (per group: released with it)
-        table, steps = batch_schedule(lengths, cos, B, cfg['precede'], cfg['with_first'], cfg['non_mask_len'])
-        g['table'] = torch.from_numpy(table).to(dev)      # the ONE upload of the schedule
-        return steps
-
-    def first_frame(n, k):
-        """the video's reference map -> frame 0 of the slot's label rows (feature size) and of its predictions (original size)"""
-        i, h, w, CO = run[k], g['h'], g['w'], g['cos'][k]
-        hw = h * w
-        rows0 = g['sb'][n, :hw * CO]
-        if soft:
-            ref = refs[i]
-            lib.bilinear_resize_f32(ref, rows0, CO, ref.shape[1], ref.shape[2], h, w, 0, 1, s)
-            lib.bilinear_resize_f32(ref, g['preds'][n, :CO * out_h * out_w], CO, ref.shape[1], ref.shape[2], out_h, out_w, 0, 0, s)
-        else:
-            lib.onehot(torch.from_numpy(np.ascontiguousarray(g['small'][k])).to(dev), rows0, hw, CO, s)
-            g['preds'][n, 0] = torch.from_numpy(np.ascontiguousarray(torch_nearest_resize(refs[i], out_h, out_w))).to(dev).reshape(-1)
-
-    # the first video's features give the feature-map size; from there on the schedule is fixed
-    h, w, C = features(0, run[0])
-    steps = set_up(h, w, C)
-    hl, ws, table = g.get('hl'), g['ws'], g['table']
-    for step, (admitted, retired, nactive, most) in enumerate(steps):
-        for n, k in admitted:
-            if (step, n) != (0, 0):
-                features(n, run[k])
-            first_frame(n, k)
-        if hl is not None:
-            lib.labelprop_f32_2pass_batch(g['fb'], hl, g['sb'], ws, ws.numel() * 4, table[step], B, nactive, most, Tcap, h, w, C, g['COcap'],
-                                          cfg['radius'], cfg['topk'], cfg['temp'], 1, s)
-        else:
-            lib.labelprop_f32_batch(g['fb'], g['sb'], ws, ws.numel() * 4, table[step], B, nactive, most, Tcap, h, w, C, g['COcap'], cfg['radius'],
-                                    cfg['topk'], cfg['temp'], s)
-        if soft:
-            lib.bilinear_resize_f32_batch(g['sb'], g['preds'], table[step], B, Tcap, h, w, g['COcap'], out_h, out_w, s)
-        else:
-            lib.seg_postprocess_exact_batch(g['sb'], g['partial'], g['preds'], table[step], B, Tcap, h, w, g['COcap'], out_h, out_w, s)
-        for n, k in retired:      # the video's maps leave the device now; its slot is refilled at the next step
-            T, CO = lengths[k], g['cos'][k]
-            if soft:
-                arr = g['preds'][n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
-            else:
-                arr = g['preds'][n, :T].reshape(T, out_h, out_w)
-            arr = arr.cpu().numpy() if dev.type != 'cpu' else arr.numpy().copy()      # (the slot's maps are overwritten by the next video)
-            outs[vids[run[k]][0]] = _result(tracker, arr)
+            arr = self.preds[n, :T].reshape(T, out_h, out_w)
+        return arr.cpu().numpy() if arr.device.type != 'cpu' else arr.numpy().copy()      # (the slot's maps are overwritten by the next video)
 
 
 def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8):
@@ -433,31 +433,30 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8)
     for i, imgs in enumerate(imgs_list):
         if imgs is None or not hasattr(imgs, 'numel') or imgs.numel() == 0:
             raise ValueError(f'forward_test_batch: video {i} has no frames')
-    tc = tracker.test_cfg
-    precision = eval_precision(tc)
-    if tracker.training:
-        raise RuntimeError('forward_test expects model.eval() (BatchNorm running statistics)')
-    nr = tc.get('neighbor_range', None)
-    with_first = bool(tc.get('with_first', True))
-    precede, topk = int(tc['precede_frames']), int(tc['topk'])
-    if topk > 10 or precede + (1 if with_first else 0) > 64:
-        raise NotImplementedError(f'label propagation kernels: topk <= 10 (got {topk}), precede_frames + first frame <= 64 '
-                                  f'(got {precede + (1 if with_first else 0)})')
-    if precision != 'fp32' or bool(tc.get('all_blocks', False)):
-        return [forward_test_hip(tracker, a, b, c)[0] for a, b, c in zip(imgs_list, ref_seg_maps, img_metas)]
-    cfg = dict(radius=int(nr) // 2 if nr is not None else 0, with_first=with_first, precede=precede, topk=topk, temp=float(tc['temperature']),
-               non_mask_len=0 if tc.get('with_first_neighbor', True) else 1, with_norm=bool(tc.get('with_norm', True)),
-               batch_step=int(tc.get('batch_step', 10)),
-               entries=int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES'))
-    groups = {}
-    for i, (imgs, ref, meta) in enumerate(zip(imgs_list, ref_seg_maps, img_metas)):
-        imgs = imgs.reshape((-1,) + tuple(imgs.shape[2:]))          # [1,3,T,H,W]
-        assert imgs.shape[0] == 1
-        out_h, out_w = meta[0]['original_shape'][:2]
-        key = (imgs.shape[3], imgs.shape[4], ref.ndim == 4, int(out_h), int(out_w), imgs.device)
-        groups.setdefault(key, []).append((i, imgs, ref, int(out_h), int(out_w)))
+    cfg = labelprop_config(tracker)
+    if cfg.precision != 'fp32' or cfg.all_blocks:
+        return [_forward_test(tracker, cfg, a, b, c)[0] for a, b, c in zip(imgs_list, ref_seg_maps, img_metas)]
     eng = shared_engine()
     outs = [None] * n
-    for vids in groups.values():
-        _run_group(tracker, eng, cfg, vids, batch, outs)
+    groups = {}
+    for i, (imgs, ref_seg_map, meta) in enumerate(zip(imgs_list, ref_seg_maps, img_metas)):
+        imgs = imgs.reshape((-1,) + tuple(imgs.shape[2:]))          # [1,3,T,H,W]
+        assert imgs.shape[0] == 1
+        soft, dev = ref_seg_map.ndim == 4, imgs.device
+        out_h, out_w = (int(v) for v in meta[0]['original_shape'][:2])
+        if imgs.size(2) > 1:
+            groups.setdefault((imgs.shape[3], imgs.shape[4], soft, out_h, out_w, dev), []).append((i, imgs, ref_seg_map))
+            continue
+        ref = _first_maps(ref_seg_map, dev)      # a one-frame clip is its (resized) reference map
+        pred0 = torch.empty(ref.shape[0], out_h, out_w, dtype=F32, device=dev) if soft else None
+        first = _first_frame(eng, ref, None, None, (out_h, out_w), pred0)
+        outs[i] = _result(tracker, (first.cpu().numpy() if soft else first)[None])
+    for (_, _, _, out_h, out_w, _), vids in groups.items():
+        group = _Group(tracker, eng, cfg, [v[1] for v in vids], [v[2] for v in vids], (out_h, out_w), batch)
+        for step, (admitted, retired, _, _) in enumerate(group.steps):
+            for slot, k in admitted:
+                group.admit(slot, k)
+            group.step(step)
+            for slot, k in retired:
+                outs[vids[k][0]] = _result(tracker, group.retire(slot, k))
     return outs
