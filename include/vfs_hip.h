@@ -616,6 +616,19 @@ int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t*
                                     int W, int COcap, int Ho, int Wo, vfs_stream_t stream);
 int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap,
                                   int Ho, int Wo, vfs_stream_t stream);
+/* The same lock-step for the bf16 kernels (test_cfg.precision = 'bf16'): vfs_labelprop_batch is one step of vfs_labelprop in every
+ * slot, vfs_seg_postprocess_batch one vfs_seg_postprocess of every active slot's propagated frame (soft maps: vfs_bilinear_resize_f32_batch,
+ * which does not depend on the precision).  Banks, descriptor rows, preds and partial as above, with fbank bf16 [nslots][Tcap][H*W][C]
+ * and no split copy; workspace per slot: vfs_labelprop_batch_workspace_bytes(H, W, nslots).  The bf16 top-k keeps the first of equal
+ * scores, so the order candidates arrive in belongs to the result: every slot splits its key frames over workgroups exactly as
+ * vfs_labelprop does for that slot's nkeys, whatever nactive and max_nkeys are (max_nkeys sizes the grid), and its output has the bits
+ * of the single-video call.  Limits as vfs_labelprop: C % 64 == 0, topk <= 10, max_nkeys <= 64. */
+int vfs_labelprop_batch_workspace_bytes(int H, int W, int nslots, long long* bytes);
+int vfs_labelprop_batch(const vfs_bf16* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots,
+                        int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk, float temperature,
+                        vfs_stream_t stream);
+int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                              int COcap, int Ho, int Wo, vfs_stream_t stream);
 
 /* ---- DAVIS-2017 semi-supervised J&F (datasets/davis_dataset.py:68-140 -> davis2017.evaluation) -----
  * pred / gt: uint8 label maps [T][H][W]; frames 1..T-2 are evaluated (first = given, last excluded);

@@ -1,12 +1,13 @@
 """Label propagation of many videos: forward_test one video after another against VanillaTracker.forward_test_batch.
 
-Synthetic clips, ResNet-18, the shipped test-time test_cfg (configs/vfs_r18.py), precision fp32:
+Synthetic clips, ResNet-18, the shipped test-time test_cfg (configs/vfs_r18.py) with --precision {fp32,bf16} and --all-blocks:
   jhmdb   240 x 320, 40 frames, 16-channel soft maps (30 x 40 features: one video does not fill the chip)
   davis   480 x 854, 30 frames, 3-D label maps (60 x 107 features)
 Arms: the per-video loop (forward_test, unchanged code) and forward_test_batch with batch = 1, 4, 8, 16, alternating inside every
 repeat on one box; the median over the repeats, the spread (min .. max) and whether the batch's maps equal the loop's are reported.
 
-  python tools/bench_labelprop_batch.py [--case jhmdb davis] [--videos 16] [--repeats 3] [--out FILE.json]"""
+  python tools/bench_labelprop_batch.py [--case jhmdb davis] [--precision bf16] [--all-blocks] [--videos 16] [--repeats 3]
+                                        [--arms loop batch] [--out FILE.json]"""
 import argparse
 import json
 import os
@@ -48,6 +49,10 @@ def main():
     ap.add_argument('--videos', type=int, default=16)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4, 8, 16])
+    ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
+    ap.add_argument('--all-blocks', action='store_true', help='test_cfg.all_blocks: every residual block of the evaluated stage')
+    ap.add_argument('--arms', nargs='+', default=['loop', 'batch'], choices=['loop', 'batch'],
+                    help='loop alone: the per-video path, e.g. of an older checkout whose forward_test_batch falls back to it')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import vfs_amd
@@ -55,6 +60,7 @@ def main():
     dev = torch.device('cuda:0')
     cfg = vfs_amd.Config.fromfile(os.path.join(REPO, 'configs', 'vfs_r18.py'))
     tc = vfs_amd.ConfigDict(cfg.test_cfg)
+    tc['precision'], tc['all_blocks'] = args.precision, args.all_blocks
     bb = dict(cfg.model['backbone'])
     bb['out_indices'], bb['strides'] = tc['out_indices'], tc['strides']
     torch.manual_seed(0)
@@ -74,14 +80,16 @@ def main():
 
         def loop():
             return [model(a, return_loss=False, ref_seg_map=b, img_meta=c)[0] for a, b, c in zip(imgs_list, refs, metas)]
-        arms = [('per-video loop', loop)] + [(f'batch={b}', (lambda b=b: model.forward_test_batch(imgs_list, refs, metas, batch=b)))
-                                             for b in args.batches]
+        arms = [('per-video loop', loop)] if 'loop' in args.arms else []
+        if 'batch' in args.arms:
+            arms += [(f'batch={b}', (lambda b=b: model.forward_test_batch(imgs_list, refs, metas, batch=b))) for b in args.batches]
         want = loop()      # warm-up of every arm; the batch's maps against the loop's
         equal = {}
-        for arm, fn in arms[1:]:
-            got = fn()
-            equal[arm] = all(np.array_equal(a, b) for a, b in zip(got, want))
-            del got
+        for arm, fn in arms:
+            if arm != 'per-video loop':
+                got = fn()
+                equal[arm] = all(np.array_equal(a, b) for a, b in zip(got, want))
+                del got
         times = {arm: [] for arm, _ in arms}
         for _ in range(args.repeats):
             for arm, fn in arms:      # alternating: clock and thermal drift hit every arm alike
@@ -93,7 +101,7 @@ def main():
         for arm, _ in arms:
             ts = sorted(times[arm])
             med = ts[len(ts) // 2]
-            row = dict(case=name, arm=arm, videos=args.videos, frames_per_video=case['frames'], size=list(case['size']),
+            row = dict(case=name, arm=arm, precision=args.precision, all_blocks=args.all_blocks, videos=args.videos, frames_per_video=case['frames'], size=list(case['size']),
                        videos_per_s=round(args.videos / med, 3), ms_per_frame=round(1e3 * med / frames, 4),
                        ms_per_frame_min=round(1e3 * ts[0] / frames, 4), ms_per_frame_max=round(1e3 * ts[-1] / frames, 4),
                        repeats=args.repeats, equals_loop=equal.get(arm))

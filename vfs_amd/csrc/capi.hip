@@ -1066,13 +1066,44 @@ int vfs_labelprop_f32_2pass_batch(const float* fbank, const vfs_bf16* hlbank, fl
   // the dense kernels behind them: a slot whose lists overflowed is redone, the workgroups of the others leave at once
   return vfs_labelprop_f32_batch_launch(b, nactive, stream_of(stream));
 }
+// the bf16 kernels (labelprop.hip): the dense workspace per slot, the split of every slot as its single-video call chooses it
+int vfs_labelprop_batch_workspace_bytes(int H, int W, int nslots, long long* bytes) {
+  if (!bytes || H <= 0 || W <= 0 || nslots < 1 || nslots > LPB_MAX_SLOTS) return vfs_set_error(VFS_ERR_ARG, "labelprop_batch_workspace_bytes: bad argument");
+  *bytes = nslots * lpb_round(lp_workspace_need(H, W));
+  return VFS_OK;
+}
+int vfs_labelprop_batch(const vfs_bf16* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots, int nactive,
+                        int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk, float temperature, vfs_stream_t stream) {
+  if (int rc = lpb_check("labelprop_batch", fbank, sbank, workspace, desc, nslots, nactive, max_nkeys, Tcap, H, W, C, COcap, topk)) return rc;
+  if (C % 64) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: C%64");
+  if ((long long)H * W > 0x7fffffff / LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: nkeys * H * W must fit the int candidate ids");
+  if (!(temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_batch: temperature > 0");
+  const long long stride = lpb_round(lp_workspace_need(H, W));
+  if (workspace_bytes < nslots * stride)
+    return vfs_set_error(VFS_ERR_ARG, "labelprop_batch: workspace smaller than vfs_labelprop_batch_workspace_bytes(H, W, nslots)");
+  if (nactive == 0) return VFS_OK;
+  LpBatchArgs b = lpb_args(nullptr, nullptr, sbank, (char*)workspace, stride, nullptr, desc, nslots, max_nkeys, Tcap, H, W, C, COcap, radius, topk,
+                           temperature);
+  b.fbank16 = fbank; b.inv_temp = 1.0f / temperature;
+  return vfs_labelprop_batch_launch(b, stream_of(stream));
+}
+static int seg_post_batch_check(const char* who, const void* sbank, const void* partial, const void* preds, const int* desc, int nslots, int Tcap,
+                                int H, int W, int COcap, int Ho, int Wo) {
+  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
+    return fail(VFS_ERR_SHAPE, who, "H, W, Ho, Wo, Tcap >= 1, 1 <= classes <= 256, 1 <= nslots <= 64");
+  if ((long long)Ho * Wo > 0x7fffffff - 255 || (long long)H * W * COcap > 0x7fffffff)
+    return fail(VFS_ERR_SHAPE, who, "Ho * Wo and H * W * classes must fit an int");
+  if (!sbank || !partial || !preds || !desc) return fail(VFS_ERR_ARG, who, "null buffer");
+  return VFS_OK;
+}
+int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap,
+                              int Ho, int Wo, vfs_stream_t stream) {
+  if (int rc = seg_post_batch_check("seg_postprocess_batch", sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo)) return rc;
+  return vfs_seg_postprocess_batch_launch(sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+}
 int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
                                     int COcap, int Ho, int Wo, vfs_stream_t stream) {
-  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
-    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: H, W, Ho, Wo, Tcap >= 1, 1 <= classes <= 256, 1 <= nslots <= 64");
-  if ((long long)Ho * Wo > 0x7fffffff - 255 || (long long)H * W * COcap > 0x7fffffff)
-    return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: Ho * Wo and H * W * classes must fit an int");
-  if (!sbank || !partial || !preds || !desc) return vfs_set_error(VFS_ERR_ARG, "seg_postprocess_exact_batch: null buffer");
+  if (int rc = seg_post_batch_check("seg_postprocess_exact_batch", sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo)) return rc;
   return vfs_seg_postprocess_exact_batch_launch(sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
 }
 int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,

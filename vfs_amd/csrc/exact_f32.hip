@@ -897,24 +897,7 @@ __global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __re
   seg_argmax_exact_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
 }
 // lock-step batch: slot blockIdx.z post-processes ITS propagated frame (frame qframe of its label rows [frame][H*W][CO_n]) with its own
-// class count into frame qframe of its label maps; the class dimension of the min / max grid is sized for COcap
-struct SegPostBatchArgs {
-  const float* sbank;      // [nslots][Tcap][H*W][COcap]
-  float* partial;          // [nslots][LP_POST_BLOCKS][COcap][2]
-  uint8_t* preds;          // [nslots][Tcap][Ho*Wo]
-  const int* desc;
-  int Tcap, COcap, H, W, Ho, Wo;
-};
-__device__ __forceinline__ bool seg_post_slot(const SegPostBatchArgs& b, const float*& seg, float*& partial, uint8_t*& label, int& CO) {
-  const int n = blockIdx.z;
-  int qframe;
-  if (!lpb_row_post(b.desc, n, b.Tcap, b.COcap, qframe, CO)) return false;
-  const size_t HW = (size_t)b.H * b.W;
-  seg = b.sbank + (size_t)n * b.Tcap * HW * b.COcap + (size_t)qframe * HW * CO;
-  partial = b.partial + (size_t)n * LP_POST_BLOCKS * b.COcap * 2;
-  label = b.preds + ((size_t)n * b.Tcap + qframe) * b.Ho * b.Wo;
-  return true;
-}
+// class count into frame qframe of its label maps (seg_post_slot: vfs_lpb.h); the class dimension of the min / max grid is sized for COcap
 __global__ __launch_bounds__(256) void seg_minmax_exact_batch_kernel(SegPostBatchArgs b) {
   const float* seg; float* partial; uint8_t* label; int CO;
   if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;

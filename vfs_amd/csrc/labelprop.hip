@@ -15,6 +15,7 @@
 //   * features are L2-normalised ONCE per frame when they enter the bank (l2norm kernel), not per
 //     propagation step.
 #include "vfs_conv.h"
+#include "vfs_lpb.h"
 #include "vfs_ops.h"
 
 #define LP_TOPK 10
@@ -64,7 +65,10 @@ __device__ __forceinline__ void topk_insert(float (&tv)[LP_TOPK], int (&ti)[LP_T
   }
 }
 
-__global__ __launch_bounds__(256) void labelprop_kernel(LabelPropArgs a) {
+// one video (A = LabelPropArgs) or one slot of a lock-step batch (A = LabelPropSlotArgs); nsplit = the key-frame splits of THIS video
+// (one video: gridDim.y), blockIdx.y < nsplit
+template <class A>
+__device__ __forceinline__ void labelprop_body(const A& a, int nsplit) {
   constexpr int BQ = 64, BK = 128, TM = 8;
   __shared__ __attribute__((aligned(16))) bf16_t sK[2][BK * 64];
   __shared__ __attribute__((aligned(16))) bf16_t sQ[2][BQ * 64];
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void labelprop_kernel(LabelPropArgs a) {
 
   // key frames are split over blockIdx.y (a DAVIS frame has only 8x14 query tiles: one workgroup
   // per tile would leave most of the 256 CUs idle); every split emits a partial top-k per query
-  const int fpb = (a.nkeys + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int fpb = (a.nkeys + nsplit - 1) / nsplit;
   const int f_begin = (int)blockIdx.y * fpb, f_end = min(a.nkeys, f_begin + fpb);
   for (int f = f_begin; f < f_end; ++f) {
     const int slot = a.kslot[f];
@@ -209,7 +213,8 @@ __global__ __launch_bounds__(256) void labelprop_kernel(LabelPropArgs a) {
 }
 
 // merge the per-split partial lists, softmax over the top-k, weighted sum of the value logits
-__global__ __launch_bounds__(256) void labelprop_merge_kernel(LabelPropArgs a, int nsplit) {
+template <class A>
+__device__ __forceinline__ void labelprop_merge_body(const A& a, int nsplit) {
   const int HW = a.H * a.W;
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= HW) return;
@@ -248,6 +253,47 @@ __global__ __launch_bounds__(256) void labelprop_merge_kernel(LabelPropArgs a, i
   }
 }
 
+// ---- the kernels: one video, or slot blockIdx.z of a lock-step batch (arguments built from the slot's descriptor row, as exact_f32.hip)
+struct LabelPropSlotArgs {      // LabelPropArgs of one slot; the key list stays in the table
+  const bf16_t* fbank; const float* sbank; float* out; float* pval; int* pidx;
+  int qframe, nkeys;
+  const int* kslot;
+  int H, W, C, CO, radius, non_mask_len, topk;
+  float inv_temp;
+};
+// false: the slot sits this step out.  nsplit: the key-frame splits the single-video launch chooses for the slot's nkeys - the top-k
+// keeps the first of equal scores, so the order the candidates arrive in (the split) is part of the result
+__device__ __forceinline__ bool lp_slot_args(const LpBatchArgs& b, LabelPropSlotArgs& a, int& nsplit) {
+  const int n = blockIdx.z;
+  LpbRow r;
+  if (!lpb_row(b.desc, n, b.Tcap, b.max_nkeys, b.COcap, b.radius, r)) return false;
+  const size_t HW = (size_t)b.H * b.W, frames = (size_t)n * b.Tcap * HW;
+  a.fbank = b.fbank16 + frames * b.C;
+  float* sb = b.sbank + frames * b.COcap;
+  a.sbank = sb;
+  a.out = sb + (size_t)r.qframe * HW * r.CO;
+  a.pval = reinterpret_cast<float*>(b.ws + (size_t)n * b.ws_stride);
+  a.pidx = reinterpret_cast<int*>(a.pval + (size_t)LP_MAX_SPLIT * HW * LP_TOPK);
+  a.qframe = r.qframe; a.nkeys = r.nkeys; a.kslot = r.kslot;
+  a.H = b.H; a.W = b.W; a.C = b.C; a.CO = r.CO; a.radius = b.radius; a.non_mask_len = r.non_mask_len; a.topk = b.topk;
+  a.inv_temp = b.inv_temp;
+  nsplit = lp_splits_for(r.nkeys, ((b.H + 7) >> 3) * ((b.W + 7) >> 3));
+  return true;
+}
+__global__ __launch_bounds__(256) void labelprop_kernel(LabelPropArgs a) { labelprop_body(a, (int)gridDim.y); }
+__global__ __launch_bounds__(256) void labelprop_merge_kernel(LabelPropArgs a, int nsplit) { labelprop_merge_body(a, nsplit); }
+__global__ __launch_bounds__(256) void labelprop_batch_kernel(LpBatchArgs b) {
+  LabelPropSlotArgs a;
+  int nsplit;
+  if (!lp_slot_args(b, a, nsplit) || (int)blockIdx.y >= nsplit) return;      // the grid is sized for the slot with the most splits
+  labelprop_body(a, nsplit);
+}
+__global__ __launch_bounds__(256) void labelprop_merge_batch_kernel(LpBatchArgs b) {
+  LabelPropSlotArgs a;
+  int nsplit;
+  if (lp_slot_args(b, a, nsplit)) labelprop_merge_body(a, nsplit);
+}
+
 int vfs_labelprop_launch(const LabelPropArgs& a, hipStream_t s) {
   if (a.C % 64) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: C%64");
   if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: 1 <= nkeys <= 64");
@@ -255,16 +301,28 @@ int vfs_labelprop_launch(const LabelPropArgs& a, hipStream_t s) {
   if (a.H >= 65536 || a.W >= 65536) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: H,W < 65536");
   const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
   if (a.pval == nullptr || a.pidx == nullptr) return vfs_set_error(VFS_ERR_ARG, "labelprop: partial workspace missing");
-  int nsplit = (768 + tiles - 1) / tiles;                 // ~3 workgroups per CU
-  if (nsplit > a.nkeys) nsplit = a.nkeys;
-  if (nsplit > LP_MAX_FSPLIT) nsplit = LP_MAX_FSPLIT;
-  const int fpb = (a.nkeys + nsplit - 1) / nsplit;
-  nsplit = (a.nkeys + fpb - 1) / fpb;
+  const int nsplit = lp_splits_for(a.nkeys, tiles);
   hipLaunchKernelGGL(labelprop_kernel, dim3(tiles, nsplit), dim3(256), 0, s, a);
   int rc = vfs_check_launch("labelprop");
   if (rc) return rc;
   hipLaunchKernelGGL(labelprop_merge_kernel, dim3((a.H * a.W + 255) / 256), dim3(256), 0, s, a, nsplit);
   return vfs_check_launch("labelprop_merge");
+}
+
+// every slot of one lock-step: the two launches of one video, each slot with the key-frame split of its own nkeys
+int vfs_labelprop_batch_launch(const LpBatchArgs& b, hipStream_t s) {
+  if (b.C % 64) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: C%64");
+  if (b.max_nkeys < 1 || b.max_nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: 1 <= max_nkeys <= 64");
+  if (b.topk < 1 || b.topk > LP_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: 1 <= topk <= 10");
+  if (b.H >= 65536 || b.W >= 65536) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: H,W < 65536");
+  const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8);
+  int most = 1;
+  for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lp_splits_for(nk, tiles));
+  hipLaunchKernelGGL(labelprop_batch_kernel, dim3(tiles, most, b.nslots), dim3(256), 0, s, b);
+  int rc = vfs_check_launch("labelprop_batch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(labelprop_merge_batch_kernel, dim3((b.H * b.W + 255) / 256, 1, b.nslots), dim3(256), 0, s, b);
+  return vfs_check_launch("labelprop_merge_batch");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -287,8 +345,8 @@ __device__ __forceinline__ float bilerp(const float* __restrict__ seg, int H, in
 }
 
 // grid (LP_POST_BLOCKS, CO): one class per workgroup (as seg_minmax_exact_kernel, csrc/exact_f32.hip)
-__global__ __launch_bounds__(256) void seg_minmax_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
-                                                         int CO, int Ho, int Wo) {
+__device__ __forceinline__ void seg_minmax_body(const float* __restrict__ seg, float* __restrict__ partial, int H, int W, int CO, int Ho,
+                                                int Wo) {
   __shared__ float smn[256], smx[256];
   const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
   const int total = Ho * Wo, c = blockIdx.y;
@@ -316,9 +374,8 @@ __global__ __launch_bounds__(256) void seg_minmax_kernel(const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict__ seg, const float* __restrict__ partial,
-                                                         int nblk, uint8_t* __restrict__ label, int H, int W, int CO, int Ho,
-                                                         int Wo) {
+__device__ __forceinline__ void seg_argmax_body(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
+                                                uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
   __shared__ float smn[LP_MAX_CLASSES], smx[LP_MAX_CLASSES];
   if ((int)threadIdx.x < CO) {
     float mn = INFINITY, mx = -INFINITY;
@@ -342,6 +399,40 @@ __global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict
     }
     label[p] = (uint8_t)bc;
   }
+}
+
+__global__ __launch_bounds__(256) void seg_minmax_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
+                                                         int CO, int Ho, int Wo) {
+  seg_minmax_body(seg, partial, H, W, CO, Ho, Wo);
+}
+__global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict__ seg, const float* __restrict__ partial,
+                                                         int nblk, uint8_t* __restrict__ label, int H, int W, int CO, int Ho,
+                                                         int Wo) {
+  seg_argmax_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
+}
+// lock-step batch: slot blockIdx.z post-processes its propagated frame with its own class count (seg_post_slot: vfs_lpb.h); the class
+// dimension of the min / max grid is sized for COcap
+__global__ __launch_bounds__(256) void seg_minmax_batch_kernel(SegPostBatchArgs b) {
+  const float* seg; float* partial; uint8_t* label; int CO;
+  if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;
+  seg_minmax_body(seg, partial, b.H, b.W, CO, b.Ho, b.Wo);
+}
+__global__ __launch_bounds__(256) void seg_argmax_batch_kernel(SegPostBatchArgs b) {
+  const float* seg; float* partial; uint8_t* label; int CO;
+  if (!seg_post_slot(b, seg, partial, label, CO)) return;
+  seg_argmax_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
+}
+int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                                     int COcap, int Ho, int Wo, hipStream_t s) {
+  if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_batch: 1 <= classes <= 256");
+  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, COcap, H, W, Ho, Wo};
+  hipLaunchKernelGGL(seg_minmax_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
+  int rc = vfs_check_launch("seg_minmax_batch");
+  if (rc) return rc;
+  int blocks = (Ho * Wo + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(seg_argmax_batch_kernel, dim3(blocks, 1, nslots), dim3(256), 0, s, b);
+  return vfs_check_launch("seg_argmax_batch");
 }
 
 int vfs_seg_postprocess_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,

@@ -27,3 +27,21 @@ __device__ __forceinline__ bool lpb_row_post(const int* __restrict__ desc, int s
   qframe = row[1]; CO = row[4];
   return qframe >= 0 && qframe < Tcap && CO >= 1 && CO <= COcap;
 }
+// label maps of a step (exact_f32.hip, labelprop.hip): what slot blockIdx.z reads and writes
+struct SegPostBatchArgs {
+  const float* sbank;      // [nslots][Tcap][H*W][COcap]
+  float* partial;          // [nslots][LP_POST_BLOCKS][COcap][2]
+  uint8_t* preds;          // [nslots][Tcap][Ho*Wo]
+  const int* desc;
+  int Tcap, COcap, H, W, Ho, Wo;
+};
+__device__ __forceinline__ bool seg_post_slot(const SegPostBatchArgs& b, const float*& seg, float*& partial, uint8_t*& label, int& CO) {
+  const int n = blockIdx.z;
+  int qframe;
+  if (!lpb_row_post(b.desc, n, b.Tcap, b.COcap, qframe, CO)) return false;
+  const size_t HW = (size_t)b.H * b.W;
+  seg = b.sbank + (size_t)n * b.Tcap * HW * b.COcap + (size_t)qframe * HW * CO;
+  partial = b.partial + (size_t)n * LP_POST_BLOCKS * b.COcap * 2;
+  label = b.preds + ((size_t)n * b.Tcap + qframe) * b.Ho * b.Wo;
+  return true;
+}

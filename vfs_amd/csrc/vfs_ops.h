@@ -348,6 +348,15 @@ struct LabelPropArgs {
   int topk;             // <= 10
   float inv_temp;
 };
+// key-frame splits (blockIdx.y) of the bf16 kernel for nkeys key frames over `tiles` query tiles: ~3 workgroups per CU.  The top-k
+// keeps the first of equal scores, so the split is part of the result: one video and its slot in a lock-step batch use this one
+__host__ __device__ inline int lp_splits_for(int nkeys, int tiles) {
+  int nsplit = (768 + tiles - 1) / tiles;
+  if (nsplit > nkeys) nsplit = nkeys;
+  if (nsplit > LP_MAX_FSPLIT) nsplit = LP_MAX_FSPLIT;
+  const int fpb = (nkeys + nsplit - 1) / nsplit;
+  return (nkeys + fpb - 1) / fpb;
+}
 int vfs_l2norm_rows_launch(const bf16_t* x, bf16_t* y, long long P, int C, hipStream_t s);
 int vfs_labelprop_launch(const LabelPropArgs& a, hipStream_t s);
 int vfs_seg_postprocess_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
@@ -448,6 +457,8 @@ struct LpBatchArgs {
   float temperature, margin;
   int want_splits, fpb_opt, cap_opt, entries, dbg, trim;      // two-pass: key-frame splits wanted per slot (the active slots share the chip)
   int target, wgs, minb;                                      // dense: workgroups wanted per slot, as vfs_labelprop_f32_launch counts them
+  const bf16_t* fbank16;      // bf16 kernels (labelprop.hip): the bank [nslots][Tcap][H*W][C] in bf16 (fbank, hl unused) ...
+  float inv_temp;             // ... and 1 / temperature as the single-video call rounds it on the host
 };
 // key-frame splits of pass 1 for nkeys key frames when `want` are wanted (vfs_lp2_splits: want = 4 workgroups per CU over the tiles
 // of every active slot)
@@ -488,6 +499,9 @@ __host__ __device__ inline int lpx_splits_for(int nkeys, int tiles, int target, 
 int vfs_lp2_splits(int H, int W, int nkeys, int nactive = 1);
 int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
 int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
+int vfs_labelprop_batch_launch(const LpBatchArgs& b, hipStream_t s);
+int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
+                                     int COcap, int Ho, int Wo, hipStream_t s);
 int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
                                            int COcap, int Ho, int Wo, hipStream_t s);
 int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,

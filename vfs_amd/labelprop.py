@@ -212,8 +212,9 @@ def _first_frame(eng, ref, feat, rows0, out_size, pred0):
     return big
 
 
-def _workspace_bytes(lib, h, w, two_pass, entries, nslots=None):
-    """workspace bytes of the dense or the two-pass kernels (`entries` list entries per query, <= 0: the library's own), one video or `nslots` slots"""
+def _workspace_bytes(lib, h, w, two_pass, entries, nslots=None, precision='fp32'):
+    """workspace bytes of the dense or the two-pass kernels (`entries` list entries per query, <= 0: the library's own), one video or
+    `nslots` slots (`precision`: which batched kernels; one video: the dense kernels of both precisions share a layout)"""
     nbytes = torch.zeros(1, dtype=torch.int64)
     if nslots is None:
         if not two_pass:
@@ -222,6 +223,8 @@ def _workspace_bytes(lib, h, w, two_pass, entries, nslots=None):
             lib.labelprop_f32_2pass_workspace_bytes_for(h, w, entries, nbytes)
         else:
             lib.labelprop_f32_2pass_workspace_bytes(h, w, nbytes)
+    elif precision == 'bf16':
+        lib.labelprop_batch_workspace_bytes(h, w, nslots, nbytes)
     elif two_pass:
         lib.labelprop_f32_2pass_batch_workspace_bytes(h, w, max(0, entries), nslots, nbytes)
     else:
@@ -238,6 +241,15 @@ def _result(tracker, arr):
     tmp.close()
     np.save(tmp.name, arr)
     return tmp.name
+
+
+def _levels_result(tracker, levels):
+    """forward_test(...)[0] from the label maps of every feature level (vanilla_tracker.py:199-205: several levels are stacked
+    [num_feats, T, ...]; save_np: the list of their paths)"""
+    res = [_result(tracker, arr) for arr in levels]
+    if len(res) == 1:
+        return res[0]
+    return res if tracker.save_np else np.stack(res, axis=0)
 
 
 def forward_test_hip(tracker, imgs, ref_seg_map, img_meta):
@@ -289,14 +301,13 @@ def _forward_test(tracker, cfg, imgs, ref_seg_map, img_meta):
             else:
                 eng.timed('seg_postprocess', (0.0, 4.0 * h * w * CO + float(out_h * out_w)), dev, post, sbank[f], partial, preds[f],
                           h, w, CO, out_h, out_w, s)
-        all_preds.append(_result(tracker, preds.cpu().numpy()))
-    if len(all_preds) > 1:      # vanilla_tracker.py:199-205: [1, num_feats, T, ...] unravelled over the batch dim (save_np: the paths)
-        return [all_preds if tracker.save_np else np.stack(all_preds, axis=0)]
-    return all_preds
+        all_preds.append(preds.cpu().numpy())
+    return [_levels_result(tracker, all_preds)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# forward_test of a batch of videos in lock-step (csrc: vfs_labelprop_f32_batch / _2pass_batch and the batched post-processing).
+# forward_test of a batch of videos in lock-step (csrc: vfs_labelprop_f32_batch / _2pass_batch, vfs_labelprop_batch for the bf16
+# precision, and the batched post-processing).
 #
 # A JHMDB or VIP frame (30 x 40 features: 20 query tiles) does not fill the chip, and an evaluation is hundreds of such videos.  Here
 # up to `batch` videos of one frame size occupy SLOTS of stacked banks and advance together: one launch set per step serves every slot,
@@ -342,87 +353,124 @@ def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_
     return table, steps
 
 
+def _level_maps(ref, shapes, out_size):
+    """a video's reference map at the size of every feature level (_at_feature_size).  Level l + 1 starts from the map level l resized
+    to the output size, not from the caller's (as _forward_test chains them): class counts of a label map may differ between levels"""
+    feats = []
+    for h, w, _ in shapes:
+        feats.append(_at_feature_size(ref, h, w))
+        if not torch.is_tensor(ref):      # (a soft map keeps its channel count: nothing else of it is read here)
+            ref = torch_nearest_resize(ref, *out_size)
+    return feats
+
+
+class _Level:
+    """one feature level of a group: its stacked banks (layout: include/vfs_hip.h), maps and descriptor table on the device"""
+
+    def __init__(self, eng, cfg, shape, split, feats, lengths, soft, out_size, B, Tcap, dev):
+        h, w, C = self.h, self.w, self.C = shape
+        out_h, out_w = out_size
+        exact = cfg.precision == 'fp32'
+        self.fb = torch.empty(B, Tcap, h * w, C, dtype=F32 if exact else BF16, device=dev)
+        self.hl = torch.empty(B, Tcap, h * w, 2 * C, dtype=BF16, device=dev) if split else None      # fp32, two-pass kernels only
+        self.feats = feats
+        self.cos = [feat[2] for feat in feats]
+        COcap = self.COcap = max(self.cos)
+        self.sb = torch.empty(B, Tcap * h * w * COcap, dtype=F32, device=dev)      # label rows, packed per slot with the slot's class count
+        if soft:
+            self.preds = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
+        else:
+            self.preds = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
+        self.ws_bytes = _workspace_bytes(eng.lib, h, w, split, cfg.entries, B, cfg.precision)
+        # the levels share one schedule; only the class-count column of their tables may differ
+        table, self.steps = batch_schedule(lengths, self.cos, B, cfg.precede, cfg.with_first, cfg.non_mask_len)
+        self.table = torch.from_numpy(table).to(dev)      # the ONE upload of the schedule
+
+
 class _Group:
-    """videos of ONE frame size, label-map kind and output size (each of >= 2 frames) in lock-step: the stacked banks of B slots
-    (layout: include/vfs_hip.h), the workspace and the schedule with its descriptor table on the device"""
+    """videos of ONE frame size, label-map kind and output size (each of >= 2 frames) in lock-step: per feature level (one, or with
+    all_blocks every block of the evaluated stages) the stacked banks of B slots, and the workspace and the schedule they share"""
 
     def __init__(self, tracker, eng, cfg, videos, ref_seg_maps, out_size, batch):
         """videos: [imgs [1,3,T,H,W]] in the order of admission"""
         self.tracker, self.eng, self.cfg, self.videos, self.out_size = tracker, eng, cfg, videos, out_size
         dev = videos[0].device
-        out_h, out_w = out_size
         self.refs = [_first_maps(r, dev) for r in ref_seg_maps]
         self.soft = torch.is_tensor(self.refs[0])
         self.lengths = [int(v.size(2)) for v in videos]
         B, Tcap = self.B, self.Tcap = min(batch, len(videos)), max(self.lengths)
         # the stacked banks can be sized only when a feature map is known: video 0 is extracted into tensors of its own, which admit()
         # copies into its slot - one device-to-device copy per group, the same launches as extracting into the slot
-        self.first = extract_feature_levels(tracker, eng, videos[0], cfg.batch_step, False, 'fp32', cfg.with_norm)
-        h, w, C = self.h, self.w, self.C = self.first[2][0]
-        self.fb = torch.empty(B, Tcap, h * w, C, dtype=F32, device=dev)
-        self.hl = torch.empty(B, Tcap, h * w, 2 * C, dtype=BF16, device=dev) if self.first[1][0] is not None else None
-        self.feats = [_at_feature_size(ref, h, w) for ref in self.refs]
-        self.cos = [feat[2] for feat in self.feats]
-        COcap = self.COcap = max(self.cos)
-        self.sb = torch.empty(B, Tcap * h * w * COcap, dtype=F32, device=dev)      # label rows, packed per slot with the slot's class count
-        if self.soft:
-            self.preds = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
-        else:
-            self.preds = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
-            self.partial = eng.ws('ws.segpost_batch', B * 64 * COcap * 2, F32, dev)
-        nbytes = _workspace_bytes(eng.lib, h, w, self.hl is not None, cfg.entries, B)
-        self.ws = torch.empty((nbytes + 3) // 4, dtype=F32, device=dev)      # (per group: released with it)
-        table, self.steps = batch_schedule(self.lengths, self.cos, B, cfg.precede, cfg.with_first, cfg.non_mask_len)
-        self.table = torch.from_numpy(table).to(dev)      # the ONE upload of the schedule
+        self.first = extract_feature_levels(tracker, eng, videos[0], cfg.batch_step, cfg.all_blocks, cfg.precision, cfg.with_norm)
+        _, splits, shapes = self.first
+        feats = [_level_maps(ref, shapes, out_size) for ref in self.refs]      # [video][level]
+        self.levels = [_Level(eng, cfg, shape, split is not None, [f[l] for f in feats], self.lengths, self.soft, out_size, B, Tcap, dev)
+                       for l, (shape, split) in enumerate(zip(shapes, splits))]
+        self.steps = self.levels[0].steps
+        if not self.soft:
+            self.partial = eng.ws('ws.segpost_batch', B * 64 * max(lv.COcap for lv in self.levels) * 2, F32, dev)
+        self.ws = torch.empty((max(lv.ws_bytes for lv in self.levels) + 3) // 4, dtype=F32, device=dev)      # (per group: released with it)
 
     def admit(self, n, k):
-        """video k enters slot n: its features, and frame 0 of its label rows and predictions"""
-        T, CO, cfg = self.lengths[k], self.cos[k], self.cfg
-        fb, hl = self.fb[n, :T], None if self.hl is None else self.hl[n, :T]
+        """video k enters slot n: its features, and frame 0 of its label rows and predictions, level by level"""
+        T, cfg = self.lengths[k], self.cfg
+        fbs, hls = [lv.fb[n, :T] for lv in self.levels], [None if lv.hl is None else lv.hl[n, :T] for lv in self.levels]
         if self.first is not None:      # video 0 (always the first admitted)
-            fb.copy_(self.first[0][0])
-            if hl is not None:
-                hl.copy_(self.first[1][0])
+            for dst, src in zip(fbs + hls, self.first[0] + self.first[1]):
+                if dst is not None:
+                    dst.copy_(src)
             self.first = None
         else:
-            extract_feature_levels(self.tracker, self.eng, self.videos[k], cfg.batch_step, False, 'fp32', cfg.with_norm, [fb], [hl])
+            extract_feature_levels(self.tracker, self.eng, self.videos[k], cfg.batch_step, cfg.all_blocks, cfg.precision, cfg.with_norm, fbs, hls)
         out_h, out_w = self.out_size
-        pred0 = self.preds[n, :CO * out_h * out_w] if self.soft else self.preds[n, 0]
-        _first_frame(self.eng, self.refs[k], self.feats[k], self.sb[n, :self.h * self.w * CO], self.out_size, pred0)
+        ref = self.refs[k]
+        for lv in self.levels:      # the next level starts from this level's map at the output size (a soft map: frame 0 of its predictions)
+            CO = lv.cos[k]
+            pred0 = lv.preds[n, :CO * out_h * out_w].reshape(CO, out_h, out_w) if self.soft else lv.preds[n, 0]
+            ref = _first_frame(self.eng, ref, lv.feats[k], lv.sb[n, :lv.h * lv.w * CO], self.out_size, pred0)
 
     def step(self, i):
-        """one launch set: every active slot propagates to and post-processes its frame of row i of the schedule"""
-        lib, cfg, ws, row = self.eng.lib, self.cfg, self.ws, self.table[i]
+        """one launch set per level: every active slot propagates to and post-processes its frame of row i of the schedule"""
+        lib, cfg, ws = self.eng.lib, self.cfg, self.ws
         _, _, nactive, most = self.steps[i]
-        B, Tcap, h, w, C, COcap = self.B, self.Tcap, self.h, self.w, self.C, self.COcap
-        out_h, out_w = self.out_size
-        s = self.eng.stream(row.device)
-        if self.hl is not None:
-            lib.labelprop_f32_2pass_batch(self.fb, self.hl, self.sb, ws, ws.numel() * 4, row, B, nactive, most, Tcap, h, w, C, COcap,
-                                          cfg.radius, cfg.topk, cfg.temp, 1, s)
-        else:
-            lib.labelprop_f32_batch(self.fb, self.sb, ws, ws.numel() * 4, row, B, nactive, most, Tcap, h, w, C, COcap, cfg.radius,
-                                    cfg.topk, cfg.temp, s)
-        if self.soft:
-            lib.bilinear_resize_f32_batch(self.sb, self.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
-        else:
-            lib.seg_postprocess_exact_batch(self.sb, self.partial, self.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
+        B, Tcap, (out_h, out_w) = self.B, self.Tcap, self.out_size
+        s = self.eng.stream(ws.device)
+        for lv in self.levels:
+            row, h, w, C, COcap = lv.table[i], lv.h, lv.w, lv.C, lv.COcap
+            if cfg.precision == 'bf16':
+                lib.labelprop_batch(lv.fb, lv.sb, ws, lv.ws_bytes, row, B, nactive, most, Tcap, h, w, C, COcap, cfg.radius, cfg.topk, cfg.temp, s)
+            elif lv.hl is not None:
+                lib.labelprop_f32_2pass_batch(lv.fb, lv.hl, lv.sb, ws, lv.ws_bytes, row, B, nactive, most, Tcap, h, w, C, COcap, cfg.radius,
+                                              cfg.topk, cfg.temp, 1, s)
+            else:
+                lib.labelprop_f32_batch(lv.fb, lv.sb, ws, lv.ws_bytes, row, B, nactive, most, Tcap, h, w, C, COcap, cfg.radius, cfg.topk,
+                                        cfg.temp, s)
+            if self.soft:
+                lib.bilinear_resize_f32_batch(lv.sb, lv.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
+            elif cfg.precision == 'bf16':
+                lib.seg_postprocess_batch(lv.sb, self.partial, lv.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
+            else:
+                lib.seg_postprocess_exact_batch(lv.sb, self.partial, lv.preds, row, B, Tcap, h, w, COcap, out_h, out_w, s)
 
     def retire(self, n, k):
-        """-> the maps of video k, which ended in slot n: they leave the device now, the slot is refilled at the next step"""
-        T, CO, (out_h, out_w) = self.lengths[k], self.cos[k], self.out_size
-        if self.soft:
-            arr = self.preds[n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
-        else:
-            arr = self.preds[n, :T].reshape(T, out_h, out_w)
-        return arr.cpu().numpy() if arr.device.type != 'cpu' else arr.numpy().copy()      # (the slot's maps are overwritten by the next video)
+        """-> forward_test(...)[0] of video k, which ended in slot n: its maps leave the device now, the slot is refilled at the next step"""
+        T, (out_h, out_w) = self.lengths[k], self.out_size
+        levels = []
+        for lv in self.levels:
+            CO = lv.cos[k]
+            if self.soft:
+                arr = lv.preds[n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
+            else:
+                arr = lv.preds[n, :T].reshape(T, out_h, out_w)
+            levels.append(arr.cpu().numpy() if arr.device.type != 'cpu' else arr.numpy().copy())      # (the slot's maps are overwritten by the next video)
+        return _levels_result(self.tracker, levels)
 
 
 def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8):
     """out[i] == forward_test(imgs_list[i], ref_seg_maps[i], img_metas[i])[0] for every video, in input order.
     Videos are grouped by frame size, kind of label map (3-D labels / 4-D soft maps) and output size; a group runs in lock-step
-    (above) with precision 'fp32' and one feature level.  precision='bf16' and all_blocks=True have no batched kernels: they are
-    served by forward_test, video by video - same results."""
+    (above) on the batched kernels of test_cfg.precision ('fp32': vfs_labelprop_f32_2pass_batch / vfs_labelprop_f32_batch, 'bf16':
+    vfs_labelprop_batch), with all_blocks=True one launch set per feature level and step.  There is no per-video path inside."""
     n = len(imgs_list)
     if len(ref_seg_maps) != n or len(img_metas) != n:
         raise ValueError(f'forward_test_batch: {n} videos, {len(ref_seg_maps)} label maps, {len(img_metas)} img_metas')
@@ -434,9 +482,9 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8)
         if imgs is None or not hasattr(imgs, 'numel') or imgs.numel() == 0:
             raise ValueError(f'forward_test_batch: video {i} has no frames')
     cfg = labelprop_config(tracker)
-    if cfg.precision != 'fp32' or cfg.all_blocks:
-        return [_forward_test(tracker, cfg, a, b, c)[0] for a, b, c in zip(imgs_list, ref_seg_maps, img_metas)]
     eng = shared_engine()
+    bb = tracker.backbone
+    nlevels = len(_block_feats(bb, 1 << 30, tuple(tracker.test_cfg.get('out_indices', bb.out_indices)))) if cfg.all_blocks else 1
     outs = [None] * n
     groups = {}
     for i, (imgs, ref_seg_map, meta) in enumerate(zip(imgs_list, ref_seg_maps, img_metas)):
@@ -447,10 +495,13 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8)
         if imgs.size(2) > 1:
             groups.setdefault((imgs.shape[3], imgs.shape[4], soft, out_h, out_w, dev), []).append((i, imgs, ref_seg_map))
             continue
-        ref = _first_maps(ref_seg_map, dev)      # a one-frame clip is its (resized) reference map
-        pred0 = torch.empty(ref.shape[0], out_h, out_w, dtype=F32, device=dev) if soft else None
-        first = _first_frame(eng, ref, None, None, (out_h, out_w), pred0)
-        outs[i] = _result(tracker, (first.cpu().numpy() if soft else first)[None])
+        ref = _first_maps(ref_seg_map, dev)      # a one-frame clip is its (resized) reference map, level after level
+        levels = []
+        for _ in range(nlevels):
+            pred0 = torch.empty(ref.shape[0], out_h, out_w, dtype=F32, device=dev) if soft else None
+            ref = _first_frame(eng, ref, None, None, (out_h, out_w), pred0)
+            levels.append((ref.cpu().numpy() if soft else ref)[None])
+        outs[i] = _levels_result(tracker, levels)
     for (_, _, _, out_h, out_w, _), vids in groups.items():
         group = _Group(tracker, eng, cfg, [v[1] for v in vids], [v[2] for v in vids], (out_h, out_w), batch)
         for step, (admitted, retired, _, _) in enumerate(group.steps):
@@ -458,5 +509,5 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8)
                 group.admit(slot, k)
             group.step(step)
             for slot, k in retired:
-                outs[vids[k][0]] = _result(tracker, group.retire(slot, k))
+                outs[vids[k][0]] = group.retire(slot, k)
     return outs
