@@ -698,6 +698,27 @@ int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const 
                                     int T, int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g,
                                     double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream);
 
+/* the same two chains for a batch whose samples were decoded at different sizes: the reference crops and resizes sample by
+ * sample, each at its own img_shape (pipelines/augmentations.py:171-334,487-596), and DecordDecode hands it every Kinetics
+ * video at its own size (340x256, 454x256, 256x340, ...).  src is a byte buffer of src_bytes bytes; srcdesc int32 [B][4],
+ * one row per SAMPLE = {offset low 32 bits, offset high 32 bits, Hs, Ws}: the V*T frames of sample b lie contiguously as
+ * uint8 [V*T][Hs_b][Ws_b][3] at src + offset_b in pipeline order (v, t); byte offsets, no alignment required.  boxes are
+ * clamped to the sample's own Hs_b, Ws_b.  Guard: a row with Hs <= 0, Ws <= 0, a negative offset or
+ * offset + V*T*Hs*Ws*3 > src_bytes makes its sample invalid: nothing is read for it and every output element it owns (imgs,
+ * x4, the x4 pad column) is zero; the other samples of the launch are unaffected.  So no table can make the kernels read
+ * outside [src, src + src_bytes).  src_bytes <= 0 is refused like a null src.  Everything else - the arithmetic, boxes,
+ * flips, photo, the workspace rule, the outputs, the frame cap - as the uniform entry points; a batch of equal sizes laid
+ * out back to back gives their bits. */
+int vfs_crop_resize_flip_norm_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes,
+                                     const uint8_t* flips, float* imgs, vfs_bf16* x4, int B, int V, int T, int Ho, int Wo,
+                                     int Wp, double mean_r, double mean_g, double mean_b, double std_r, double std_g,
+                                     double std_b, vfs_stream_t stream);
+int vfs_crop_resize_flip_photo_norm_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes,
+                                           const uint8_t* flips, const int* photo, void* workspace,
+                                           long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T,
+                                           int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b,
+                                           double std_r, double std_g, double std_b, vfs_stream_t stream);
+
 /* ---- SiamFC probe head (projects/siamfc-pytorch/siamfc/heads.py:16-23,51-58 `_fast_xcorr`): response maps
  * out[m][i][j] = scale * sum_{u,v,c} z[m % nz][u][v][c] * x[m][i+u][j+v][c]; z bf16 [nz][Hz][Wz][C], x bf16 [nx][H][W][C] (NHWC),
  * out fp32 [nx][H-Hz+1][W-Wz+1]; nx % nz == 0, C % 8 == 0.  Forward only (inference of a trained probe). */

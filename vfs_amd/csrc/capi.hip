@@ -211,6 +211,39 @@ static PipelineArgs pipeline_args(const uint8_t* src, const int* boxes, const ui
   return a;
 }
 
+// the ragged entries describe the source per sample instead of by one Hs, Ws pair (which they leave 0)
+static PipelineArgs ragged_args(PipelineArgs a, const int* srcdesc, long long src_bytes) {
+  a.srcdesc = srcdesc; a.src_bytes = src_bytes; a.ragged = true;
+  return a;
+}
+
+// the argument checks of the uniform and the ragged pipeline entries (an empty source buffer is refused like a null one)
+static int pipeline_check(const char* who, const PipelineArgs& a, const void* photo) {
+  if (!a.src || !a.boxes || !a.flips || !photo || (!a.imgs && !a.x4) || (a.ragged && (!a.srcdesc || a.src_bytes <= 0)))
+    return fail(VFS_ERR_ARG, who, "null buffer");
+  if (a.x4 && a.Wp < a.Wo) return fail(VFS_ERR_SHAPE, who, "Wp < Wo");
+  return VFS_OK;
+}
+
+static int pipeline_run(const char* who, const PipelineArgs& a, hipStream_t s) {
+  const int rc = pipeline_check(who, a, a.src);
+  return rc != VFS_OK ? rc : vfs_crop_resize_flip_norm_launch(a, s);
+}
+
+static int photo_run(const char* who, const PipelineArgs& a, const int* photo, void* workspace, long long workspace_bytes, hipStream_t s) {
+  const int rc = pipeline_check(who, a, photo);
+  if (rc != VFS_OK) return rc;
+  if (a.B <= 0 || a.V <= 0 || a.T <= 0 || a.Ho <= 0 || a.Wo <= 0) return fail(VFS_ERR_SHAPE, who, "empty batch");
+  if (!workspace || workspace_bytes < vfs_photo_workspace_bytes(a.B * a.V * a.T, a.Ho, a.Wo))
+    return fail(VFS_ERR_ARG, who, "workspace smaller than vfs_crop_resize_flip_photo_norm_workspace_bytes");
+  PhotoArgs pa{};
+  pa.p = a;
+  pa.photo = photo;
+  pa.sums = (unsigned long long*)workspace;
+  pa.pix = (uint32_t*)((char*)workspace + (size_t)a.B * a.V * a.T * 8);
+  return vfs_crop_resize_flip_photo_norm_launch(pa, s);
+}
+
 extern "C" {
 
 const char* vfs_last_error(void) { return g_err; }
@@ -1165,10 +1198,8 @@ int vfs_pose_heatmaps(const float* patch, const int* kp, float* out, int K, int 
 int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_t* flips, float* imgs, vfs_bf16* x4, int B, int V, int T,
                               int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r,
                               double std_g, double std_b, vfs_stream_t stream) {
-  if (!src || !boxes || !flips || (!imgs && !x4)) return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_norm: null buffer");
-  if (x4 && Wp < Wo) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_norm: Wp < Wo");
   const PipelineArgs a = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
-  return vfs_crop_resize_flip_norm_launch(a, stream_of(stream));
+  return pipeline_run("crop_resize_flip_norm", a, stream_of(stream));
 }
 
 int vfs_crop_resize_flip_photo_norm_workspace_bytes(int frames, int Ho, int Wo, long long* bytes) {
@@ -1181,18 +1212,25 @@ int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const 
                                     long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T, int Hs, int Ws, int Ho,
                                     int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r, double std_g,
                                     double std_b, vfs_stream_t stream) {
-  if (!src || !boxes || !flips || !photo || (!imgs && !x4)) return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm: null buffer");
-  if (x4 && Wp < Wo) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_photo_norm: Wp < Wo");
-  if (B <= 0 || V <= 0 || T <= 0 || Ho <= 0 || Wo <= 0) return vfs_set_error(VFS_ERR_SHAPE, "crop_resize_flip_photo_norm: empty batch");
-  long long need = 0;
-  if (vfs_crop_resize_flip_photo_norm_workspace_bytes(B * V * T, Ho, Wo, &need) != VFS_OK || !workspace || workspace_bytes < need)
-    return vfs_set_error(VFS_ERR_ARG, "crop_resize_flip_photo_norm: workspace smaller than vfs_crop_resize_flip_photo_norm_workspace_bytes");
-  PhotoArgs pa{};
-  pa.p = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
-  pa.photo = photo;
-  pa.sums = (unsigned long long*)workspace;
-  pa.pix = (uint32_t*)((char*)workspace + (size_t)B * V * T * 8);
-  return vfs_crop_resize_flip_photo_norm_launch(pa, stream_of(stream));
+  const PipelineArgs a = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
+  return photo_run("crop_resize_flip_photo_norm", a, photo, workspace, workspace_bytes, stream_of(stream));
+}
+
+int vfs_crop_resize_flip_norm_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes, const uint8_t* flips,
+                                     float* imgs, vfs_bf16* x4, int B, int V, int T, int Ho, int Wo, int Wp, double mean_r, double mean_g,
+                                     double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream) {
+  const PipelineArgs a = ragged_args(pipeline_args(src, boxes, flips, imgs, x4, B, V, T, 0, 0, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g,
+                                                   std_b), srcdesc, src_bytes);
+  return pipeline_run("crop_resize_flip_norm_ragged", a, stream_of(stream));
+}
+
+int vfs_crop_resize_flip_photo_norm_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes,
+                                           const uint8_t* flips, const int* photo, void* workspace, long long workspace_bytes, float* imgs,
+                                           vfs_bf16* x4, int B, int V, int T, int Ho, int Wo, int Wp, double mean_r, double mean_g,
+                                           double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream) {
+  const PipelineArgs a = ragged_args(pipeline_args(src, boxes, flips, imgs, x4, B, V, T, 0, 0, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g,
+                                                   std_b), srcdesc, src_bytes);
+  return photo_run("crop_resize_flip_photo_norm_ragged", a, photo, workspace, workspace_bytes, stream_of(stream));
 }
 
 }  // extern "C"

@@ -34,6 +34,78 @@ __device__ __forceinline__ void cv_linear_coef(int d, int n, int m, int& s0, int
   w1 = (int)rintf(f * 2048.f);
 }
 
+// Where the pixels of frame f lie.  The uniform entry points take one dense [F][Hs][Ws][3] tensor; the ragged ones
+// (vfs_crop_resize_flip_norm_ragged) a byte buffer and a descriptor row per SAMPLE, int32 {offset low, offset high, Hs, Ws}:
+// the reference crops and resizes sample by sample, each at its own img_shape (augmentations.py:171-334,487-596), and
+// DecordDecode returns every Kinetics video at its own size.  A row that would let a frame reach outside
+// [src, src + src_bytes) makes the whole sample invalid (img == nullptr): it reads nothing and its outputs are zeros.
+struct FrameSrc {
+  const uint8_t* img;    // [Hs][Ws][3]
+  int Hs, Ws;
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ FrameSrc frame_src(const PipelineArgs& a, int f) {
+  if (!RAGGED) return FrameSrc{a.src + (size_t)f * a.Hs * a.Ws * 3, a.Hs, a.Ws};
+  const int per = a.V * a.T;
+  const int* d = a.srcdesc + 4 * (f / per);
+  const long long off = (long long)(((unsigned long long)(uint32_t)d[1] << 32) | (unsigned long long)(uint32_t)d[0]);
+  const int Hs = d[2], Ws = d[3];
+  if (Hs <= 0 || Ws <= 0 || off < 0 || off > a.src_bytes) return FrameSrc{nullptr, 0, 0};
+  const unsigned long long frame = (unsigned long long)Hs * (unsigned long long)Ws * 3ull;     // < 3 * 2^62
+  unsigned long long need;
+  if (__builtin_umulll_overflow(frame, (unsigned long long)per, &need) || need > (unsigned long long)(a.src_bytes - off))
+    return FrameSrc{nullptr, 0, 0};
+  return FrameSrc{a.src + off + (size_t)(f % per) * frame, Hs, Ws};
+}
+
+// crop + resize + flip of one output pixel (cv2.resize's two fixed-point passes, per channel, before the uint8 saturation)
+__device__ __forceinline__ void resize_pixel(const PipelineArgs& a, const FrameSrc& s, int f, int x, int y, int u[3]) {
+  // boxes come from the host: clamp them to the frame so a bad box can never read outside it
+  const int left = min(max(a.boxes[4 * f], 0), s.Ws - 1), top = min(max(a.boxes[4 * f + 1], 0), s.Hs - 1);
+  const int right = min(max(a.boxes[4 * f + 2], left + 1), s.Ws), bottom = min(max(a.boxes[4 * f + 3], top + 1), s.Hs);
+  const int cw = right - left, ch = bottom - top;
+  const int xr = a.flips[f] ? a.Wo - 1 - x : x;  // cv2.flip(img, 1) AFTER the resize
+  int sx, sx1, ax0, ax1, sy, sy1, by0, by1;
+  cv_linear_coef<true>(xr, cw, a.Wo, sx, sx1, ax0, ax1);
+  cv_linear_coef<false>(y, ch, a.Ho, sy, sy1, by0, by1);
+  const uint8_t* p00 = s.img + ((size_t)(top + sy) * s.Ws + left + sx) * 3;
+  const uint8_t* p01 = s.img + ((size_t)(top + sy) * s.Ws + left + sx1) * 3;
+  const uint8_t* p10 = s.img + ((size_t)(top + sy1) * s.Ws + left + sx) * 3;
+  const uint8_t* p11 = s.img + ((size_t)(top + sy1) * s.Ws + left + sx1) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int h0 = p00[c] * ax0 + p01[c] * ax1;          // horizontal pass, 8 + 11 bits
+    const int h1 = p10[c] * ax0 + p11[c] * ax1;
+    u[c] = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;   // vertical pass
+  }
+}
+
+// mmcv.imnormalize_ of one channel value
+__device__ __forceinline__ float normalized(const PipelineArgs& a, int c, int u) {
+  const float d = (float)((double)u - a.mean[c]);       // cv2.subtract(float32 image, float64 scalar)
+  return (float)((double)d * a.stdinv[c]);              // cv2.multiply(..., 1/std)
+}
+
+// FormatShape: one pixel of frame f (pipeline order (b, v, t)) into both output layouts
+__device__ __forceinline__ void store_pixel(const PipelineArgs& a, int f, int x, int y, const float o[3]) {
+  const int t = f % a.T, v = (f / a.T) % a.V, b = f / (a.T * a.V);
+  if (a.imgs) {
+    const size_t plane = (size_t)a.T * a.Ho * a.Wo;
+    float* q = a.imgs + (((size_t)b * a.V + v) * 3) * plane + ((size_t)t * a.Ho + y) * a.Wo + x;
+    q[0] = o[0]; q[plane] = o[1]; q[2 * plane] = o[2];
+  }
+  if (a.x4) {   // frame order of the backbone batch: (view, b, t), as vfs_imgs_to_nhwc4
+    const size_t fr = ((size_t)v * a.B + b) * a.T + t;
+    u32x2 pk;
+    pk.x = pack2bf(o[0], o[1]);
+    pk.y = pack2bf(o[2], 0.f);
+    st8(a.x4 + ((fr * a.Ho + y) * a.Wp + x) * 4, pk);
+    if (a.Wp > a.Wo && x == a.Wo - 1) st8(a.x4 + ((fr * a.Ho + y) * a.Wp + a.Wo) * 4, (u32x2){0u, 0u});
+  }
+}
+
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void crop_resize_flip_norm_kernel(PipelineArgs a) {
   const long long total = (long long)a.B * a.V * a.T * a.Ho * a.Wo;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -41,42 +113,15 @@ __global__ __launch_bounds__(256) void crop_resize_flip_norm_kernel(PipelineArgs
     long long r = i / a.Wo;
     const int y = (int)(r % a.Ho); r /= a.Ho;
     const int f = (int)r;                          // frame index in pipeline order: (b, v, t)
-    const int t = f % a.T, v = (f / a.T) % a.V, b = f / (a.T * a.V);
-    // boxes come from the host: clamp them to the frame so a bad box can never read outside it
-    const int left = min(max(a.boxes[4 * f], 0), a.Ws - 1), top = min(max(a.boxes[4 * f + 1], 0), a.Hs - 1);
-    const int right = min(max(a.boxes[4 * f + 2], left + 1), a.Ws), bottom = min(max(a.boxes[4 * f + 3], top + 1), a.Hs);
-    const int cw = right - left, ch = bottom - top;
-    const int xr = a.flips[f] ? a.Wo - 1 - x : x;  // cv2.flip(img, 1) AFTER the resize
-    int sx, sx1, ax0, ax1, sy, sy1, by0, by1;
-    cv_linear_coef<true>(xr, cw, a.Wo, sx, sx1, ax0, ax1);
-    cv_linear_coef<false>(y, ch, a.Ho, sy, sy1, by0, by1);
-    const uint8_t* img = a.src + (size_t)f * a.Hs * a.Ws * 3;
-    const uint8_t* p00 = img + ((size_t)(top + sy) * a.Ws + left + sx) * 3;
-    const uint8_t* p01 = img + ((size_t)(top + sy) * a.Ws + left + sx1) * 3;
-    const uint8_t* p10 = img + ((size_t)(top + sy1) * a.Ws + left + sx) * 3;
-    const uint8_t* p11 = img + ((size_t)(top + sy1) * a.Ws + left + sx1) * 3;
-    float o[3];
+    const FrameSrc s = frame_src<RAGGED>(a, f);
+    float o[3] = {0.f, 0.f, 0.f};                  // what a sample with a bad descriptor row gets
+    if (!RAGGED || s.img) {
+      int u[3];
+      resize_pixel(a, s, f, x, y, u);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int h0 = p00[c] * ax0 + p01[c] * ax1;          // horizontal pass, 8 + 11 bits
-      const int h1 = p10[c] * ax0 + p11[c] * ax1;
-      const int u = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;   // vertical pass
-      const float d = (float)((double)u - a.mean[c]);       // cv2.subtract(float32 image, float64 scalar)
-      o[c] = (float)((double)d * a.stdinv[c]);              // cv2.multiply(..., 1/std)
+      for (int c = 0; c < 3; ++c) o[c] = normalized(a, c, u[c]);
     }
-    if (a.imgs) {
-      const size_t plane = (size_t)a.T * a.Ho * a.Wo;
-      float* q = a.imgs + (((size_t)b * a.V + v) * 3) * plane + ((size_t)t * a.Ho + y) * a.Wo + x;
-      q[0] = o[0]; q[plane] = o[1]; q[2 * plane] = o[2];
-    }
-    if (a.x4) {   // frame order of the backbone batch: (view, b, t), as vfs_imgs_to_nhwc4
-      const size_t fr = ((size_t)v * a.B + b) * a.T + t;
-      u32x2 pk;
-      pk.x = pack2bf(o[0], o[1]);
-      pk.y = pack2bf(o[2], 0.f);
-      st8(a.x4 + ((fr * a.Ho + y) * a.Wp + x) * 4, pk);
-      if (a.Wp > a.Wo && x == a.Wo - 1) st8(a.x4 + ((fr * a.Ho + y) * a.Wp + a.Wo) * 4, (u32x2){0u, 0u});
-    }
+    store_pixel(a, f, x, y, o);
   }
 }
 
@@ -85,7 +130,8 @@ int vfs_crop_resize_flip_norm_launch(const PipelineArgs& a, hipStream_t s) {
   const long long total = (long long)a.B * a.V * a.T * a.Ho * a.Wo;
   long long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(crop_resize_flip_norm_kernel, dim3((int)blocks), dim3(256), 0, s, a);
+  if (a.ragged) hipLaunchKernelGGL(crop_resize_flip_norm_kernel<true>, dim3((int)blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(crop_resize_flip_norm_kernel<false>, dim3((int)blocks), dim3(256), 0, s, a);
   return vfs_check_launch("crop_resize_flip_norm");
 }
 
@@ -195,57 +241,21 @@ __device__ __forceinline__ void jitter_op(int op, const PhotoFrame& ph, int cmea
 
 __device__ __forceinline__ uint32_t pack_rgb(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
 
-// crop + resize + flip of one output pixel: the arithmetic of crop_resize_flip_norm_kernel (uint8 per channel)
-__device__ __forceinline__ void resize_pixel(const PipelineArgs& a, int f, int x, int y, int u[3]) {
-  const int left = min(max(a.boxes[4 * f], 0), a.Ws - 1), top = min(max(a.boxes[4 * f + 1], 0), a.Hs - 1);
-  const int right = min(max(a.boxes[4 * f + 2], left + 1), a.Ws), bottom = min(max(a.boxes[4 * f + 3], top + 1), a.Hs);
-  const int cw = right - left, ch = bottom - top;
-  const int xr = a.flips[f] ? a.Wo - 1 - x : x;
-  int sx, sx1, ax0, ax1, sy, sy1, by0, by1;
-  cv_linear_coef<true>(xr, cw, a.Wo, sx, sx1, ax0, ax1);
-  cv_linear_coef<false>(y, ch, a.Ho, sy, sy1, by0, by1);
-  const uint8_t* img = a.src + (size_t)f * a.Hs * a.Ws * 3;
-  const uint8_t* p00 = img + ((size_t)(top + sy) * a.Ws + left + sx) * 3;
-  const uint8_t* p01 = img + ((size_t)(top + sy) * a.Ws + left + sx1) * 3;
-  const uint8_t* p10 = img + ((size_t)(top + sy1) * a.Ws + left + sx) * 3;
-  const uint8_t* p11 = img + ((size_t)(top + sy1) * a.Ws + left + sx1) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int h0 = p00[c] * ax0 + p01[c] * ax1;
-    const int h1 = p10[c] * ax0 + p11[c] * ax1;
-    u[c] = min((((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2, 255);
-  }
-}
-
-// mmcv.imnormalize_ + FormatShape of one uint8 pixel, both outputs laid out as crop_resize_flip_norm_kernel writes them
+// mmcv.imnormalize_ + FormatShape of one uint8 pixel
 __device__ __forceinline__ void store_normalized(const PipelineArgs& a, int f, int x, int y, uint32_t px) {
-  const int t = f % a.T, v = (f / a.T) % a.V, b = f / (a.T * a.V);
   float o[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int u = (int)((px >> (8 * c)) & 255u);
-    const float d = (float)((double)u - a.mean[c]);
-    o[c] = (float)((double)d * a.stdinv[c]);
-  }
-  if (a.imgs) {
-    const size_t plane = (size_t)a.T * a.Ho * a.Wo;
-    float* q = a.imgs + (((size_t)b * a.V + v) * 3) * plane + ((size_t)t * a.Ho + y) * a.Wo + x;
-    q[0] = o[0]; q[plane] = o[1]; q[2 * plane] = o[2];
-  }
-  if (a.x4) {
-    const size_t fr = ((size_t)v * a.B + b) * a.T + t;
-    u32x2 pk;
-    pk.x = pack2bf(o[0], o[1]);
-    pk.y = pack2bf(o[2], 0.f);
-    st8(a.x4 + ((fr * a.Ho + y) * a.Wp + x) * 4, pk);
-    if (a.Wp > a.Wo && x == a.Wo - 1) st8(a.x4 + ((fr * a.Ho + y) * a.Wp + a.Wo) * 4, (u32x2){0u, 0u});
-  }
+  for (int c = 0; c < 3; ++c) o[c] = normalized(a, c, (int)((px >> (8 * c)) & 255u));
+  store_pixel(a, f, x, y, o);
 }
 
 // launch A: grid (pixel blocks, frames)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void photo_resize_kernel(PhotoArgs pa) {
   const PipelineArgs& a = pa.p;
   const int f = blockIdx.y;
+  const FrameSrc fs = frame_src<RAGGED>(a, f);
+  if (RAGGED && !fs.img) return;     // block-uniform: a bad descriptor row, launch B writes the frame's zeros
   const PhotoFrame ph = load_photo(pa.photo + 8 * f);
   const long long hw = (long long)a.Ho * a.Wo;
   uint32_t* out = pa.pix + (size_t)f * hw;
@@ -253,7 +263,9 @@ __global__ __launch_bounds__(256) void photo_resize_kernel(PhotoArgs pa) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < hw; i += (long long)gridDim.x * 256) {
     const int x = (int)(i % a.Wo), y = (int)(i / a.Wo);
     int u[3];
-    resize_pixel(a, f, x, y, u);
+    resize_pixel(a, fs, f, x, y, u);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = min(u[c], 255);     // cv2.resize's saturate_cast<uchar>
     for (int k = 0; k < ph.split; ++k) jitter_op(ph.ops[k], ph, 0, u[0], u[1], u[2]);
     out[i] = pack_rgb(u[0], u[1], u[2]);
     lsum += (uint32_t)pil_luma(u[0], u[1], u[2]);
@@ -289,9 +301,18 @@ __device__ __forceinline__ uint32_t photo_post(uint32_t px, const PhotoFrame& ph
 }
 
 // launch B: grid (column tiles, row tiles, frames)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void photo_finish_kernel(PhotoArgs pa) {
   const PipelineArgs& a = pa.p;
   const int f = blockIdx.z, x0 = blockIdx.x * PHOTO_TW, y0 = blockIdx.y * PHOTO_TH;
+  if (RAGGED && !frame_src<RAGGED>(a, f).img) {     // block-uniform: a bad descriptor row, launch A wrote nothing for the frame
+    const float zero[3] = {0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+      const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+      if (x < a.Wo && y < a.Ho) store_pixel(a, f, x, y, zero);
+    }
+    return;
+  }
   const PhotoFrame ph = load_photo(pa.photo + 8 * f);
   const uint32_t* in = pa.pix + (size_t)f * a.Ho * a.Wo;
   int cmean = 0;
@@ -357,11 +378,13 @@ int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& pa, hipStream_t s) {
   const long long hw = (long long)a.Ho * a.Wo;
   long long bx = (hw + 255) / 256;
   if (bx > 4096) bx = 4096;
-  hipLaunchKernelGGL(photo_resize_kernel, dim3((int)bx, (int)F), dim3(256), 0, s, pa);
+  if (a.ragged) hipLaunchKernelGGL(photo_resize_kernel<true>, dim3((int)bx, (int)F), dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL(photo_resize_kernel<false>, dim3((int)bx, (int)F), dim3(256), 0, s, pa);
   int rc = vfs_check_launch("photo_resize");
   if (rc != VFS_OK) return rc;
   const int tx = (a.Wo + PHOTO_TW - 1) / PHOTO_TW, ty = (a.Ho + PHOTO_TH - 1) / PHOTO_TH;
   if (ty > 65535) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: output too tall");
-  hipLaunchKernelGGL(photo_finish_kernel, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
+  if (a.ragged) hipLaunchKernelGGL(photo_finish_kernel<true>, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL(photo_finish_kernel<false>, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
   return vfs_check_launch("photo_finish");
 }

@@ -551,6 +551,9 @@ int vfs_pose_heatmaps_launch(const PoseHeatmapArgs& a, hipStream_t s);
 // ---- pipeline.hip: training input pipeline ----------------------------------------------------------------
 struct PipelineArgs {
   const uint8_t* src;    // [F][Hs][Ws][3] decoded RGB frames, F = B*V*T in pipeline order (b, v, t)
+  bool ragged;           // the ragged entry points: src is a byte buffer described per sample, Hs and Ws are unused
+  const int* srcdesc;    //   [B][4] = offset low, offset high, Hs, Ws; the sample's V*T frames [V*T][Hs_b][Ws_b][3] lie at src + offset_b,
+  long long src_bytes;   //   all of them inside [src, src + src_bytes) or the sample's outputs are zeros
   const int* boxes;      // [F][4] crop box left, top, right, bottom (img[top:bottom, left:right])
   const uint8_t* flips;  // [F] horizontal flip after the resize
   float* imgs;           // optional out: fp32 [B][V][3][T][Ho][Wo]

@@ -9,9 +9,15 @@ RandomGrayScale and RandomGaussianBlur between Flip and Normalize (augmentations
 them present the chain runs as two launches (`vfs_crop_resize_flip_photo_norm`) that apply them to the uint8
 resized frame, where the reference's PIL / cv2 calls act.
 
+DecordDecode returns every video at its own size (Kinetics-400: 340x256, 454x256, 256x340, ...) and the reference crops
+and resizes sample by sample; a batch of such samples is packed into one byte buffer (`pack_frames`) and goes through
+the same one or two launches (`vfs_crop_resize_flip_norm_ragged`, `vfs_crop_resize_flip_photo_norm_ragged`), which
+read a per-sample descriptor table {offset, Hs, Ws}.
+
 The random decisions are drawn on the host with the reference's own rules and RNG streams
 (`np.random` for the candidates / flips, `random.randint` for the offsets): seeding both reproduces the
 reference's boxes and flips (tests/golden/pipeline_decisions.npz)."""
+import collections
 import math
 import random
 
@@ -131,10 +137,61 @@ def pack_photometric(photo):
     return rows
 
 
+class PackedFrames(collections.namedtuple('PackedFrames', 'buffer offsets shapes')):
+    """A batch whose samples were decoded at different sizes, as the ragged kernels read it: `buffer` 1-D uint8 on the
+    device, sample i's frames uint8 [F][Hs_i][Ws_i][3] at byte `offsets[i]` of it (python ints, no alignment needed),
+    `shapes[i]` = (Hs_i, Ws_i).  Made by pack_frames, or by a loader that decodes straight into one buffer."""
+    __slots__ = ()
+
+
+def _sample_info(i, s):
+    """(device, shape) of sample i of a mixed-size batch; ValueError for anything but uint8 [F][Hs][Ws][3]"""
+    if not isinstance(s, (np.ndarray, torch.Tensor)):
+        raise ValueError(f'sample {i}: a numpy array or a tensor is expected, got {type(s).__name__}')
+    if s.dtype != (torch.uint8 if isinstance(s, torch.Tensor) else np.uint8):
+        raise ValueError(f'sample {i}: dtype {s.dtype}, decoded frames are uint8')
+    shape = tuple(int(v) for v in s.shape)
+    if len(shape) != 4 or shape[3] != 3 or min(shape) <= 0:
+        raise ValueError(f'sample {i}: shape {shape}, expected [F][Hs][Ws][3]')
+    return (s.device if isinstance(s, torch.Tensor) else torch.device('cpu')), shape
+
+
+def pack_frames(samples, device=None, pinned=None):
+    """B decoded samples, each uint8 [F][Hs_i][Ws_i][3] at its own size (numpy arrays, host tensors or device tensors, all on
+    one device) -> PackedFrames on `device` (None: where the samples are).  Host samples are written back to back into one
+    staging tensor - `pinned` when the caller passes a 1-D uint8 tensor that is large enough, so that a loader can reuse
+    its pinned buffer (and must not refill it before the copy has run), else a fresh one, pinned when there is a GPU -
+    and uploaded with ONE non-blocking copy; device samples are concatenated with one torch.cat."""
+    if len(samples) == 0:
+        raise ValueError('pack_frames: no samples')
+    infos = [_sample_info(i, s) for i, s in enumerate(samples)]
+    src = infos[0][0]
+    for i, (d, _) in enumerate(infos):
+        if d != src:
+            raise ValueError(f'sample {i}: on {d}, sample 0 is on {src} (one device per batch)')
+    device = src if device is None else torch.device(device)
+    sizes = [int(np.prod(shape)) for _, shape in infos]
+    offsets = [int(v) for v in np.cumsum([0] + sizes[:-1])]
+    shapes = [shape[1:3] for _, shape in infos]
+    total = sum(sizes)
+    if src.type != 'cpu':
+        buffer = torch.cat([s.reshape(-1) for s in samples]).to(device)
+        return PackedFrames(buffer, offsets, shapes)
+    if (pinned is None or pinned.dtype != torch.uint8 or pinned.dim() != 1 or pinned.device.type != 'cpu'
+            or not pinned.is_contiguous() or pinned.numel() < total):
+        pinned = torch.empty(total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    stage = pinned.numpy()
+    for s, off, n in zip(samples, offsets, sizes):
+        stage[off:off + n] = (s.numpy() if isinstance(s, torch.Tensor) else s).reshape(-1)
+    return PackedFrames(pinned[:total].to(device, non_blocking=True), offsets, shapes)
+
+
 class GpuTrainPipeline:
     """Built from the reference's `train_pipeline` list; `__call__(frames)` with frames uint8
     [B][num_clips*clip_len][Hs][Ws][3] on the GPU returns dict(imgs=fp32 [B][num_clips][3][clip_len][H][W])
-    (and x4, the bf16 NHWC4 frames, when asked)."""
+    (and x4, the bf16 NHWC4 frames, when asked).  A batch of samples decoded at different sizes (DecordDecode on
+    Kinetics: 340x256, 454x256, 256x340, ...) goes in as a list of per-sample [num_clips*clip_len][Hs_i][Ws_i][3]
+    arrays / tensors or as a PackedFrames, through the same number of launches (`vfs_crop_resize_flip_norm_ragged`)."""
 
     def __init__(self, pipeline_cfg, num_clips=None, clip_len=None):
         if num_clips is None or clip_len is None:
@@ -274,16 +331,49 @@ class GpuTrainPipeline:
             self._ws = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
         return self._ws
 
-    def __call__(self, frames, boxes=None, flips=None, want_x4=False, want_imgs=True, photo=None):
+    def _ragged_input(self, frames, device):
+        """a list of per-sample frames or a PackedFrames -> (PackedFrames, int32 [B][4] descriptor table of the ragged
+        entry points: offset low, offset high, Hs, Ws per sample), checked here: the kernels zero a sample whose row is
+        bad, the host names it"""
+        F = self.num_clips * self.clip_len
+        if not isinstance(frames, PackedFrames):
+            for i, s in enumerate(frames):
+                if _sample_info(i, s)[1][0] != F:
+                    raise ValueError(f'sample {i}: {s.shape[0]} frames, the pipeline takes num_clips * clip_len = {F}')
+            frames = pack_frames(frames, device)
+        buf = frames.buffer
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+            raise ValueError('PackedFrames.buffer: a contiguous 1-D uint8 tensor is expected')
+        if len(frames.offsets) != len(frames.shapes) or len(frames.shapes) == 0:
+            raise ValueError(f'PackedFrames: {len(frames.offsets)} offsets, {len(frames.shapes)} shapes')
+        desc = np.empty((len(frames.shapes), 4), np.uint32)
+        for i, (off, (Hs, Ws)) in enumerate(zip(frames.offsets, frames.shapes)):
+            off, Hs, Ws = int(off), int(Hs), int(Ws)
+            if Hs <= 0 or Ws <= 0 or max(Hs, Ws) >= 1 << 31:
+                raise ValueError(f'sample {i}: frame size {Hs} x {Ws}')
+            if off < 0 or off + F * Hs * Ws * 3 > buf.numel():
+                raise ValueError(f'sample {i}: {F} frames of {Hs} x {Ws} at offset {off} do not fit the buffer of {buf.numel()} bytes')
+            desc[i] = off & 0xFFFFFFFF, off >> 32, Hs, Ws
+        return frames, desc.view(np.int32)
+
+    def __call__(self, frames, boxes=None, flips=None, want_x4=False, want_imgs=True, photo=None, device=None):
         """boxes / flips / photo: decisions to use instead of sampling them (tests); photo = sample_photometric's dict
         (concatenated over the samples) or packed int32 [B*F][8] rows; with explicit boxes and no photo, no frame gets a
-        photometric step"""
-        assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3, frames.shape
-        B, F, Hs, Ws, _ = frames.shape
-        assert F == self.num_clips * self.clip_len
-        dev = frames.device
+        photometric step.  frames: the dense uint8 tensor, or a mixed-size batch: a list / tuple of per-sample frames, packed
+        with pack_frames onto `device` (None: where they are), or a PackedFrames, read in place.  Decisions are drawn sample
+        by sample at the sample's own size: the reference's RNG consumption for the batch"""
+        F = self.num_clips * self.clip_len
+        desc = None
+        if isinstance(frames, (list, tuple)):      # PackedFrames is a tuple
+            frames, desc = self._ragged_input(frames, device)
+            B, dev, shapes = len(frames.shapes), frames.buffer.device, [(int(h), int(w)) for h, w in frames.shapes]
+        else:
+            assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3, frames.shape
+            B, nf, Hs, Ws, _ = frames.shape
+            assert nf == F
+            dev, shapes = frames.device, [(Hs, Ws)] * B
         if boxes is None:      # sample by sample: crop boxes of all its frames, then its flips, then the photometric steps (pipeline order)
-            draws = [self.sample(F, (Hs, Ws)) for _ in range(B)]
+            draws = [self.sample(F, shape) for shape in shapes]
             boxes, flips = np.concatenate([d[0] for d in draws]), np.concatenate([d[1] for d in draws])
             if self.photometric:
                 photo = {k: np.concatenate([d[2][k] for d in draws]) for k in draws[0][2]}
@@ -291,10 +381,21 @@ class GpuTrainPipeline:
         Wp = W + (W & 1)
         imgs = torch.empty(B, self.num_clips, 3, self.clip_len, H, W, device=dev) if want_imgs else None
         x4 = torch.empty(self.num_clips * B * self.clip_len, H, Wp, 4, dtype=BF16, device=dev) if want_x4 else None
-        bt = torch.as_tensor(np.ascontiguousarray(boxes, dtype=np.int32)).to(dev)
-        ft = torch.as_tensor(np.ascontiguousarray(flips, dtype=np.uint8)).to(dev)
+        boxes_i32 = np.ascontiguousarray(boxes, dtype=np.int32)
+        flips_u8 = np.ascontiguousarray(flips, dtype=np.uint8)
+        if boxes_i32.shape != (B * F, 4) or flips_u8.shape != (B * F,):
+            raise ValueError(f'boxes {boxes_i32.shape} / flips {flips_u8.shape}: one row per frame, {B * F} frames')
+        if desc is None:
+            bt = torch.as_tensor(boxes_i32).to(dev)
+            src, size, entry = (frames.contiguous(),), shapes[0], ''
+        else:      # the descriptor table travels with the boxes: one upload
+            tab = torch.as_tensor(np.concatenate([desc.reshape(-1), boxes_i32.reshape(-1)])).to(dev)
+            bt = tab[desc.size:]
+            src, size, entry = (frames.buffer, frames.buffer.numel(), tab[:desc.size]), (), '_ragged'
+        ft = torch.as_tensor(flips_u8).to(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else None
-        out = dict(boxes=boxes, flips=flips)
+        out = dict(boxes=boxes, flips=flips, shapes=shapes)
+        tail = (imgs, x4, B, self.num_clips, self.clip_len, *size, H, W, Wp, *self.mean, *self.std, stream)
         if self.photometric:
             if photo is None:
                 rows = np.zeros((B * F, 8), np.int32)
@@ -307,11 +408,9 @@ class GpuTrainPipeline:
             out['photo_rows'] = rows
             pt = torch.as_tensor(rows).to(dev)
             ws = self._workspace(B * F, H, W, dev)
-            get_lib().crop_resize_flip_photo_norm(frames.contiguous(), bt, ft, pt, ws, ws.numel(), imgs, x4, B, self.num_clips,
-                                                  self.clip_len, Hs, Ws, H, W, Wp, *self.mean, *self.std, stream)
+            getattr(get_lib(), 'crop_resize_flip_photo_norm' + entry)(*src, bt, ft, pt, ws, ws.numel(), *tail)
         else:
-            get_lib().crop_resize_flip_norm(frames.contiguous(), bt, ft, imgs, x4, B, self.num_clips, self.clip_len, Hs, Ws, H,
-                                            W, Wp, *self.mean, *self.std, stream)
+            getattr(get_lib(), 'crop_resize_flip_norm' + entry)(*src, bt, ft, *tail)
         if want_imgs:
             out['imgs'] = imgs
         if want_x4:
