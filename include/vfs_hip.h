@@ -629,6 +629,24 @@ int vfs_labelprop_batch(const vfs_bf16* fbank, float* sbank, void* workspace, lo
                         vfs_stream_t stream);
 int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
                               int COcap, int Ho, int Wo, vfs_stream_t stream);
+/* ---- table-driven ingest of a feature bank: ring banks and streaming (csrc/bank_ingest.hip) ----
+ * For query frame f the reference reads frame 0 and frames max(0, f - precede_frames) .. f - 1 only (vanilla_tracker.py:132-149):
+ * a bank of precede_frames + 2 positions per video serves a clip of any length, and a frame can enter it when it arrives.  One
+ * call stores the feature maps of n images (one new frame of every video of a step) in ONE launch, each image at its own place:
+ *   feats     [n][P][C], the maps as the backbone leaves them (P = H*W rows of C channels per image), fp32 / bf16;
+ *   fbank     [bank_rows][C] in the type of feats, hlbank [bank_rows][2C] or NULL (fp32 only);
+ *   table     device pointer, long long [n][2]: image i goes to rows table[2i] .. table[2i] + P of fbank and to rows table[2i + 1] ..
+ *             of hlbank (ignored without hlbank).  An image whose rows do not lie inside [0, bank_rows) is left out, nothing of it
+ *             is written.  Destinations must not overlap.
+ *   unit_rows 1: a row of fbank = vfs_l2norm_rows_f32 (vfs_l2norm_rows) of the feature row and a row of hlbank =
+ *             vfs_split_rows_bf16x2 of that, bit for bit: the same code; every feature row is read once.  0 (test_cfg.with_norm=False):
+ *             a plain copy, and hlbank must be NULL.
+ * VFS_ERR_SHAPE: n outside 1 .. 65535, P < 1, bank_rows < P, C % 4 (bf16: C % 8), C > 2048 (a row is held in registers), C % 16
+ * with hlbank, feature maps or banks not 16-byte aligned. */
+int vfs_bank_ingest_f32(const float* feats, float* fbank, vfs_bf16* hlbank, const long long* table, int n, long long P, int C,
+                        long long bank_rows, int unit_rows, vfs_stream_t stream);
+int vfs_bank_ingest_bf16(const vfs_bf16* feats, vfs_bf16* fbank, const long long* table, int n, long long P, int C, long long bank_rows,
+                         int unit_rows, vfs_stream_t stream);
 
 /* ---- DAVIS-2017 semi-supervised J&F (datasets/davis_dataset.py:68-140 -> davis2017.evaluation) -----
  * pred / gt: uint8 label maps [T][H][W]; frames 1..T-2 are evaluated (first = given, last excluded);

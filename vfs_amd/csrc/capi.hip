@@ -1154,6 +1154,31 @@ int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, 
                               vfs_stream_t stream) {
   return vfs_seg_postprocess_exact_launch(seg, partial, label, H, W, CO, Ho, Wo, stream_of(stream));
 }
+// ---- table-driven ingest of a feature bank (bank_ingest.hip): the checks both precisions share, and the argument struct ----
+static int bank_ingest_args(const char* who, BankIngestArgs* a, const void* feats, void* fbank, vfs_bf16* hlbank, const long long* table, int n,
+                            long long P, int C, long long bank_rows, int unit_rows) {
+  if (n < 1 || n > BANK_INGEST_MAX_N) return fail(VFS_ERR_SHAPE, who, "1 <= n <= 65535 images");
+  if (P < 1 || P > 4LL * 0x7fffffff || C < 1 || bank_rows < P) return fail(VFS_ERR_SHAPE, who, "P >= 1 (four rows per workgroup), C >= 1, bank_rows >= P");
+  if (!feats || !fbank || !table) return fail(VFS_ERR_ARG, who, "null buffer");
+  if (hlbank && !unit_rows) return fail(VFS_ERR_ARG, who, "a split copy is taken of unit rows only");
+  if (((size_t)feats | (size_t)fbank | (size_t)hlbank) & 15 || (size_t)table & 7)
+    return fail(VFS_ERR_SHAPE, who, "16-byte aligned feature maps and banks, 8-byte aligned table");
+  *a = BankIngestArgs{};
+  a->x = feats; a->fbank = fbank; a->hl = hlbank; a->table = table; a->P = P; a->bank_rows = bank_rows; a->n = n; a->C = C; a->unit = unit_rows != 0;
+  return VFS_OK;
+}
+int vfs_bank_ingest_f32(const float* feats, float* fbank, vfs_bf16* hlbank, const long long* table, int n, long long P, int C,
+                        long long bank_rows, int unit_rows, vfs_stream_t stream) {
+  BankIngestArgs a;
+  if (int rc = bank_ingest_args("bank_ingest_f32", &a, feats, fbank, hlbank, table, n, P, C, bank_rows, unit_rows)) return rc;
+  return vfs_bank_ingest_f32_launch(a, stream_of(stream));
+}
+int vfs_bank_ingest_bf16(const vfs_bf16* feats, vfs_bf16* fbank, const long long* table, int n, long long P, int C, long long bank_rows,
+                         int unit_rows, vfs_stream_t stream) {
+  BankIngestArgs a;
+  if (int rc = bank_ingest_args("bank_ingest_bf16", &a, feats, fbank, nullptr, table, n, P, C, bank_rows, unit_rows)) return rc;
+  return vfs_bank_ingest_bf16_launch(a, stream_of(stream));
+}
 
 int vfs_davis_counts(const uint8_t* pred, const uint8_t* gt, int* counts, void* scratch, int T, int H, int W, int nobj, int radius,
                      int use_void, vfs_stream_t stream) {

@@ -17,6 +17,7 @@
 //     fused steps are written as explicit fmaf();
 //   * exp() of the softmax is the explicit polynomial vexp(); top-k ties go to the lowest candidate index.
 #include "vfs_ops.h"
+#include "vfs_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -465,28 +466,16 @@ int vfs_maxpool_f32_launch(const float* x, float* y, int N, int H, int W, int C,
 }
 
 // F.normalize(p=2, dim=channel, eps=1e-12) of rows [P][C]; one wave per row: lane l owns the float4 groups
-// l, l+64, ... (one fmaf chain), butterfly over the lanes, y = x / max(sqrt(ss), eps)
+// l, l+64, ... (one fmaf chain), butterfly over the lanes, y = x / max(sqrt(ss), eps) - the row arithmetic is vfs_rows.h's
 __global__ __launch_bounds__(256) void l2norm_rows_f32_kernel(const float* __restrict__ x, float* __restrict__ y, long long P, int C) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= P) return;
   const float* src = x + (size_t)row * C;
   float ss = 0.f;
-  for (int g = lane; g * 4 < C; g += 64) {
-    const f32x4 v = ldf4(src + g * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ss = __builtin_fmaf(v[e], v[e], ss);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) ss = ss + __shfl_xor(ss, d);
-  float nrm = sqrtf(ss);
-  nrm = nrm > 1e-12f ? nrm : 1e-12f;
-  for (int g = lane; g * 4 < C; g += 64) {
-    f32x4 v = ldf4(src + g * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = v[e] / nrm;
-    stf4(y + (size_t)row * C + g * 4, v);
-  }
+  for (int g = lane; g * 4 < C; g += 64) ss = rows_f32_sumsq(ldf4(src + g * 4), ss);
+  const float nrm = rows_f32_norm(rows_wave_sum(ss));
+  for (int g = lane; g * 4 < C; g += 64) stf4(y + (size_t)row * C + g * 4, rows_f32_unit(ldf4(src + g * 4), nrm));
 }
 int vfs_l2norm_rows_f32_launch(const float* x, float* y, long long P, int C, hipStream_t s) {
   if (C % 4) return vfs_set_error(VFS_ERR_SHAPE, "l2norm_f32: C % 4");

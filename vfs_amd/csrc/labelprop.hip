@@ -17,33 +17,21 @@
 #include "vfs_conv.h"
 #include "vfs_lpb.h"
 #include "vfs_ops.h"
+#include "vfs_rows.h"
 
 #define LP_TOPK 10
 
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long long P,
                                                           int C) {
-  // one wave per pixel row of C channels (F.normalize(p=2, dim=channel, eps=1e-12))
+  // one wave per pixel row of C channels (F.normalize(p=2, dim=channel, eps=1e-12)); the row arithmetic is vfs_rows.h's
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= P) return;
   const bf16_t* src = x + (size_t)row * C;
   float ss = 0.f;
-  for (int c = lane * 8; c < C; c += 512) {
-    float f[8];
-    unpack8(ld16(src + c), f);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss += f[i] * f[i];
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-  for (int c = lane * 8; c < C; c += 512) {
-    float f[8];
-    unpack8(ld16(src + c), f);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] *= inv;
-    st16(y + (size_t)row * C + c, pack8(f));
-  }
+  for (int c = lane * 8; c < C; c += 512) ss = rows_bf16_sumsq(ld16(src + c), ss);
+  const float inv = rows_bf16_inv(rows_wave_sum(ss));
+  for (int c = lane * 8; c < C; c += 512) st16(y + (size_t)row * C + c, rows_bf16_unit(ld16(src + c), inv));
 }
 
 int vfs_l2norm_rows_launch(const bf16_t* x, bf16_t* y, long long P, int C, hipStream_t s) {

@@ -29,6 +29,7 @@
 // no barrier and no cross-wave traffic inside the channel loop; the four partial 64x64 score tiles meet in LDS once per key block.
 #include "vfs_lpx.h"
 #include "vfs_lpb.h"
+#include "vfs_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -48,15 +49,10 @@ __global__ __launch_bounds__(256) void split_rows_bf16x2_kernel(const float* __r
   const int c8 = (int)(i - row * c8n);
   const float* src = x + (size_t)row * C + c8 * 8;
   const f32x4 v0 = lpx_ldf4(src), v1 = lpx_ldf4(src + 4);
-  float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]}, lo[8];
-  u32x4 hv, lv;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) lo[j] = v[j] - round_bf(v[j]);      // exact in fp32
-  hv = pack8(v);
-  lv = pack8(lo);
-  bf16_t* dst = hl + (size_t)row * 2 * C + (c8 >> 1) * 32 + (c8 & 1) * 8;
-  st16(dst, hv);
-  st16(dst + 16, lv);
+  const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+  bf16_t* dst = hl + (size_t)row * 2 * C + rows_split_at(c8);      // (the split itself: vfs_rows.h)
+  st16(dst, rows_split_hi(v));
+  st16(dst + 16, rows_split_lo(v));
 }
 int vfs_split_rows_bf16x2_launch(const float* x, bf16_t* hl, long long P, int C, hipStream_t s) {
   if (C % 16) return vfs_set_error(VFS_ERR_SHAPE, "split_rows_bf16x2: C % 16");

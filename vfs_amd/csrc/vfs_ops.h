@@ -507,6 +507,20 @@ int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, u
 int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
                                          int Wo, hipStream_t s);
 
+// ---- bank_ingest.hip: the frames of n images enter their positions of a feature bank in one launch (ring banks, streaming) ----
+#define BANK_INGEST_MAX_C 2048      // a row is held in registers between its read and its writes
+#define BANK_INGEST_MAX_N 65535     // the grid's y dimension carries the image
+struct BankIngestArgs {
+  const void* x;             // [n][P][C] the feature maps of n images as the backbone leaves them (fp32 / bf16)
+  void* fbank;               // [bank_rows][C] in the type of x
+  bf16_t* hl;                // [bank_rows][2C] split copy (vfs_split_rows_bf16x2 layout) or null; fp32 unit rows only
+  const long long* table;    // device [n][2]: image i goes to rows table[2i] .. + P of fbank and rows table[2i + 1] .. + P of hl
+  long long P, bank_rows;    // rows per image; rows of the banks: an image whose destination does not lie inside is left out
+  int n, C, unit;            // unit = 0: plain copy (test_cfg.with_norm=False)
+};
+int vfs_bank_ingest_f32_launch(const BankIngestArgs& a, hipStream_t s);
+int vfs_bank_ingest_bf16_launch(const BankIngestArgs& a, hipStream_t s);
+
 // ---- davis.hip: DAVIS J&F ingredients ---------------------------------------------------------------------
 struct DavisArgs {
   const uint8_t* pred;   // [T][H][W] predicted labels

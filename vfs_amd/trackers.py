@@ -682,8 +682,16 @@ class VanillaTracker(BaseTracker):
         from .labelprop import forward_test_hip
         return forward_test_hip(self, imgs, ref_seg_map, img_meta)
 
-    def forward_test_batch(self, imgs_list, ref_seg_maps, img_metas, batch=8):
+    def forward_test_batch(self, imgs_list, ref_seg_maps, img_metas, batch=8, ring=False):
         """forward_test of many videos, `batch` of them at a time in lock-step on the device (vfs_amd/labelprop.py):
-        out[i] == forward_test(imgs_list[i], ref_seg_maps[i], img_metas[i])[0]"""
+        out[i] == forward_test(imgs_list[i], ref_seg_maps[i], img_metas[i])[0].  ring=True: a slot's banks hold
+        precede_frames + 2 frame positions instead of every frame of the longest clip; the same results"""
         from .labelprop import forward_test_batch_hip
-        return forward_test_batch_hip(self, imgs_list, ref_seg_maps, img_metas, batch)
+        return forward_test_batch_hip(self, imgs_list, ref_seg_maps, img_metas, batch, ring)
+
+    def open_stream(self, first, ref_seg_map, img_meta):
+        """forward_test for frames that arrive one at a time: first [1,3,H,W] (normalised fp32, as forward_test takes its clip) and its
+        label map open a stream `s`; s.first holds frame 0 of what forward_test returns, s.push(frames [1,3,H,W] or [1,3,t,H,W]) returns
+        its rows [t, ...] of the pushed frames, s.close() releases the device buffers (vfs_amd/labelprop.py LabelPropStream)"""
+        from .labelprop import LabelPropStream
+        return LabelPropStream(self, first, ref_seg_map, img_meta)
