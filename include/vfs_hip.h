@@ -589,10 +589,11 @@ int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, 
  *             its own class count, [frame][H*W][CO_n].  The output of a step is frame `qframe` of the slot's label rows.
  *   desc      device pointer to the rows of THIS step, int32 [nslots][VFS_LPB_DESC_INTS]: [0] active (0: the slot's workgroups
  *             leave at once, nothing of the slot is read or written), [1] qframe, [2] nkeys, [3] non_mask_len, [4] CO_n,
- *             [5..7] reserved (0), [8..71] key frames (frame indices inside the slot, reference order).  A caller that knows every
- *             clip's length writes the rows of all steps once ([steps][nslots][VFS_LPB_DESC_INTS]) and passes row block `step`:
- *             nothing is copied to the device inside the step loop.  A row outside the single-video ranges (qframe / key frames
- *             < Tcap, 1 <= nkeys <= max_nkeys, 0 <= non_mask_len < nkeys, 1 <= CO_n <= COcap) is treated as inactive.
+ *             [5] map position (read by the post-processing only, below; the propagation kernels do not read it), [6..7] reserved
+ *             (0), [8..71] key frames (frame indices inside the slot, reference order).  A caller that knows every clip's length
+ *             writes the rows of all steps once ([steps][nslots][VFS_LPB_DESC_INTS]) and passes row block `step`: nothing is copied
+ *             to the device inside the step loop.  A row outside the single-video ranges (qframe / key frames < Tcap, 1 <= nkeys <=
+ *             max_nkeys, 0 <= non_mask_len < nkeys, 1 <= CO_n <= COcap) is treated as inactive.
  *   host side nactive = active rows of this step (the key-frame splits are chosen for that many videos sharing the chip),
  *             max_nkeys >= every active row's nkeys (sizes the grids).
  *   workspace per slot, as the single-video calls: vfs_labelprop_f32_batch_workspace_bytes(H, W, nslots);
@@ -601,8 +602,11 @@ int vfs_seg_postprocess_exact(const float* seg, float* partial, uint8_t* label, 
  *             slot, decided on the device; the other slots are not touched) + nslots regions in the single-video layout.
  *   vfs_labelprop_f32_2pass_batch runs the dense kernels for every slot when hlbank = NULL, unit_rows = 0 or C is not 256 / 512 / 1024.
  * vfs_seg_postprocess_exact_batch / vfs_bilinear_resize_f32_batch: the per-step post-processing of every active slot in one launch
- * set, from frame qframe of the slot's label rows into frame qframe of preds: uint8 [nslots][Tcap][Ho*Wo] label maps (partial: fp32
- * [nslots][64][COcap][2]), or fp32 soft maps, slot n at n * Tcap * COcap * Ho*Wo holding [frame][CO_n][Ho][Wo] packed. */
+ * set, from frame qframe ([1]) of the slot's label rows into the map position ([5]) of the slot's maps.  The maps have Tmaps
+ * positions per slot, whatever Tcap is (a ring bank of a few positions feeds the maps of a whole clip): preds uint8
+ * [nslots][Tmaps][Ho*Wo] label maps (partial: fp32 [nslots][64][COcap][2]), or fp32 soft maps, slot n at n * Tmaps * COcap * Ho*Wo
+ * holding [map position][CO_n][Ho][Wo] packed.  A row whose map position is outside [0, Tmaps), whose qframe is outside [0, Tcap)
+ * or whose CO_n is outside [1, COcap] is inactive for the post-processing: nothing of the slot is written. */
 #define VFS_LPB_DESC_INTS 72
 int vfs_labelprop_f32_batch_workspace_bytes(int H, int W, int nslots, long long* bytes);
 int vfs_labelprop_f32_batch(const float* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots,
@@ -612,10 +616,10 @@ int vfs_labelprop_f32_2pass_batch_workspace_bytes(int H, int W, int entries_per_
 int vfs_labelprop_f32_2pass_batch(const float* fbank, const vfs_bf16* hlbank, float* sbank, void* workspace, long long workspace_bytes,
                                   const int* desc, int nslots, int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap,
                                   int radius, int topk, float temperature, int unit_rows, vfs_stream_t stream);
-int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H,
-                                    int W, int COcap, int Ho, int Wo, vfs_stream_t stream);
-int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap,
-                                  int Ho, int Wo, vfs_stream_t stream);
+int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps,
+                                    int H, int W, int COcap, int Ho, int Wo, vfs_stream_t stream);
+int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H, int W,
+                                  int COcap, int Ho, int Wo, vfs_stream_t stream);
 /* The same lock-step for the bf16 kernels (test_cfg.precision = 'bf16'): vfs_labelprop_batch is one step of vfs_labelprop in every
  * slot, vfs_seg_postprocess_batch one vfs_seg_postprocess of every active slot's propagated frame (soft maps: vfs_bilinear_resize_f32_batch,
  * which does not depend on the precision).  Banks, descriptor rows, preds and partial as above, with fbank bf16 [nslots][Tcap][H*W][C]
@@ -627,8 +631,8 @@ int vfs_labelprop_batch_workspace_bytes(int H, int W, int nslots, long long* byt
 int vfs_labelprop_batch(const vfs_bf16* fbank, float* sbank, void* workspace, long long workspace_bytes, const int* desc, int nslots,
                         int nactive, int max_nkeys, int Tcap, int H, int W, int C, int COcap, int radius, int topk, float temperature,
                         vfs_stream_t stream);
-int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                              int COcap, int Ho, int Wo, vfs_stream_t stream);
+int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                              int W, int COcap, int Ho, int Wo, vfs_stream_t stream);
 /* ---- table-driven ingest of a feature bank: ring banks and streaming (csrc/bank_ingest.hip) ----
  * For query frame f the reference reads frame 0 and frames max(0, f - precede_frames) .. f - 1 only (vanilla_tracker.py:132-149):
  * a bank of precede_frames + 2 positions per video serves a clip of any length, and a frame can enter it when it arrives.  One

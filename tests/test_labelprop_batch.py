@@ -30,10 +30,10 @@ def _features(T, HW, C, CO, seed, smooth=0.0):
 
 
 def _desc_rows(nslots, rows):
-    """rows: {slot: (qframe, key frames, non_mask_len, CO)}; the other slots are inactive"""
+    """rows: {slot: (qframe, key frames, non_mask_len, CO[, map position: qframe])}; the other slots are inactive"""
     d = torch.zeros(nslots, DESC, dtype=torch.int32)
-    for n, (qframe, keys, nml, CO) in rows.items():
-        d[n, 0], d[n, 1], d[n, 2], d[n, 3], d[n, 4] = 1, qframe, len(keys), nml, CO
+    for n, (qframe, keys, nml, CO, *mpos) in rows.items():
+        d[n, 0], d[n, 1], d[n, 2], d[n, 3], d[n, 4], d[n, 5] = 1, qframe, len(keys), nml, CO, (mpos[0] if mpos else qframe)
         d[n, 8:8 + len(keys)] = torch.tensor(keys, dtype=torch.int32)
     return d
 
@@ -202,9 +202,9 @@ def test_batched_postprocessing(backend):
     desc = _desc_rows(3, {n: (qf[n], [0], 0, cos[n]) for n in range(3)})
     preds = torch.full((3, Tcap, Ho * Wo), 255, dtype=torch.uint8)
     partial = torch.zeros(3, 64, COcap, 2)
-    lib.seg_postprocess_exact_batch(sb, partial, preds, desc, 3, Tcap, H, W, COcap, Ho, Wo, None)
+    lib.seg_postprocess_exact_batch(sb, partial, preds, desc, 3, Tcap, Tcap, H, W, COcap, Ho, Wo, None)
     soft = torch.full((3, Tcap * COcap * Ho * Wo), float('nan'))
-    lib.bilinear_resize_f32_batch(sb, soft, desc, 3, Tcap, H, W, COcap, Ho, Wo, None)
+    lib.bilinear_resize_f32_batch(sb, soft, desc, 3, Tcap, Tcap, H, W, COcap, Ho, Wo, None)
     for n in range(3):
         lab = torch.zeros(Ho * Wo, dtype=torch.uint8)
         lib.seg_postprocess_exact(segs[n], torch.zeros(64 * cos[n] * 2), lab, H, W, cos[n], Ho, Wo, None)
@@ -218,6 +218,85 @@ def test_batched_postprocessing(backend):
         assert same_bits(soft[n, qf[n] * per:(qf[n] + 1) * per].numpy(), up.reshape(-1).numpy()), n
         rest = torch.cat([soft[n, :qf[n] * per], soft[n, (qf[n] + 1) * per:]])
         assert torch.isnan(rest).all()
+
+
+SENTINEL = 0xA5      # every byte of preds, the soft maps and partial before a call
+
+
+def _sentinel(shape, dtype):
+    t = torch.empty(shape, dtype=dtype)
+    t.view(torch.uint8).fill_(SENTINEL)
+    return t
+
+
+def _untouched(t):
+    return bool((t.contiguous().view(torch.uint8) == SENTINEL).all())
+
+
+def check_map_positions(lib, batch, single):
+    """label maps with a map position of their own (descriptor column 5), for `batch` = seg_postprocess_exact_batch / seg_postprocess_batch
+    against `single` = seg_postprocess_exact / seg_postprocess: 3 slots of 9 x 11 -> 37 x 45 (the bilinear clamp on both axes), 5, 2 and 3
+    classes inside COcap = 5, Tcap = 4 positions of label rows and Tmaps = 7 of maps.  Slot 0 reads position 3 and writes map 6, slot 1
+    is inactive, slot 2 reads position 1 and writes map 0 - bit for bit the single-video call, and no other byte of preds changes.
+    Then map positions Tmaps and -1: nothing is written; Tmaps = 0: refused, nothing written.  -> (label rows, descriptor rows)"""
+    from vfs_amd._lib import VfsError
+    H, W, Ho, Wo, Tcap, Tmaps, COcap = 9, 11, 37, 45, 4, 7, 5
+    HW = H * W
+    plan = {0: (3, 6, 5), 2: (1, 0, 3)}      # slot: (position of the label rows, map position, classes)
+    g = torch.Generator().manual_seed(51)
+    sb = torch.full((3, Tcap * HW * COcap), float('nan'))
+    sb[1, :HW * 2] = torch.randn(HW * 2, generator=g)      # slot 1 holds rows (2 classes) and sits the step out
+    segs = {}
+    for n, (q, m, CO) in plan.items():
+        segs[n] = torch.randn(HW, CO, generator=g)
+        sb[n, q * HW * CO:(q + 1) * HW * CO] = segs[n].reshape(-1)
+    rows = {n: (q, [0], 0, CO, m) for n, (q, m, CO) in plan.items()}
+    preds, partial = _sentinel((3, Tmaps, Ho * Wo), torch.uint8), _sentinel((3, 64, COcap, 2), torch.float32)
+    batch(sb, partial, preds, _desc_rows(3, rows), 3, Tcap, Tmaps, H, W, COcap, Ho, Wo, None)
+    for n, (q, m, CO) in plan.items():
+        lab = torch.zeros(Ho * Wo, dtype=torch.uint8)
+        single(segs[n], torch.zeros(64 * CO * 2), lab, H, W, CO, Ho, Wo, None)
+        assert len(set(lab.tolist())) > 1
+        assert torch.equal(preds[n, m], lab), n
+        assert _untouched(preds[n, [p for p in range(Tmaps) if p != m]]), n
+    assert _untouched(preds[1]) and _untouched(partial[1])
+    for bad, Tm, refused in (({0: Tmaps, 2: -1}, Tmaps, False), ({}, 0, True)):
+        preds, partial = _sentinel((3, Tmaps, Ho * Wo), torch.uint8), _sentinel((3, 64, COcap, 2), torch.float32)
+        desc = _desc_rows(3, {n: r[:4] + (bad.get(n, r[4]),) for n, r in rows.items()})
+        if refused:
+            with pytest.raises(VfsError, match=r'failed \(-1\)'):      # csrc/vfs_common.h: VFS_ERR_SHAPE
+                batch(sb, partial, preds, desc, 3, Tcap, Tm, H, W, COcap, Ho, Wo, None)
+        else:
+            batch(sb, partial, preds, desc, 3, Tcap, Tm, H, W, COcap, Ho, Wo, None)
+        assert _untouched(preds) and _untouched(partial), (bad, Tm)
+    return sb, segs, rows
+
+
+def test_batched_postprocessing_map_positions(backend):
+    """fp32 label maps (check_map_positions) and the soft maps of the same rows: slot n starts at n * Tmaps * COcap * Ho * Wo and holds
+    [map position][CO_n][Ho][Wo] packed, so slot 0's map 6 (5 classes) and slot 2's map 0 (3 classes) lie at their own offsets"""
+    from vfs_amd._lib import VfsError
+    lib = backend.hostlib
+    sb, segs, rows = check_map_positions(lib, lib.seg_postprocess_exact_batch, lib.seg_postprocess_exact)
+    H, W, Ho, Wo, Tcap, Tmaps, COcap = 9, 11, 37, 45, 4, 7, 5
+    soft = _sentinel((3, Tmaps * COcap * Ho * Wo), torch.float32)
+    lib.bilinear_resize_f32_batch(sb, soft, _desc_rows(3, rows), 3, Tcap, Tmaps, H, W, COcap, Ho, Wo, None)
+    for n, (q, _, _, CO, m) in rows.items():
+        up = torch.zeros(CO, Ho, Wo)
+        lib.bilinear_resize_f32(segs[n], up, CO, H, W, Ho, Wo, 1, 0, None)
+        per = CO * Ho * Wo
+        assert same_bits(soft[n, m * per:(m + 1) * per].numpy(), up.reshape(-1).numpy()), n
+        assert _untouched(soft[n, :m * per]) and _untouched(soft[n, (m + 1) * per:]), n
+    assert _untouched(soft[1])
+    for bad, Tm, refused in (({0: Tmaps, 2: -1}, Tmaps, False), ({}, 0, True)):
+        soft = _sentinel((3, Tmaps * COcap * Ho * Wo), torch.float32)
+        desc = _desc_rows(3, {n: r[:4] + (bad.get(n, r[4]),) for n, r in rows.items()})
+        if refused:
+            with pytest.raises(VfsError, match=r'failed \(-1\)'):
+                lib.bilinear_resize_f32_batch(sb, soft, desc, 3, Tcap, Tm, H, W, COcap, Ho, Wo, None)
+        else:
+            lib.bilinear_resize_f32_batch(sb, soft, desc, 3, Tcap, Tm, H, W, COcap, Ho, Wo, None)
+        assert _untouched(soft), (bad, Tm)
 
 
 def test_invalid_rows_and_arguments_are_refused(emu_backend):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_labelprop_batch import _assert_same, _desc_rows, _features, _per_video, _tracker, _videos, same_bits
+from tests.test_labelprop_batch import _assert_same, _desc_rows, _features, _per_video, _tracker, _videos, check_map_positions, same_bits
 
 TEMP = 0.07
 
@@ -135,7 +135,7 @@ def test_batched_bf16_postprocessing(backend):
     desc = _desc_rows(4, {n: (q, [0], 0, CO) for n, (q, CO) in plan.items()})
     preds = torch.full((4, Tcap, Ho * Wo), 255, dtype=torch.uint8)
     partial = torch.zeros(4, 64, COcap, 2)
-    lib.seg_postprocess_batch(sb, partial, preds, desc, 4, Tcap, H, W, COcap, Ho, Wo, None)
+    lib.seg_postprocess_batch(sb, partial, preds, desc, 4, Tcap, Tcap, H, W, COcap, Ho, Wo, None)
     want = torch.full_like(preds, 255)
     for n, (q, CO) in plan.items():
         lab = torch.zeros(Ho * Wo, dtype=torch.uint8)
@@ -143,6 +143,11 @@ def test_batched_bf16_postprocessing(backend):
         assert len(set(lab.tolist())) > 1
         want[n, q] = lab
     assert torch.equal(preds, want)
+
+
+def test_batched_bf16_postprocessing_map_positions(backend):
+    """label rows at one position, the map at another (descriptor column 5), against vfs_seg_postprocess"""
+    check_map_positions(backend.hostlib, backend.hostlib.seg_postprocess_batch, backend.hostlib.seg_postprocess)
 
 
 def test_bf16_batch_arguments_and_invalid_rows(emu_backend):

@@ -3,7 +3,7 @@ Which video sits in which slot at which frame, and the descriptor rows the batch
 import numpy as np
 import pytest
 
-from vfs_amd.labelprop import DESC_INTS, _key_frames, batch_schedule
+from vfs_amd.labelprop import DESC_INTS, _key_frames, _ring_rows, batch_schedule, ring_position
 
 # (lengths, nslots, precede, with_first, non_mask_len): nslots >, == and < the number of videos; lengths 2, 3 and > precede + 2
 CASES = [
@@ -44,8 +44,8 @@ def test_batch_schedule(lengths, nslots, precede, with_first, non_mask_len):
                 continue
             v, f = occupant[n], len(frames[occupant[n]]) + 1
             keys = _key_frames(f, precede, with_first)
-            assert tuple(rows[n, :5]) == (1, f, len(keys), non_mask_len, classes[v])
-            assert rows[n, 8:8 + len(keys)].tolist() == keys and not rows[n, 5:8].any() and not rows[n, 8 + len(keys):].any()
+            assert tuple(rows[n, :6]) == (1, f, len(keys), non_mask_len, classes[v], f)      # [5]: the map position is the frame number
+            assert rows[n, 8:8 + len(keys)].tolist() == keys and not rows[n, 6:8].any() and not rows[n, 8 + len(keys):].any()
             frames[v].append((i, n, f))
         vacated = {n for n, _ in retired}
         for n, v in retired:
@@ -57,6 +57,23 @@ def test_batch_schedule(lengths, nslots, precede, with_first, non_mask_len):
         assert [f for _, _, f in frames[v]] == list(range(1, T))
         assert len({n for _, n, _ in frames[v]}) == 1
         assert [i for i, _, _ in frames[v]] == list(range(frames[v][0][0], frames[v][0][0] + T - 1))
+
+
+@pytest.mark.parametrize('lengths,nslots,precede,with_first,non_mask_len', CASES)
+def test_ring_rows_change_the_bank_positions_only(lengths, nslots, precede, with_first, non_mask_len):
+    """columns 1 (query frame) and 8.. (key frames) become ring positions; the map position (5) and everything else stay"""
+    table, _ = batch_schedule(lengths, [2] * len(lengths), nslots, precede, with_first, non_mask_len)
+    before = table.copy()
+    rows = _ring_rows(table, precede)
+    assert np.array_equal(table, before) and rows.dtype == table.dtype and rows.shape == table.shape
+    assert np.array_equal(rows[..., 0], table[..., 0]) and np.array_equal(rows[..., 2:8], table[..., 2:8])
+    active = table[..., 0] == 1
+    assert np.array_equal(rows[..., 5][active], table[..., 1][active]) and not rows[..., 5][~active].any()
+    assert np.array_equal(rows[..., 1], ring_position(table[..., 1], precede))
+    assert np.array_equal(rows[..., 8:], ring_position(table[..., 8:], precede))
+    assert rows[..., 1].max() <= precede + 1 and rows[..., 8:].max() <= precede + 1
+    if max(lengths) > precede + 2:      # a ring wraps: positions and frame numbers differ somewhere
+        assert (rows[..., 1] != rows[..., 5]).any()
 
 
 def test_batch_schedule_of_no_videos():

@@ -7,8 +7,11 @@ batches than forward_test (one frame, a pushed chunk, the active slots of a step
 features do not depend on the batch a frame is extracted in is part of what these tests establish, in both precisions."""
 import numpy as np
 import pytest
+import torch
 
 from tests.test_labelprop_batch import _assert_same, _per_video, _tracker, _videos
+from tests.test_labelprop_batch_bf16 import CountingLib
+from tests.test_labelprop_batch_levels import LEVELS, _level_videos
 from vfs_amd import labelprop
 
 T, SIZE, R = 8, (32, 48), 4
@@ -124,24 +127,77 @@ def test_ring_batch_equals_per_video(backend, precision, soft):
     _assert_same(model.forward_test_batch(imgs_list, refs, metas, batch=2, ring=True), want)
 
 
-@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
-def test_ring_bank_shapes(emu_backend, precision):
-    """the memory condition: a slot's banks hold R positions with ring=True and Tcap, the longest clip, without - R / Tcap of the bytes"""
-    model = _tracker(emu_backend.dev, precision=precision)
+def test_ring_batch_all_blocks_equals_per_video(backend):
+    """the same clips with all_blocks=True: two feature levels, each writing its own maps in place; video 0's thin object gives level 2
+    (whose class counts come from level 1's map) another class count than level 1"""
+    model = _tracker(backend.dev, all_blocks=True)
+    imgs_list, refs, metas = _level_videos(LENGTHS, [SIZE] * 4, False, backend.dev)
+    want = _per_video(model, imgs_list, refs, metas)
+    assert [w.shape[:2] for w in want] == [(LEVELS, T) for T in LENGTHS]
+    _assert_same(model.forward_test_batch(imgs_list, refs, metas, batch=2, ring=True), want)
+
+
+def _groups(backend, precision, channels):
+    """a whole-clip and a ring group of the clips above (two slots); channels: of their soft maps, None: label maps"""
+    model = _tracker(backend.dev, precision=precision)
     lengths = [n for n in LENGTHS if n > 1]
-    imgs_list, refs, metas = _videos(lengths, [SIZE] * 3, False, emu_backend.dev)
+    imgs_list, refs, metas = _videos(lengths, [SIZE] * 3, False, backend.dev)
+    if channels:
+        g = torch.Generator().manual_seed(11)
+        refs = [torch.softmax(2.0 * torch.randn((1, channels) + SIZE, generator=g), dim=1) for _ in lengths]
     cfg = labelprop.labelprop_config(model)
     videos = [v.reshape((-1,) + tuple(v.shape[2:])) for v in imgs_list]
-    groups = {ring: labelprop._Group(model, emu_backend.eng, cfg, videos, refs, SIZE, 2, ring=ring) for ring in (False, True)}
-    Tcap = max(lengths)
-    for ring, frames in ((False, Tcap), (True, R)):
-        (lv,) = groups[ring].levels
-        assert tuple(lv.fb.shape) == (2, frames, 24, 256)
-        assert (lv.hl is not None) == (precision == 'fp32') and (lv.hl is None or tuple(lv.hl.shape) == (2, frames, 24, 512))
-        assert tuple(lv.sb.shape) == (2, frames * 24 * lv.COcap)
-    for name in ('fb', 'hl', 'sb'):
-        a, b = (getattr(groups[ring].levels[0], name) for ring in (True, False))
-        assert a is None and b is None or a.numel() * Tcap == b.numel() * R      # bank bytes per slot: R / Tcap of today's
+    return {ring: labelprop._Group(model, backend.eng, cfg, videos, refs, SIZE, 2, ring=ring) for ring in (False, True)}, max(lengths)
+
+
+def _tensors(obj):
+    return {name: t for name, t in vars(obj).items() if torch.is_tensor(t)}
+
+
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+def test_ring_bank_shapes(emu_backend, precision):
+    """the memory condition: a slot's banks hold R positions with ring=True and Tcap, the longest clip, without - R / Tcap of the bytes;
+    the maps are the same in both modes, one buffer per level, so a ring group never holds more bytes than the whole-clip group - label
+    maps and 16-channel soft maps alike"""
+    for channels in (None, 16):
+        groups, Tcap = _groups(emu_backend, precision, channels)
+        for ring, frames in ((False, Tcap), (True, R)):
+            (lv,) = groups[ring].levels
+            assert tuple(lv.fb.shape) == (2, frames, 24, 256)
+            assert (lv.hl is not None) == (precision == 'fp32') and (lv.hl is None or tuple(lv.hl.shape) == (2, frames, 24, 512))
+            assert tuple(lv.sb.shape) == (2, frames * 24 * lv.COcap) and lv.COcap == (channels or 4)
+            assert tuple(lv.preds.shape) == ((2, Tcap * 16 * SIZE[0] * SIZE[1]) if channels else (2, Tcap, SIZE[0] * SIZE[1]))
+            assert lv.preds.dtype == (torch.float32 if channels else torch.uint8)
+            # no second map buffer: these are all the tensors of a level
+            assert set(_tensors(lv)) - {'hl'} == {'fb', 'sb', 'preds', 'table'} | ({'ingest'} if ring else set())
+        for name in ('fb', 'hl', 'sb'):
+            a, b = (getattr(groups[ring].levels[0], name) for ring in (True, False))
+            assert a is None and b is None or a.numel() * Tcap == b.numel() * R      # bank bytes per slot: R / Tcap of today's
+        nbytes = {ring: sum(t.numel() * t.element_size() for obj in [g] + g.levels for t in _tensors(obj).values()) for ring, g in groups.items()}
+        assert nbytes[True] <= nbytes[False], (channels, nbytes)
+
+
+@pytest.mark.parametrize('precision,channels', [('fp32', None), ('bf16', None), ('fp32', 4)])
+def test_ring_step_issues_the_whole_clip_calls(emu_backend, monkeypatch, precision, channels):
+    """a ring step makes the post-processing library calls of a whole-clip step - one per level, into the maps - and no Tensor.copy_"""
+    groups, _ = _groups(emu_backend, precision, channels)
+    eng, calls, copies = emu_backend.eng, {}, {}
+    lib = eng.lib
+    for ring, group in groups.items():
+        group.admit(0)
+        eng.lib = counted = CountingLib(lib)
+        copied = []
+        with monkeypatch.context() as m:
+            m.setattr(torch.Tensor, 'copy_', lambda *a, _copy=torch.Tensor.copy_, **k: copied.append(1) or _copy(*a, **k))
+            try:
+                group.step(0)
+            finally:
+                eng.lib = lib
+        post = {k: v for k, v in counted.calls.items() if k.startswith(('seg_postprocess', 'bilinear_resize'))}
+        calls[ring], copies[ring] = post, len(copied)
+    name = 'bilinear_resize_f32_batch' if channels else ('seg_postprocess_batch' if precision == 'bf16' else 'seg_postprocess_exact_batch')
+    assert calls[True] == calls[False] == {name: 1}
+    assert copies == {False: 0, True: 0}
 
 
 def test_ring_is_off_by_default(emu_backend):

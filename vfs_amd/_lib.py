@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'vfs_hip.h')
 TUNING_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'vfs_hip_tuning.h')      # vfs_set_option: the A/B switchboard, not part of the operator contract
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libvfs_hip.so')
+ABI_VERSION = 3      # vfs_abi_version() of the library this header and the callers in this package are written for (csrc/capi.hip)
 
 _CT = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float,
        'double': ctypes.c_double, 'vfs_stream_t': ctypes.c_void_p}
@@ -60,6 +61,8 @@ class VfsLib:
             fn.restype = ret
             fn.argtypes = [t for t, _ in args]
             self._fns[name] = fn
+        if self._fns['vfs_abi_version']() != ABI_VERSION:      # a library of another version takes other arguments under the same names
+            raise VfsError(f'{path}: vfs_abi_version() = {self._fns["vfs_abi_version"]()}, this package needs {ABI_VERSION}: rebuild it')
 
     def last_error(self):
         return self._fns['vfs_last_error']().decode()

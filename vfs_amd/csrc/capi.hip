@@ -247,7 +247,7 @@ static int photo_run(const char* who, const PipelineArgs& a, const int* photo, v
 extern "C" {
 
 const char* vfs_last_error(void) { return g_err; }
-int vfs_abi_version(void) { return 2; }      // 2: vfs_sgd_step(skip_flag), vfs_labelprop*(workspace_bytes)
+int vfs_abi_version(void) { return 3; }      // 2: vfs_sgd_step(skip_flag), vfs_labelprop*(workspace_bytes); 3: batched post-processing (Tmaps), desc [5]
 int vfs_set_option(const char* name, int value) {
   for (const auto& o : g_options) {
     if (strcmp(name, o.name)) continue;
@@ -1121,29 +1121,30 @@ int vfs_labelprop_batch(const vfs_bf16* fbank, float* sbank, void* workspace, lo
   return vfs_labelprop_batch_launch(b, stream_of(stream));
 }
 static int seg_post_batch_check(const char* who, const void* sbank, const void* partial, const void* preds, const int* desc, int nslots, int Tcap,
-                                int H, int W, int COcap, int Ho, int Wo) {
-  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
-    return fail(VFS_ERR_SHAPE, who, "H, W, Ho, Wo, Tcap >= 1, 1 <= classes <= 256, 1 <= nslots <= 64");
+                                int Tmaps, int H, int W, int COcap, int Ho, int Wo) {
+  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || COcap < 1 || COcap > LP_MAX_CLASSES || Tcap < 1 || Tmaps < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
+    return fail(VFS_ERR_SHAPE, who, "H, W, Ho, Wo, Tcap, Tmaps >= 1, 1 <= classes <= 256, 1 <= nslots <= 64");
   if ((long long)Ho * Wo > 0x7fffffff - 255 || (long long)H * W * COcap > 0x7fffffff)
     return fail(VFS_ERR_SHAPE, who, "Ho * Wo and H * W * classes must fit an int");
   if (!sbank || !partial || !preds || !desc) return fail(VFS_ERR_ARG, who, "null buffer");
   return VFS_OK;
 }
-int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap,
-                              int Ho, int Wo, vfs_stream_t stream) {
-  if (int rc = seg_post_batch_check("seg_postprocess_batch", sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo)) return rc;
-  return vfs_seg_postprocess_batch_launch(sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+int vfs_seg_postprocess_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H, int W,
+                              int COcap, int Ho, int Wo, vfs_stream_t stream) {
+  if (int rc = seg_post_batch_check("seg_postprocess_batch", sbank, partial, preds, desc, nslots, Tcap, Tmaps, H, W, COcap, Ho, Wo)) return rc;
+  return vfs_seg_postprocess_batch_launch(sbank, partial, preds, desc, nslots, Tcap, Tmaps, H, W, COcap, Ho, Wo, stream_of(stream));
 }
-int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                                    int COcap, int Ho, int Wo, vfs_stream_t stream) {
-  if (int rc = seg_post_batch_check("seg_postprocess_exact_batch", sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo)) return rc;
-  return vfs_seg_postprocess_exact_batch_launch(sbank, partial, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+int vfs_seg_postprocess_exact_batch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                                    int W, int COcap, int Ho, int Wo, vfs_stream_t stream) {
+  if (int rc = seg_post_batch_check("seg_postprocess_exact_batch", sbank, partial, preds, desc, nslots, Tcap, Tmaps, H, W, COcap, Ho, Wo)) return rc;
+  return vfs_seg_postprocess_exact_batch_launch(sbank, partial, preds, desc, nslots, Tcap, Tmaps, H, W, COcap, Ho, Wo, stream_of(stream));
 }
-int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
-                                  int Wo, vfs_stream_t stream) {
-  if (Tcap < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS) return vfs_set_error(VFS_ERR_SHAPE, "bilinear_resize_f32_batch: Tcap >= 1, 1 <= nslots <= 64");
+int vfs_bilinear_resize_f32_batch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H, int W, int COcap,
+                                  int Ho, int Wo, vfs_stream_t stream) {
+  if (Tcap < 1 || Tmaps < 1 || nslots < 1 || nslots > LPB_MAX_SLOTS)
+    return vfs_set_error(VFS_ERR_SHAPE, "bilinear_resize_f32_batch: Tcap, Tmaps >= 1, 1 <= nslots <= 64");
   if (!sbank || !preds || !desc) return vfs_set_error(VFS_ERR_ARG, "bilinear_resize_f32_batch: null buffer");
-  return vfs_bilinear_resize_f32_batch_launch(sbank, preds, desc, nslots, Tcap, H, W, COcap, Ho, Wo, stream_of(stream));
+  return vfs_bilinear_resize_f32_batch_launch(sbank, preds, desc, nslots, Tcap, Tmaps, H, W, COcap, Ho, Wo, stream_of(stream));
 }
 int vfs_bilinear_resize_f32(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,
                             vfs_stream_t stream) {

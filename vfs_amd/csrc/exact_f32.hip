@@ -886,7 +886,7 @@ __global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __re
   seg_argmax_exact_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
 }
 // lock-step batch: slot blockIdx.z post-processes ITS propagated frame (frame qframe of its label rows [frame][H*W][CO_n]) with its own
-// class count into frame qframe of its label maps (seg_post_slot: vfs_lpb.h); the class dimension of the min / max grid is sized for COcap
+// class count into the row's map position of its label maps (seg_post_slot: vfs_lpb.h); the class dimension of the min / max grid is sized for COcap
 __global__ __launch_bounds__(256) void seg_minmax_exact_batch_kernel(SegPostBatchArgs b) {
   const float* seg; float* partial; uint8_t* label; int CO;
   if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;
@@ -897,10 +897,10 @@ __global__ __launch_bounds__(256) void seg_argmax_exact_batch_kernel(SegPostBatc
   if (!seg_post_slot(b, seg, partial, label, CO)) return;
   seg_argmax_exact_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
 }
-int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                                           int COcap, int Ho, int Wo, hipStream_t s) {
+int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                                           int W, int COcap, int Ho, int Wo, hipStream_t s) {
   if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: 1 <= classes <= 256");
-  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, COcap, H, W, Ho, Wo};
+  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
   hipLaunchKernelGGL(seg_minmax_exact_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
   int rc = vfs_check_launch("seg_minmax_exact_batch");
   if (rc) return rc;
@@ -953,25 +953,25 @@ __global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* _
                                                                   long long dsy, long long dsx) {
   bilinear_resize_f32_body(src, dst, C, H, W, Ho, Wo, ssc, ssy, ssx, dsc, dsy, dsx);
 }
-// lock-step batch, soft maps: slot blockIdx.z resizes ITS propagated frame [H*W][CO_n] into frame qframe of its maps [Tcap][CO_n][Ho][Wo]
-// (packed with the slot's own channel count inside a region sized for COcap)
+// lock-step batch, soft maps: slot blockIdx.z resizes ITS propagated frame [H*W][CO_n] into the row's map position of its maps
+// [Tmaps][CO_n][Ho][Wo] (packed with the slot's own channel count inside a region sized for COcap)
 __global__ __launch_bounds__(256) void bilinear_resize_f32_batch_kernel(const float* __restrict__ sbank, float* __restrict__ preds,
-                                                                        const int* __restrict__ desc, int Tcap, int COcap, int H, int W, int Ho,
-                                                                        int Wo) {
+                                                                        const int* __restrict__ desc, int Tcap, int Tmaps, int COcap, int H, int W,
+                                                                        int Ho, int Wo) {
   const int n = blockIdx.z;
-  int qframe, CO;
-  if (!lpb_row_post(desc, n, Tcap, COcap, qframe, CO)) return;
+  int qframe, mpos, CO;
+  if (!lpb_row_post(desc, n, Tcap, Tmaps, COcap, qframe, mpos, CO)) return;
   const size_t HW = (size_t)H * W, HWo = (size_t)Ho * Wo;
   const float* src = sbank + (size_t)n * Tcap * HW * COcap + (size_t)qframe * HW * CO;
-  float* dst = preds + (size_t)n * Tcap * HWo * COcap + (size_t)qframe * HWo * CO;
+  float* dst = preds + (size_t)n * Tmaps * HWo * COcap + (size_t)mpos * HWo * CO;
   bilinear_resize_f32_body(src, dst, CO, H, W, Ho, Wo, 1, (long long)W * CO, CO, (long long)HWo, Wo, 1);
 }
-int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
-                                         int Wo, hipStream_t s) {
+int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H, int W, int COcap,
+                                         int Ho, int Wo, hipStream_t s) {
   if (COcap < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return vfs_set_error(VFS_ERR_SHAPE, "bilinear_resize_f32_batch: geometry");
   const long long total = (long long)COcap * Ho * Wo;
   hipLaunchKernelGGL(bilinear_resize_f32_batch_kernel, dim3((unsigned)((total + 255) / 256), 1, nslots), dim3(256), 0, s, sbank, preds, desc, Tcap,
-                     COcap, H, W, Ho, Wo);
+                     Tmaps, COcap, H, W, Ho, Wo);
   return vfs_check_launch("bilinear_resize_f32_batch");
 }
 int vfs_bilinear_resize_f32_launch(const float* src, float* dst, int C, int H, int W, int Ho, int Wo, int src_nhwc, int dst_nhwc,

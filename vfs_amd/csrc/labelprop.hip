@@ -410,10 +410,10 @@ __global__ __launch_bounds__(256) void seg_argmax_batch_kernel(SegPostBatchArgs 
   if (!seg_post_slot(b, seg, partial, label, CO)) return;
   seg_argmax_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
 }
-int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                                     int COcap, int Ho, int Wo, hipStream_t s) {
+int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                                     int W, int COcap, int Ho, int Wo, hipStream_t s) {
   if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_batch: 1 <= classes <= 256");
-  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, COcap, H, W, Ho, Wo};
+  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
   hipLaunchKernelGGL(seg_minmax_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
   int rc = vfs_check_launch("seg_minmax_batch");
   if (rc) return rc;

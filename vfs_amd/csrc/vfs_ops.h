@@ -500,12 +500,12 @@ int vfs_lp2_splits(int H, int W, int nkeys, int nactive = 1);
 int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
 int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s);
 int vfs_labelprop_batch_launch(const LpBatchArgs& b, hipStream_t s);
-int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                                     int COcap, int Ho, int Wo, hipStream_t s);
-int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int H, int W,
-                                           int COcap, int Ho, int Wo, hipStream_t s);
-int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int H, int W, int COcap, int Ho,
-                                         int Wo, hipStream_t s);
+int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                                     int W, int COcap, int Ho, int Wo, hipStream_t s);
+int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
+                                           int W, int COcap, int Ho, int Wo, hipStream_t s);
+int vfs_bilinear_resize_f32_batch_launch(const float* sbank, float* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H, int W, int COcap,
+                                         int Ho, int Wo, hipStream_t s);
 
 // ---- bank_ingest.hip: the frames of n images enter their positions of a feature bank in one launch (ring banks, streaming) ----
 #define BANK_INGEST_MAX_C 2048      // a row is held in registers between its read and its writes

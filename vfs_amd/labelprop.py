@@ -339,8 +339,9 @@ class _SingleStep:
 # of R = precede_frames + 2 positions therefore serves a clip of any length: position 0 keeps frame 0, frame f >= 1 lives at position
 # 1 + (f - 1) % (precede_frames + 1) - the precede_frames key frames and the query frame never share a position.  The label rows use the
 # same positions, and the kernels, which address their banks through qframe / kslot / descriptor rows, get positions instead of frame
-# numbers: the key lists keep the reference's order and duplicates.  A frame enters its position through the table-driven ingest
-# (csrc/bank_ingest.hip): one launch per feature level for the new frames of every video of a step.
+# numbers: the key lists keep the reference's order and duplicates.  The label maps of a clip are not a ring: a descriptor row names
+# the map position its post-processing writes on its own (column 5), and that stays the frame number.  A frame enters its position
+# through the table-driven ingest (csrc/bank_ingest.hip): one launch per feature level for the new frames of every video of a step.
 def ring_positions(precede):
     """bank positions per video of a ring bank"""
     return precede + 2
@@ -352,7 +353,8 @@ def ring_position(f, precede):
 
 
 def _ring_rows(table, precede):
-    """the descriptor rows of batch_schedule with every frame number - query frame, key frames - replaced by its ring position"""
+    """the descriptor rows of batch_schedule with the frame numbers that address the banks - query frame (column 1), key frames
+    (8..) - replaced by their ring positions; the map position (column 5) stays the frame number"""
     rows = table.copy()
     rows[..., 1] = ring_position(table[..., 1], precede)
     rows[..., 8:] = ring_position(table[..., 8:], precede)
@@ -485,7 +487,8 @@ class LabelPropStream:
 # lengths are known, so the schedule of the whole group - per step and slot: active, query frame, key frames, non_mask_len, class
 # count - is worked out on the host first and uploaded ONCE as the descriptor table the kernels read (include/vfs_hip.h); inside the
 # step loop nothing is read back and nothing but a newly admitted video's frames and first label map goes to the device.
-DESC_INTS = 72      # include/vfs_hip.h VFS_LPB_DESC_INTS
+DESC_INTS = 72      # include/vfs_hip.h VFS_LPB_DESC_INTS: [0] active, [1] query frame (bank position), [2] key frames, [3] non_mask_len,
+                    # [4] classes, [5] map position (the query frame's number), [6..7] 0, [8..] the key frames (bank positions)
 
 
 def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_len):
@@ -510,7 +513,7 @@ def batch_schedule(lengths, class_counts, nslots, precede, with_first, non_mask_
                 continue
             v, f = sl
             keys = _key_frames(f, precede, with_first, non_mask_len)
-            row[n, :5] = (1, f, len(keys), non_mask_len, class_counts[v])
+            row[n, :6] = (1, f, len(keys), non_mask_len, class_counts[v], f)
             row[n, 8:8 + len(keys)] = keys
             most = max(most, len(keys))
             sl[1] += 1
@@ -535,13 +538,15 @@ def _level_maps(ref, shapes, out_size):
 
 
 class _Level:
-    """one feature level of a group: its stacked banks (layout: include/vfs_hip.h), maps and descriptor table on the device"""
+    """one feature level of a group: its stacked banks (layout: include/vfs_hip.h), maps and descriptor table on the device.  `ring`
+    decides the positions per slot of the feature, split and label-row banks (and, in _Group, when frames are extracted) and nothing
+    else: the maps hold every frame of the longest clip either way, and the kernels write them in place"""
 
     def __init__(self, eng, cfg, shape, split, feats, lengths, soft, out_size, B, Tcap, dev, ring=False):
         h, w, C = self.h, self.w, self.C = shape
         out_h, out_w = out_size
         exact = cfg.precision == 'fp32'
-        # frame positions per slot of the banks and of what the kernels write: every frame of the longest clip, or a ring
+        # frame positions per slot of the banks: every frame of the longest clip, or a ring
         Tb = self.Tb = ring_positions(cfg.precede) if ring else Tcap
         self.fb = torch.empty(B, Tb, h * w, C, dtype=F32 if exact else BF16, device=dev)
         self.hl = torch.empty(B, Tb, h * w, 2 * C, dtype=BF16, device=dev) if split else None      # fp32, two-pass kernels only
@@ -549,15 +554,10 @@ class _Level:
         self.cos = [feat[2] for feat in feats]
         COcap = self.COcap = max(self.cos)
         self.sb = torch.empty(B, Tb * h * w * COcap, dtype=F32, device=dev)      # label rows, packed per slot with the slot's class count
-
-        def maps(T):
-            if soft:
-                return torch.empty(B, T * COcap * out_h * out_w, dtype=F32, device=dev)
-            return torch.empty(B, T, out_h * out_w, dtype=torch.uint8, device=dev)
-        self.preds = maps(Tb)
-        # the maps of a whole clip, which retire() hands over: what the kernels write, or (ring: the post-processing kernels address
-        # label rows and maps with ONE position) per-clip buffers that step() copies every finished map into
-        self.out = maps(Tcap) if ring else self.preds
+        if soft:
+            self.preds = torch.empty(B, Tcap * COcap * out_h * out_w, dtype=F32, device=dev)
+        else:
+            self.preds = torch.empty(B, Tcap, out_h * out_w, dtype=torch.uint8, device=dev)
         self.ws_bytes = _workspace_bytes(eng.lib, h, w, split, cfg.entries, B, cfg.precision)
         # the levels share one schedule; only the class-count column of their tables may differ
         self.frames, self.steps = batch_schedule(lengths, self.cos, B, cfg.precede, cfg.with_first, cfg.non_mask_len)
@@ -647,14 +647,14 @@ class _Group:
             ref = self.refs[k]
             for lv in self.levels:      # the next level starts from this level's map at the output size (a soft map: frame 0 of its predictions)
                 CO = lv.cos[k]
-                pred0 = lv.out[n, :CO * out_h * out_w].reshape(CO, out_h, out_w) if self.soft else lv.out[n, 0]
+                pred0 = lv.preds[n, :CO * out_h * out_w].reshape(CO, out_h, out_w) if self.soft else lv.preds[n, 0]
                 ref = _first_frame(self.eng, ref, lv.feats[k], lv.sb[n, :lv.h * lv.w * CO], self.out_size, pred0)
 
     def step(self, i):
         """one launch set per level: every active slot propagates to and post-processes its frame of row i of the schedule"""
         lib, cfg, ws = self.eng.lib, self.cfg, self.ws
         _, _, nactive, most = self.steps[i]
-        B, (out_h, out_w) = self.B, self.out_size
+        B, Tcap, (out_h, out_w) = self.B, self.Tcap, self.out_size
         s = self.eng.stream(ws.device)
         if self.ring:
             self._extract([(k, f) for _, k, f in self.active[i]], (i, 1), nactive)
@@ -669,15 +669,11 @@ class _Group:
                 lib.labelprop_f32_batch(lv.fb, lv.sb, ws, lv.ws_bytes, row, B, nactive, most, Tb, h, w, C, COcap, cfg.radius, cfg.topk,
                                         cfg.temp, s)
             if self.soft:
-                lib.bilinear_resize_f32_batch(lv.sb, lv.preds, row, B, Tb, h, w, COcap, out_h, out_w, s)
+                lib.bilinear_resize_f32_batch(lv.sb, lv.preds, row, B, Tb, Tcap, h, w, COcap, out_h, out_w, s)
             elif cfg.precision == 'bf16':
-                lib.seg_postprocess_batch(lv.sb, self.partial, lv.preds, row, B, Tb, h, w, COcap, out_h, out_w, s)
+                lib.seg_postprocess_batch(lv.sb, self.partial, lv.preds, row, B, Tb, Tcap, h, w, COcap, out_h, out_w, s)
             else:
-                lib.seg_postprocess_exact_batch(lv.sb, self.partial, lv.preds, row, B, Tb, h, w, COcap, out_h, out_w, s)
-            if self.ring:      # the maps of a clip are kept per clip: every slot's new map leaves its ring position
-                for n, k, f in self.active[i]:
-                    pos, per = int(ring_position(f, cfg.precede)), (lv.cos[k] if self.soft else 1) * out_h * out_w
-                    lv.out[n].reshape(-1)[f * per:(f + 1) * per].copy_(lv.preds[n].reshape(-1)[pos * per:(pos + 1) * per])
+                lib.seg_postprocess_exact_batch(lv.sb, self.partial, lv.preds, row, B, Tb, Tcap, h, w, COcap, out_h, out_w, s)
 
     def retire(self, n, k):
         """-> forward_test(...)[0] of video k, which ended in slot n: its maps leave the device now, the slot is refilled at the next step"""
@@ -686,9 +682,9 @@ class _Group:
         for lv in self.levels:
             CO = lv.cos[k]
             if self.soft:
-                arr = lv.out[n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
+                arr = lv.preds[n, :T * CO * out_h * out_w].reshape(T, CO, out_h, out_w)
             else:
-                arr = lv.out[n, :T].reshape(T, out_h, out_w)
+                arr = lv.preds[n, :T].reshape(T, out_h, out_w)
             levels.append(arr.cpu().numpy() if arr.device.type != 'cpu' else arr.numpy().copy())      # (the slot's maps are overwritten by the next video)
         return _levels_result(self.tracker, levels)
 
@@ -699,7 +695,8 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8,
     (above) on the batched kernels of test_cfg.precision ('fp32': vfs_labelprop_f32_2pass_batch / vfs_labelprop_f32_batch, 'bf16':
     vfs_labelprop_batch), with all_blocks=True one launch set per feature level and step.  There is no per-video path inside.
     ring=True: a slot's feature and label-row banks hold precede_frames + 2 positions instead of every frame of the longest clip, and
-    the frames are extracted step by step, one backbone pass for the next frame of every active slot (above: ring banks)."""
+    the frames are extracted step by step, one backbone pass for the next frame of every active slot (above: ring banks); the maps
+    are the whole-clip batch's, written in place."""
     n = len(imgs_list)
     if len(ref_seg_maps) != n or len(img_metas) != n:
         raise ValueError(f'forward_test_batch: {n} videos, {len(ref_seg_maps)} label maps, {len(img_metas)} img_metas')
