@@ -19,7 +19,8 @@
 //           (score desc, candidate id asc), softmax (vexp) and value sum as labelprop_f32_merge_kernel: identical bits, by
 //           construction, whatever pass 1's rounding did.
 //   Anything the lists cannot hold (capacity overflow), a bank that is not unit-norm (test_cfg.with_norm=False) or a channel count
-//   the register-resident query tile does not cover falls back to the dense kernel; the overflow case WITHOUT a host round trip
+//   the register-resident query tile does not cover (C = 2048, ResNet-50 stage 3: 512 VGPRs of query fragments per wave, the
+//   whole register file) falls back to the dense kernel; the overflow case WITHOUT a host round trip
 //   (the dense launches read a device flag and exit at once when it is clear).
 //
 // Pass-1 work shape (what round 3's probes asked for, MEASUREMENTS.md "What bounds the fp32 evaluation kernels"): the 8x8 query
@@ -138,9 +139,9 @@ __device__ __forceinline__ void lp2_seed_body(const A& a) {
   if (q >= HW) return;
   const int qy = q / W, qx = q - qy * W;
   const float* qrow = a.fbank + ((size_t)a.qframe * HW + q) * C;
-  f32x4 qv[4];      // C <= 1024: channels 256 j + 4 lane .. + 3
+  f32x4 qv[4];      // C <= 1024: channels 256 j + 4 lane .. + 3 (C = 64, 128: the first 16 / 32 lanes hold the row, the others zeros)
 #pragma unroll
-  for (int j = 0; j < 4; ++j) qv[j] = 256 * j < C ? lpx_ldf4(qrow + 256 * j + 4 * lane) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < 4; ++j) qv[j] = 256 * j + 4 * lane < C ? lpx_ldf4(qrow + 256 * j + 4 * lane) : (f32x4){0.f, 0.f, 0.f, 0.f};
   float tv[LPX_TOPK];
 #pragma unroll
   for (int i = 0; i < LPX_TOPK; ++i) tv[i] = -INFINITY;
@@ -157,7 +158,7 @@ __device__ __forceinline__ void lp2_seed_body(const A& a) {
       float acc = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (256 * j < C) {
+        if (256 * j + 4 * lane < C) {
           const f32x4 kv = lpx_ldf4(krow + 256 * j + 4 * lane);
           acc = __builtin_fmaf(kv[0], qv[j][0], acc); acc = __builtin_fmaf(kv[1], qv[j][1], acc);
           acc = __builtin_fmaf(kv[2], qv[j][2], acc); acc = __builtin_fmaf(kv[3], qv[j][3], acc);
@@ -659,6 +660,163 @@ __device__ __forceinline__ void lp2_score_body(const A& a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Pass 1 for the NARROW banks, C = 64 and C = 128 (ResNet-18 stages 0 and 1; NG = C / 16 = 4 / 8 groups of 16 channels).
+// lp2_score_body gives every wave a channel QUARTER of at least 64 channels (two stages of its ring): a quarter of 16 or 32
+// channels is no stage.  Here the whole dot product is short enough for ONE wave: wave w owns the 32 x 32 tile (key half w & 1,
+// query half w >> 1) of the 64-key x 64-query block over ALL channels - v_mfma_f32_32x32x16_bf16 again (at C = 64 the four K-steps
+// of the 32 x 32 shape keep the 8 x 8 query tile and the 64-key block, and with them the lists, the epilogue and pass 2, unchanged;
+// the 16 x 16 x 32 shape would halve the K-steps and double the tiles: the same MFMA cycles).  The wave's query half stays in
+// registers (2 NG x 4 VGPRs), a lane reads its key row's fragments straight from the split bank (16 bytes per group and half, a
+// row's 4 C bytes within NG loads of the wave: whole lines through the vector cache), no LDS staging, no cross-wave reduction.
+// Lists, thresholds (seed, running top 10, exchange between the key-frame splits) and the epilogue are lp2_score_body's.
+//
+// Prefilter bound, re-derived for these widths (unit rows q, k; d = 2^-9 the relative error of a round-to-nearest bf16):
+//   representation  x = hi + lo + e with |hi| <= (1 + d)|x|, |lo| <= d|x|, |e| <= d^2|x| element by element, so by Cauchy-Schwarz
+//                   q.k - (hi_q.hi_k + hi_q.lo_k + lo_q.hi_k) = lo_q.lo_k + e_q.k + (hi_q + lo_q).e_k  is at most
+//                   d^2 + d^2 + (1 + 2d) d^2 < 3.02 * 2^-18 in size - independent of C;
+//   accumulation    the matrix unit adds 3 C exact products (bf16 x bf16 fits fp32) of absolute sum <= (1 + d)^2 + 2 d (1 + d)
+//                   < 1.01 into fp32 in an order of its own: allowing a TRUNCATING adder, < 3 C * 2^-23 * 1.01; no partial sums
+//                   of other waves are added here;
+//   reference       the dense kernel's chain rounds C times: <= C * 2^-24 (sum of |q_c k_c| <= 1).
+//   |s~ - s| < 3.02 * 2^-18 + 7.1 C * 2^-24 =: e(C): 3.9e-5 at C = 64, 6.6e-5 at C = 128.  EPS(C) = 3 * 2^-16 + 4 C * 2^-24 of
+//   lp2_margin is 6.1e-5 / 7.6e-5 there: it covers e(C) for every C <= 770 even under the truncating-adder assumption (for wider
+//   banks it rests on the matrix unit rounding to nearest), so the narrow kernels keep margin = 2 EPS(C) + 2^-21, and the seed's
+//   EPS covers the seed dot product's own 10 roundings (4 + the 6 butterfly steps; the wide banks' C / 64 + 6).
+template <int NG, class A>
+__device__ __forceinline__ void lp2_score_narrow_body(const A& a) {
+  __shared__ int sKC[64], sThr[64], sCnt[64], sEn[64];
+  __shared__ float sEq[64][LP2_BLOCK_QUEUE];
+  __shared__ float sTop[LPX_TOPK][64];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int li = lane & 31, kgrp = lane >> 5;
+  const int H = a.H, W = a.W, C = a.C, HW = H * W;
+  const int tiles_x = (W + 7) >> 3;
+  const int lb = blockIdx.x;      // (tile row, key-frame split, tile column) in dispatch order
+  const int trow = lb / (a.nsplit * tiles_x), rem = lb - trow * (a.nsplit * tiles_x);
+  const int split = rem / tiles_x, tcol = rem - split * tiles_x;
+  const int qy0 = trow * 8, qx0 = tcol * 8;
+  const int fpb = (a.nkeys + a.nsplit - 1) / a.nsplit;
+  const int f_begin = split * fpb, f_end = min(a.nkeys, f_begin + fpb);
+  const int kh = wave & 1, qhh = wave >> 1;
+  // the wave's queries: B fragments (16 channels x 32 queries) of every group, hi and lo
+  const int myq = qhh * 32 + li;
+  const int qy = qy0 + (myq >> 3), qx = qx0 + (myq & 7);
+  const bool q_in = qy < H && qx < W;
+  const int qpix = q_in ? qy * W + qx : 0;
+  bf16x8 qh[NG], ql[NG];
+  {
+    const bf16_t* b = a.hl + ((size_t)a.qframe * HW + (size_t)(min(qy, H - 1) * W + min(qx, W - 1))) * 2 * C + kgrp * 8;      // rows past the map: a valid row, masked below
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      qh[g] = *reinterpret_cast<const bf16x8*>(b + g * 32);
+      ql[g] = *reinterpret_cast<const bf16x8*>(b + g * 32 + 16);
+    }
+  }
+  int tq_pix = -1, gseen = lp2_enc(-INFINITY);
+  if (t < 64) {
+    const int y = qy0 + (t >> 3), x = qx0 + (t & 7);
+    if (y < H && x < W) { tq_pix = y * W + x; gseen = a.gthr[tq_pix]; }
+    sThr[t] = gseen; sCnt[t] = 0; sEn[t] = 0;
+#pragma unroll
+    for (int i = 0; i < LPX_TOPK; ++i) sTop[i][t] = -INFINITY;
+  }
+  unsigned long long* mylist = a.lists + ((size_t)split * HW + qpix) * a.cap;
+  const int R = 32 * kh + li;      // the lane's key row of a block
+
+  for (int cf = f_end - 1; cf >= f_begin; --cf) {      // key frames newest first, blocks centre-out (as lp2_score_body)
+    const Lp2Window cw = lp2_window(a, cf, qy0, qx0);
+    const bf16_t* frame = a.hl + (size_t)cw.slot * HW * 2 * C + kgrp * 8;
+    for (int ci = 0; ci < cw.nkb; ++ci) {
+      const int kb = lp2_block_of(ci, cw.nkb);
+      if (t < 64) {
+        const int kk = kb * 64 + t;
+        const int ky = kk / cw.ww;
+        sKC[t] = kk >= cw.nwin ? -1 : (((cw.wy0 + ky) << 16) | (cw.wx0 + kk - ky * cw.ww));
+      }
+      f32x16 tot;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tot[r] = 0.f;
+      {
+        const int kk = min(kb * 64 + R, cw.nwin - 1);      // rows past the window: its last key (their scores are masked)
+        const int ky = kk / cw.ww, kx = kk - ky * cw.ww;
+        const bf16_t* krow = frame + (size_t)((cw.wy0 + ky) * W + cw.wx0 + kx) * 2 * C;
+        bf16x8 kh8[NG], kl8[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          kh8[g] = *reinterpret_cast<const bf16x8*>(krow + g * 32);
+          kl8[g] = *reinterpret_cast<const bf16x8*>(krow + g * 32 + 16);
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          tot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh8[g], qh[g], tot, 0, 0, 0);
+          tot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh8[g], ql[g], tot, 0, 0, 0);
+          tot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl8[g], qh[g], tot, 0, 0, 0);
+        }
+      }
+      __syncthreads();      // sKC of this block, sThr as the previous block left it
+      const float thr_e = (a.dbg & 16) ? -INFINITY : lp2_dec(sThr[myq]) - a.margin;
+      unsigned long long hot = 0;
+#pragma unroll
+      for (int rg = 0; rg < 16; ++rg) hot |= __ballot(q_in && tot[rg] >= thr_e);
+      if (hot != 0) {
+        const int fid = cf * HW;
+        float b1 = -INFINITY, b2 = -INFINITY;      // the lane's best two feed the query's running top 10 (at most eight values per query and block)
+#pragma unroll
+        for (int rg = 0; rg < 16; ++rg) {
+          if (q_in && tot[rg] >= thr_e) {
+            const int pk = sKC[kh * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kgrp];
+            const int cy = pk >> 16, cx = pk & 0xffff;
+            const int dy = cy - qy, dx = cx - qx;
+            if (pk >= 0 && (cw.r <= 0 || dy * dy + dx * dx < cw.r * cw.r)) {
+              const float sc = tot[rg];
+              const int idx = atomicAdd(&sCnt[myq], 1);
+              if (idx < a.cap) mylist[idx] = ((unsigned long long)(unsigned)(fid + cy * W + cx) << 32) | (unsigned long long)__builtin_bit_cast(unsigned, sc);
+              if (sc > b1) { b2 = b1; b1 = sc; }
+              else if (sc > b2) b2 = sc;
+            }
+          }
+        }
+        if (b1 > -INFINITY) {
+          const int e = atomicAdd(&sEn[myq], 1);
+          if (e < LP2_BLOCK_QUEUE) sEq[myq][e] = b1;
+        }
+        if (b2 > -INFINITY) {
+          const int e = atomicAdd(&sEn[myq], 1);
+          if (e < LP2_BLOCK_QUEUE) sEq[myq][e] = b2;
+        }
+      }
+      __syncthreads();      // sKC is rewritten by the next block; the block's listed scores are complete
+      if (t < 64 && tq_pix >= 0) {
+        const int n = min(sEn[t], LP2_BLOCK_QUEUE);
+        if (n > 0) {
+          float tv[LPX_TOPK];
+#pragma unroll
+          for (int i = 0; i < LPX_TOPK; ++i) tv[i] = sTop[i][t];
+          for (int e = 0; e < n; ++e) lp2_insert_val(tv, sEq[t][e]);
+#pragma unroll
+          for (int i = 0; i < LPX_TOPK; ++i) sTop[i][t] = tv[i];
+          sEn[t] = 0;
+        }
+        const int mine = lp2_enc(sTop[LPX_TOPK - 1][t]);
+        const int best = max(mine, gseen);
+        if (mine > gseen) gseen = max(best, atomicMax(&a.gthr[tq_pix], mine));
+        else gseen = max(gseen, __hip_atomic_load(&a.gthr[tq_pix], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        sThr[t] = best;      // (read behind the next block's first barrier)
+      }
+    }
+  }
+  if (t < 64) {
+    const int y = qy0 + (t >> 3), x = qx0 + (t & 7);
+    if (y < H && x < W) {
+      const int n = sCnt[t];
+      a.counts[(size_t)split * HW + y * W + x] = min(n, a.cap);
+      if (n > a.cap) atomicOr(a.flags, 1);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // pass 2: one WAVE per query (no workgroup barrier: the four waves of a workgroup are independent)
 #define LP2_SURV_CAP 512      // survivors of one query the refinement stages in LDS
 __device__ __forceinline__ void lp2_wave_sync() {
@@ -666,7 +824,8 @@ __device__ __forceinline__ void lp2_wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-template <class A>
+// NP = 32-channel pieces a lane group has in flight per row: 8 for C = 256, 512, 1024 (C % 256 == 0), C / 32 for C = 64, 128
+template <int NP, class A>
 __device__ __forceinline__ void lp2_refine_body(const A& a) {
   __shared__ __attribute__((aligned(16))) float sQ[4][1024];      // the query row (C <= 1024)
   __shared__ unsigned long long sSurv[4][LP2_SURV_CAP];      // the query's survivors
@@ -755,12 +914,12 @@ __device__ __forceinline__ void lp2_refine_body(const A& a) {
     const int fr = id / HW, px = id - fr * HW;
     const float* krow = a.fbank + ((size_t)a.kslot[fr] * HW + px) * C + 4 * sub;
     float acc = 0.f;
-    for (int c0 = 0; c0 < C; c0 += 256) {      // 8 pieces of 32 channels in flight per lane (C = 256, 512, 1024: C % 256 == 0)
-      f32x4 kv[8];
+    for (int c0 = 0; c0 < C; c0 += 32 * NP) {      // NP pieces of 32 channels in flight per lane (C % (32 NP) == 0)
+      f32x4 kv[NP];
 #pragma unroll
-      for (int p = 0; p < 8; ++p) kv[p] = lpx_ldf4(krow + c0 + 32 * p);
+      for (int p = 0; p < NP; ++p) kv[p] = lpx_ldf4(krow + c0 + 32 * p);
 #pragma unroll
-      for (int p = 0; p < 8; ++p) {
+      for (int p = 0; p < NP; ++p) {
         const f32x4 qv = *reinterpret_cast<const f32x4*>(&sQ[wave][c0 + 32 * p + 4 * sub]);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
@@ -853,7 +1012,10 @@ __device__ __forceinline__ bool lp2_slot_args(const LpBatchArgs& b, Lp2SlotArgs&
 __global__ __launch_bounds__(256) void lp2_seed_kernel(Lp2Args a) { lp2_seed_body(a); }
 template <int NG>
 __global__ __launch_bounds__(256, 1) void lp2_score_kernel(Lp2Args a) { lp2_score_body<NG>(a); }
-__global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) { lp2_refine_body(a); }
+template <int NG>
+__global__ __launch_bounds__(256) void lp2_score_narrow_kernel(Lp2Args a) { lp2_score_narrow_body<NG>(a); }
+template <int NP>
+__global__ __launch_bounds__(256) void lp2_refine_kernel(Lp2Args a) { lp2_refine_body<NP>(a); }
 
 __global__ __launch_bounds__(256) void lp2_seed_batch_kernel(LpBatchArgs b) {
   Lp2SlotArgs a;
@@ -866,9 +1028,17 @@ __global__ __launch_bounds__(256, 1) void lp2_score_batch_kernel(LpBatchArgs b) 
   if ((int)blockIdx.x >= ((b.H + 7) >> 3) * ((b.W + 7) >> 3) * a.nsplit) return;      // the grid is sized for the slot with the most key frames
   lp2_score_body<NG>(a);
 }
+template <int NG>
+__global__ __launch_bounds__(256) void lp2_score_narrow_batch_kernel(LpBatchArgs b) {
+  Lp2SlotArgs a;
+  if (!lp2_slot_args(b, a)) return;
+  if ((int)blockIdx.x >= ((b.H + 7) >> 3) * ((b.W + 7) >> 3) * a.nsplit) return;      // the grid is sized for the slot with the most key frames
+  lp2_score_narrow_body<NG>(a);
+}
+template <int NP>
 __global__ __launch_bounds__(256) void lp2_refine_batch_kernel(LpBatchArgs b) {
   Lp2SlotArgs a;
-  if (lp2_slot_args(b, a)) lp2_refine_body(a);
+  if (lp2_slot_args(b, a)) lp2_refine_body<NP>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -888,7 +1058,8 @@ int vfs_lp2_wanted_splits(int H, int W, int nactive) {
 }
 int vfs_lp2_splits(int H, int W, int nkeys, int nactive) { return lp2_splits_for(vfs_lp2_wanted_splits(H, W, nactive), nkeys, vfs_option_lp2_fpb); }
 
-bool vfs_lp2_eligible(int C) { return vfs_option_lp2 && (C == 256 || C == 512 || C == 1024); }
+// C = 64, 128: the narrow pass 1 (lp2_score_narrow_body); C = 2048 stays on the dense kernel (the query tile does not fit in registers)
+bool vfs_lp2_eligible(int C) { return vfs_option_lp2 && (C == 64 || C == 128 || C == 256 || C == 512 || C == 1024); }
 
 static float lp2_margin(int C) {
   // |s~ - s| <= EPS for unit rows: 3 * 2^-16 (the dropped lo.lo product and the two representation remainders, Cauchy-Schwarz) +
@@ -897,11 +1068,12 @@ static float lp2_margin(int C) {
   // gap of more than one ulp of the quotient (2^-23 relative): with the extra 2^-21 (|s| <= 1) a pruned candidate's exact score
   // lies more than four ulps below each of its ten betters, so it cannot tie with one of them after the division either
   // (round 4 advisor finding: the proof was stated on s, the order on s / temperature)
+  // C = 64, 128: the bound is re-derived in front of lp2_score_narrow_body; EPS(C) as below covers it
   return 2.0f * (3.0f / 65536.0f + 4.0f * (float)C / 16777216.0f) + 1.0f / 2097152.0f;
 }
 
 int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
-  if (!vfs_lp2_eligible(a.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: C must be 256, 512 or 1024");
+  if (!vfs_lp2_eligible(a.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: C must be 64, 128, 256, 512 or 1024");
   if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: 1 <= nkeys <= 64");
   if (a.topk < 1 || a.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: 1 <= topk <= 10");
   if (a.H >= 32768 || a.W >= 65536 || (long long)a.nkeys * a.H * a.W >= 0x7fffffffLL || (long long)a.H * a.W * a.C * 4 >= 0xFFFFFFF0LL)
@@ -921,18 +1093,22 @@ int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
   a.xcd_order = vfs_option_lp2_xcd >= 0 ? vfs_option_lp2_xcd : (a.C >= 1024 ? 1 : 0);
   a.trim = vfs_option_lp2_trim;
   a.dbg = vfs_option_lp2_dbg;
-  if (a.C == 256) hipLaunchKernelGGL(lp2_score_kernel<4>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
+  if (a.C == 64) hipLaunchKernelGGL(lp2_score_narrow_kernel<4>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
+  else if (a.C == 128) hipLaunchKernelGGL(lp2_score_narrow_kernel<8>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
+  else if (a.C == 256) hipLaunchKernelGGL(lp2_score_kernel<4>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
   else if (a.C == 512) hipLaunchKernelGGL(lp2_score_kernel<8>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(lp2_score_kernel<16>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
   int rc = vfs_check_launch("lp2_score");
   if (rc) return rc;
-  hipLaunchKernelGGL(lp2_refine_kernel, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
+  if (a.C == 64) hipLaunchKernelGGL(lp2_refine_kernel<2>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
+  else if (a.C == 128) hipLaunchKernelGGL(lp2_refine_kernel<4>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(lp2_refine_kernel<8>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
   return vfs_check_launch("lp2_refine");
 }
 
 // every slot of one lock-step: memset of the slots' overflow words, seed, score, refine - the launches of one video
 int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
-  if (!vfs_lp2_eligible(b.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: C must be 256, 512 or 1024");
+  if (!vfs_lp2_eligible(b.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: C must be 64, 128, 256, 512 or 1024");
   if (b.topk < 1 || b.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: 1 <= topk <= 10");
   if (b.H >= 32768 || b.W >= 65536 || (long long)b.max_nkeys * b.H * b.W >= 0x7fffffffLL || (long long)b.H * b.W * b.C * 4 >= 0xFFFFFFF0LL)
     return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: map too large");
@@ -953,11 +1129,16 @@ int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t
   int rc = vfs_check_launch("lp2_seed_batch");
   if (rc) return rc;
   const dim3 grid(tiles * most, 1, b.nslots);
-  if (b.C == 256) hipLaunchKernelGGL(lp2_score_batch_kernel<4>, grid, dim3(256), 0, s, b);
+  if (b.C == 64) hipLaunchKernelGGL(lp2_score_narrow_batch_kernel<4>, grid, dim3(256), 0, s, b);
+  else if (b.C == 128) hipLaunchKernelGGL(lp2_score_narrow_batch_kernel<8>, grid, dim3(256), 0, s, b);
+  else if (b.C == 256) hipLaunchKernelGGL(lp2_score_batch_kernel<4>, grid, dim3(256), 0, s, b);
   else if (b.C == 512) hipLaunchKernelGGL(lp2_score_batch_kernel<8>, grid, dim3(256), 0, s, b);
   else hipLaunchKernelGGL(lp2_score_batch_kernel<16>, grid, dim3(256), 0, s, b);
   rc = vfs_check_launch("lp2_score_batch");
   if (rc) return rc;
-  hipLaunchKernelGGL(lp2_refine_batch_kernel, dim3((HW + 3) / 4, 1, b.nslots), dim3(256), 0, s, b);
+  const dim3 rgrid((HW + 3) / 4, 1, b.nslots);
+  if (b.C == 64) hipLaunchKernelGGL(lp2_refine_batch_kernel<2>, rgrid, dim3(256), 0, s, b);
+  else if (b.C == 128) hipLaunchKernelGGL(lp2_refine_batch_kernel<4>, rgrid, dim3(256), 0, s, b);
+  else hipLaunchKernelGGL(lp2_refine_batch_kernel<8>, rgrid, dim3(256), 0, s, b);
   return vfs_check_launch("lp2_refine_batch");
 }

@@ -7,6 +7,14 @@ evaluated stage (the reference also computes and discards layer4), and the dense
 affinity / boolean mask are never materialised.  forward_test and forward_test_batch hold every frame of a clip; a stream
 (LabelPropStream) and forward_test_batch(..., ring=True) hold the precede_frames + 2 frames the algorithm reads (ring banks, below).
 
+Feature levels: with test_cfg.all_blocks every residual block of the stages in test_cfg.out_indices; otherwise the output of EVERY
+stage listed there (the backbone's own out_indices where the config has none), in stage order, from ONE backbone pass that stops after
+the last listed stage - tools/test.py:130-131 sets the backbone's out_indices from the test-time config, ResNet.forward returns a tuple
+and forward_test propagates once per entry (vanilla_tracker.py:86-93, 199-205).  Every level has its own (h, w, C), workspace and
+kernel; the result is [num_feats, T, H, W] (soft: [num_feats, T, CO, H, W]), a single level [T, ...].  The two-pass exact kernels
+(csrc/labelprop2.hip) cover C = 256 / 512 / 1024 and C = 64 / 128 (test_cfg.lp2_narrow=False: the dense kernel there); C = 2048 (ResNet-50 stage 3) stays on the
+dense fp32 kernel: the two-pass query tile does not fit in registers.
+
 Two precisions (test_cfg.precision, default 'fp32'; env VFS_EVAL_PRECISION overrides the default):
   'fp32'  fp32 storage and bit-defined fp32 arithmetic (csrc/exact_f32.hip, vfs_amd/exact.py) - what the
           reference computes in; label maps equal the C oracle's bit for bit;
@@ -28,7 +36,7 @@ from .engine import BF16, shared_engine
 F32 = torch.float32
 
 
-LabelPropConfig = namedtuple('LabelPropConfig', 'precision radius with_first non_mask_len with_norm all_blocks precede topk temp batch_step entries')
+LabelPropConfig = namedtuple('LabelPropConfig', 'precision radius with_first non_mask_len with_norm all_blocks precede topk temp batch_step entries narrow')
 
 
 def labelprop_config(tracker):
@@ -50,7 +58,8 @@ def labelprop_config(tracker):
         with_first=with_first, non_mask_len=0 if tc.get('with_first_neighbor', True) else 1,      # vanilla_tracker.py:158-159
         with_norm=bool(tc.get('with_norm', True)), all_blocks=bool(tc.get('all_blocks', False)), precede=precede, topk=topk,
         temp=float(tc['temperature']), batch_step=int(tc.get('batch_step', 10)),
-        entries=int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES'))      # list entries per query of the two-pass kernels
+        entries=int(tc['lp2_entries']) if 'lp2_entries' in tc else knobs.integer('VFS_LP2_ENTRIES'),      # list entries per query of the two-pass kernels
+        narrow=two_pass_narrow(tracker))
 
 
 def pil_nearest_resize(label, out_h, out_w):
@@ -96,11 +105,28 @@ def _block_feats(bb, ctx_blocks, stages):
     return sel
 
 
-def two_pass_ok(precision, with_norm, C):
+def feature_stages(tracker):
+    """the backbone stages behind the feature levels, in network order (as ResNet.forward returns them): test_cfg.out_indices, or the
+    backbone's own where the config has none"""
+    return tuple(sorted({int(s) for s in tracker.test_cfg.get('out_indices', tracker.backbone.out_indices)}))
+
+
+LP2_NARROW_DEFAULT = True      # the two-pass kernels for C = 64 / 128 where test_cfg.lp2_narrow names nothing: measured faster than the dense kernel at both widths (MEASUREMENTS.md)
+
+
+def two_pass_narrow(tracker):
+    """test_cfg.lp2_narrow: the levels of 64 and 128 channels (ResNet-18 stages 0 and 1) on the two-pass kernels - same bits"""
+    tc = tracker.test_cfg
+    return bool(tc.get('lp2_narrow', LP2_NARROW_DEFAULT)) if tc is not None else LP2_NARROW_DEFAULT
+
+
+def two_pass_ok(precision, with_norm, C, narrow=None):
     """the two-pass exact label propagation (csrc/labelprop2.hip: bf16 hi/lo prefilter + exact rescoring, same bits as the dense
-    kernel) needs the fp32 path, unit rows and a channel count its register-resident query tile covers; VFS_LP_TWO_PASS=0 keeps
-    the dense kernel (A/B)"""
-    return precision == 'fp32' and with_norm and C in (256, 512, 1024) and knobs.flag('VFS_LP_TWO_PASS')
+    kernel) needs the fp32 path, unit rows and a channel count its register-resident query tile covers: 256, 512, 1024, and with
+    `narrow` (None: LP2_NARROW_DEFAULT) 64 and 128.  C = 2048 (ResNet-50 stage 3) stays on the dense kernel: the query tile does not
+    fit in registers.  VFS_LP_TWO_PASS=0 keeps the dense kernel everywhere (A/B)"""
+    widths = (64, 128, 256, 512, 1024) if (LP2_NARROW_DEFAULT if narrow is None else narrow) else (256, 512, 1024)
+    return precision == 'fp32' and with_norm and C in widths and knobs.flag('VFS_LP_TWO_PASS')
 
 
 def _prepare_backbone(tracker, eng, precision):
@@ -112,12 +138,24 @@ def _prepare_backbone(tracker, eng, precision):
 
 def _backbone_levels(tracker, eng, frames_ncthw, all_blocks, precision):
     """ONE backbone pass over the n frames of imgs [1,3,n,H,W] (after _prepare_backbone) -> [(feature map [n,h,w,C] as the backbone
-    leaves it, h, w, C)], one entry per feature level.  The maps live in the engine's buffers until the next pass."""
+    leaves it, h, w, C)], one entry per feature level: the outputs of the listed stages (feature_stages), or with all_blocks the
+    blocks of those stages.  The maps live in the engine's buffers until the next pass."""
+    bb = tracker.backbone
+    stages = feature_stages(tracker)
+    own = bb.out_indices
+    if not all_blocks and tuple(own) != stages:      # the pass returns the listed stages and stops after the last of them
+        bb.out_indices = stages
+    try:
+        return _backbone_pass(tracker, eng, frames_ncthw, all_blocks, precision, stages)
+    finally:
+        bb.out_indices = own
+
+
+def _backbone_pass(tracker, eng, frames_ncthw, all_blocks, precision, stages):
     bb = tracker.backbone
     dev = frames_ncthw.device
     _, _, n, H, W = frames_ncthw.shape
     s = eng.stream(dev)
-    stages = tuple(tracker.test_cfg.get('out_indices', bb.out_indices))
     chunk = frames_ncthw.contiguous().float()
     if precision == 'fp32':
         from .exact import exact_state
@@ -133,7 +171,7 @@ def _backbone_levels(tracker, eng, frames_ncthw, all_blocks, precision):
         block_feats = [(b['out'], b['dims'][-1][2], b['dims'][-1][3], b['out'].shape[-1]) for b in ctx['blocks']]
     if all_blocks:          # every block output of the listed stages, in network order
         return [block_feats[i] for i in _block_feats(bb, len(block_feats), stages)]
-    return [outs[stages[0]]]
+    return [outs[si] for si in stages]      # the outputs of the listed stages: each its own h x w and channel count
 
 
 def extract_feature_levels(tracker, eng, frames_ncthw, batch_step, all_blocks=False, precision='bf16', with_norm=True, banks=None, split_banks=None):
@@ -155,7 +193,7 @@ def extract_feature_levels(tracker, eng, frames_ncthw, batch_step, all_blocks=Fa
             shapes = [(h, w, C) for (_, h, w, C) in feats]
             if banks is None:
                 banks = [torch.empty(T, h * w, C, dtype=F32 if exact else BF16, device=dev) for (h, w, C) in shapes]
-                split_banks = [torch.empty(T, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(precision, with_norm, C) else None
+                split_banks = [torch.empty(T, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(precision, with_norm, C, two_pass_narrow(tracker)) else None
                                for (h, w, C) in shapes]
             split_banks = split_banks or [None] * len(banks)      # destinations without split copies: the dense kernels
         for bank, hl, (feat, h, w, C) in zip(banks, split_banks, feats):
@@ -393,7 +431,7 @@ class _StreamLevel:
         h, w, C = shape
         exact = cfg.precision == 'fp32'
         self.bank = torch.empty(R, h * w, C, dtype=F32 if exact else BF16, device=dev)
-        self.hl = torch.empty(R, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(cfg.precision, cfg.with_norm, C) else None
+        self.hl = torch.empty(R, h * w, 2 * C, dtype=BF16, device=dev) if two_pass_ok(cfg.precision, cfg.with_norm, C, cfg.narrow) else None
         self.sbank = torch.zeros(R, h * w, CO, dtype=F32, device=dev)
         self.table = (torch.arange(R, dtype=torch.int64) * (h * w))[:, None].repeat(1, 2).to(dev)
         self.step = _SingleStep(eng, cfg, self.bank, self.hl, self.sbank, shape, CO, out_size)
@@ -401,7 +439,7 @@ class _StreamLevel:
 
 class LabelPropStream:
     """VanillaTracker.forward_test for frames that arrive one at a time (tracker.open_stream): `first` holds what forward_test returns
-    for frame 0 and push(frames) what it returns for the pushed frames, bit for bit - [t, ...] per push (with all_blocks [levels, t,
+    for frame 0 and push(frames) what it returns for the pushed frames, bit for bit - [t, ...] per push (with several feature levels [levels, t,
     ...]; `first` with t = 1), so that the rows of `first` and of every push, joined along the frame axis, are forward_test(...)[0] of
     the whole clip.  Always arrays: test_cfg.save_np is forward_test's.  The device buffers are ring banks of `bank_positions` =
     precede_frames + 2 positions per feature level, whatever the number of frames pushed; the packed weights of the bf16 precision are
@@ -582,7 +620,7 @@ class _Group:
             _prepare_backbone(tracker, eng, cfg.precision)
             self.first = None
             shapes = [(h, w, C) for _, h, w, C in _backbone_levels(tracker, eng, videos[0][:, :, :1], cfg.all_blocks, cfg.precision)]
-            splits = [True if two_pass_ok(cfg.precision, cfg.with_norm, C) else None for _, _, C in shapes]
+            splits = [True if two_pass_ok(cfg.precision, cfg.with_norm, C, cfg.narrow) else None for _, _, C in shapes]
         else:         # video 0 is extracted into tensors of its own, which admit() copies into its slot - one device-to-device copy per
             # group, the same launches as extracting into the slot
             self.first = extract_feature_levels(tracker, eng, videos[0], cfg.batch_step, cfg.all_blocks, cfg.precision, cfg.with_norm)
@@ -710,7 +748,7 @@ def forward_test_batch_hip(tracker, imgs_list, ref_seg_maps, img_metas, batch=8,
     cfg = labelprop_config(tracker)
     eng = shared_engine()
     bb = tracker.backbone
-    nlevels = len(_block_feats(bb, 1 << 30, tuple(tracker.test_cfg.get('out_indices', bb.out_indices)))) if cfg.all_blocks else 1
+    nlevels = len(_block_feats(bb, 1 << 30, feature_stages(tracker))) if cfg.all_blocks else len(feature_stages(tracker))
     outs = [None] * n
     groups = {}
     for i, (imgs, ref_seg_map, meta) in enumerate(zip(imgs_list, ref_seg_maps, img_metas)):
