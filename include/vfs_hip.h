@@ -707,10 +707,16 @@ int vfs_crop_resize_flip_norm(const uint8_t* src, const int* boxes, const uint8_
  *       4 hue, 0 none.  0 = ColorJitter not applied to the frame (its shuffled order, torchvision 0.7 get_params)
  *   [1] [2] [3] brightness / contrast / saturation factors as fp32 bits: PIL ImageEnhance = Image.blend(degenerate,
  *       img, factor) with degenerate 0 / the frame's mean PIL luma int(mean + 0.5) when contrast runs / the pixel's luma
- *   [4] hue shift added to PIL's uint8 H, mod 256 (= np.uint8(hue_factor * 255) of torchvision 0.7 adjust_hue)
+ *   [4] bits 0..7: hue shift added to PIL's uint8 H, mod 256 (= np.uint8(hue_factor * 255) of torchvision 0.7 adjust_hue);
+ *       bits 8..15: r, the integer part of the blur's box radius.  Read by the _blur entry points only, which clamp it to
+ *       their max_blur_radius; vfs_crop_resize_flip_photo_norm and its _ragged form ignore bits 8 and up (r = 0)
  *   [5] grey flag: mmcv.rgb2gray = cv2 RGB2GRAY fixed point (R*4899 + G*9617 + B*1868 + 8192) >> 14, to 3 channels
- *   [6] [7] blur ww, fw: PIL GaussianBlur(radius=sigma) box weights for a box radius < 1 (ww = 2^24 / (2*r + 1),
- *       fw = (2^24 - ww) / 2); three horizontal then three vertical passes, edges replicated.  ww = 0: no blur
+ *   [6] [7] blur ww, fw: PIL GaussianBlur(radius=sigma) = an extended box blur of fp32 radius rad, r = int(rad):
+ *       ww = int(2^24 / (2*rad + 1)) in fp32, fw = (2^24 - (2*r + 1) * ww) / 2; one pass along a line of n pixels is
+ *       out[x] = (ww * sum_{|d| <= r} in[clamp(x+d)] + fw * (in[clamp(x-r-1)] + in[clamp(x+r+1)]) + 2^23) >> 24 with
+ *       clamp(i) = min(max(i, 0), n-1), per channel, uint8 after every pass; three horizontal then three vertical passes.
+ *       ww = 0: no blur.  Larger values are clamped: ww to 2^24 / (2*r + 1), fw to (2^24 - (2*r + 1) * ww) / 2
+ *   A row with r = 0 (every row written before the radius existed) means the same to all four entry points.
  * Frames whose row is all zero come out bit-identical to vfs_crop_resize_flip_norm.  workspace: at least
  * vfs_crop_resize_flip_photo_norm_workspace_bytes(B*V*T, Ho, Wo) bytes ([F] luma sums, [F][Ho][Wo] uint8 RGBX frames),
  * workspace_bytes = what the caller allocated: a smaller buffer is REFUSED.  Other arguments as vfs_crop_resize_flip_norm. */
@@ -719,6 +725,15 @@ int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const 
                                     void* workspace, long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V,
                                     int T, int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r, double mean_g,
                                     double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream);
+/* the photometric chain for blurs of box radius 1 and above (sigma_range (0.1, 2.0) of the SimSiam / BYOL recipes reaches
+ * 1.375).  max_blur_radius (0..3, else VFS_ERR_SHAPE) = the largest r a row of this launch may carry; it selects the
+ * second launch's tile (halo 3 * (max_blur_radius + 1) pixels), so a caller that keeps it fixed runs the same launches
+ * whatever radii a batch drew.  0 launches exactly what vfs_crop_resize_flip_photo_norm launches.  Same workspace. */
+int vfs_crop_resize_flip_photo_norm_blur(const uint8_t* src, const int* boxes, const uint8_t* flips, const int* photo,
+                                         void* workspace, long long workspace_bytes, float* imgs, vfs_bf16* x4, int B,
+                                         int V, int T, int Hs, int Ws, int Ho, int Wo, int Wp, double mean_r,
+                                         double mean_g, double mean_b, double std_r, double std_g, double std_b,
+                                         int max_blur_radius, vfs_stream_t stream);
 
 /* the same two chains for a batch whose samples were decoded at different sizes: the reference crops and resizes sample by
  * sample, each at its own img_shape (pipelines/augmentations.py:171-334,487-596), and DecordDecode hands it every Kinetics
@@ -740,6 +755,13 @@ int vfs_crop_resize_flip_photo_norm_ragged(const uint8_t* src, long long src_byt
                                            long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T,
                                            int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b,
                                            double std_r, double std_g, double std_b, vfs_stream_t stream);
+/* vfs_crop_resize_flip_photo_norm_blur for a batch of mixed frame sizes */
+int vfs_crop_resize_flip_photo_norm_blur_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc,
+                                                const int* boxes, const uint8_t* flips, const int* photo, void* workspace,
+                                                long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T,
+                                                int Ho, int Wo, int Wp, double mean_r, double mean_g, double mean_b,
+                                                double std_r, double std_g, double std_b, int max_blur_radius,
+                                                vfs_stream_t stream);
 
 /* ---- SiamFC probe head (projects/siamfc-pytorch/siamfc/heads.py:16-23,51-58 `_fast_xcorr`): response maps
  * out[m][i][j] = scale * sum_{u,v,c} z[m % nz][u][v][c] * x[m][i+u][j+v][c]; z bf16 [nz][Hz][Wz][C], x bf16 [nx][H][W][C] (NHWC),

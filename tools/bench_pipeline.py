@@ -2,8 +2,9 @@
 """Time the fused crop/resize/flip/normalise kernel on the reference's training shapes
 (340x256 decoded frames -> 224x224, 2 frames per sample) and print its HBM roofline fraction.
 
---color: the plain pipeline against the colour pipeline of the object-level configs (ColorJitter p=0.8,
-RandomGrayScale p=0.2, RandomGaussianBlur p=0.5 between Flip and Normalize, decisions sampled), fp32 imgs out.
+--color [--arms plain,color,wide] [--out FILE]: the plain pipeline against the colour pipeline of the object-level configs
+(ColorJitter p=0.8, RandomGrayScale p=0.2, RandomGaussianBlur p=0.5 between Flip and Normalize, decisions sampled) and
+against the same steps with sigma_range=(0.1, 2.0) at max_blur_radius=1 (wide), fp32 imgs out; arms interleaved.
 
 --ragged [--out FILE]: batches of mixed frame sizes.  B samples of 2 frames at the four sizes DecordDecode returns for
 Kinetics-400, repeated, -> 224x224, through ONE ragged call (plain and colour) against what the uniform entry points offer
@@ -30,40 +31,55 @@ COLOR_STEPS = [dict(type='ColorJitter', brightness=0.4, contrast=0.4, saturation
                dict(type='RandomGaussianBlur', p=0.5, same_across_clip=False, same_on_clip=False)]
 
 
-def _time(fn, n=20):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def color(B):
+def color(B, arms=('plain', 'color', 'wide'), out_path=None):
+    """arms: plain; color = the object-level configs' steps (sigma_range (0.1, 0.2)); wide = the same steps with the blur of
+    the SimSiam / BYOL recipes, sigma_range (0.1, 2.0), at max_blur_radius=1.  Same frames, boxes, flips and the same
+    jitter / grey / blur flags for color and wide (one draw of the RNGs each, from the same seed); the arms are interleaved,
+    ROUNDS rounds of 20 calls, `ms` = the median round, with the min / max over the rounds beside it."""
+    from vfs_amd.pipeline import pack_photometric
     dev = torch.device('cuda:0')
     head = [dict(type='RandomResizedCrop', area_range=(0.2, 1.), same_across_clip=False, same_on_clip=False),
             dict(type='Resize', scale=(224, 224), keep_ratio=False),
             dict(type='Flip', flip_ratio=0.5, same_across_clip=False, same_on_clip=False)]
     tail = [dict(type='Normalize', mean=MEAN, std=STD, to_bgr=False), dict(type='FormatShape', input_format='NCTHW')]
+    wide_steps = COLOR_STEPS[:2] + [dict(COLOR_STEPS[2], sigma_range=(0.1, 2.0))]
     plain, colour = GpuTrainPipeline(head + tail, 2, 1), GpuTrainPipeline(head + COLOR_STEPS + tail, 2, 1)
-    np.random.seed(0)
-    random.seed(0)
     frames = torch.randint(0, 256, (B, 2, 256, 340, 3), dtype=torch.uint8, device=dev)
-    draws = [colour.sample(2, (256, 340)) for _ in range(B)]
-    boxes, flips = np.concatenate([d[0] for d in draws]), np.concatenate([d[1] for d in draws])
-    photo = {k: np.concatenate([d[2][k] for d in draws]) for k in draws[0][2]}
-    from vfs_amd.pipeline import pack_photometric
+
+    def decisions(pipe):
+        np.random.seed(0)
+        random.seed(0)
+        draws = [pipe.sample(2, (256, 340)) for _ in range(B)]
+        photo = {k: np.concatenate([d[2][k] for d in draws]) for k in draws[0][2]}
+        return np.concatenate([d[0] for d in draws]), np.concatenate([d[1] for d in draws]), photo
+    boxes, flips, photo = decisions(colour)
     rows = pack_photometric(photo)
-    res = dict(B=B, frames=2 * B, jitter=int(photo['jitter'].sum()), gray=int(photo['gray'].sum()), blur=int(photo['blur'].sum()))
-    for name, fn in [('plain', lambda: plain(frames, boxes=boxes, flips=flips)),
-                     ('color', lambda: colour(frames, boxes=boxes, flips=flips, photo=rows))]:
-        ms = _time(fn)
-        res[name] = dict(ms=round(ms, 4), frames_per_s=round(2 * B / ms * 1e3))
+    res = dict(B=B, frames=2 * B, rounds=ROUNDS, jitter=int(photo['jitter'].sum()), gray=int(photo['gray'].sum()),
+               blur=int(photo['blur'].sum()))
+    fns = dict(plain=lambda: plain(frames, boxes=boxes, flips=flips), color=lambda: colour(frames, boxes=boxes, flips=flips, photo=rows))
+    if 'wide' in arms:
+        wide = GpuTrainPipeline(head + wide_steps + tail, 2, 1, max_blur_radius=1)
+        wboxes, wflips, wphoto = decisions(wide)
+        assert np.array_equal(wboxes, boxes) and np.array_equal(wflips, flips) and np.array_equal(wphoto['blur'], photo['blur'])
+        wrows = pack_photometric(wphoto, max_blur_radius=1)
+        res['wide_radius_1_frames'] = int((((wrows[:, 4] >> 8) & 255) == 1).sum())
+        fns['wide'] = lambda: wide(frames, boxes=boxes, flips=flips, photo=wrows)
+    fns = {k: fns[k] for k in arms}
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(ROUNDS):
+        for k, fn in fns.items():
+            times[k].append(_window(fn, 20))
+    for k, t in times.items():
+        sp = _spread(t)
+        res[k] = dict(ms=sp['median_ms'], min_ms=sp['min_ms'], max_ms=sp['max_ms'], frames_per_s=round(2 * B / sp['median_ms'] * 1e3))
     print(json.dumps(res))
+    if out_path:
+        with open(out_path, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
 
 
 K400 = [(256, 340), (256, 454), (340, 256), (256, 342)]      # (Hs, Ws)
@@ -176,9 +192,14 @@ def main():
     if '--out' in sys.argv:
         out_path = sys.argv[sys.argv.index('--out') + 1]
         args.remove(out_path)
+    arms = ('plain', 'color', 'wide')
+    if '--arms' in sys.argv:
+        text = sys.argv[sys.argv.index('--arms') + 1]
+        args.remove(text)
+        arms = tuple(text.split(','))
     B = int(args[0]) if args else 128
     if '--color' in sys.argv:
-        return color(B)
+        return color(B, arms, out_path)
     if '--ragged' in sys.argv:
         return ragged(int(args[0]) if args else 32, out_path)
     dev = torch.device('cuda:0')

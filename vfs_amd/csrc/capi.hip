@@ -230,9 +230,12 @@ static int pipeline_run(const char* who, const PipelineArgs& a, hipStream_t s) {
   return rc != VFS_OK ? rc : vfs_crop_resize_flip_norm_launch(a, s);
 }
 
-static int photo_run(const char* who, const PipelineArgs& a, const int* photo, void* workspace, long long workspace_bytes, hipStream_t s) {
+// max_blur_radius: 0 for the entry points whose rows carry no radius, 0..3 from the _blur ones
+static int photo_run(const char* who, const PipelineArgs& a, const int* photo, void* workspace, long long workspace_bytes, int max_blur_radius,
+                     hipStream_t s) {
   const int rc = pipeline_check(who, a, photo);
   if (rc != VFS_OK) return rc;
+  if (max_blur_radius < 0 || max_blur_radius > 3) return fail(VFS_ERR_SHAPE, who, "max_blur_radius outside 0..3");
   if (a.B <= 0 || a.V <= 0 || a.T <= 0 || a.Ho <= 0 || a.Wo <= 0) return fail(VFS_ERR_SHAPE, who, "empty batch");
   if (!workspace || workspace_bytes < vfs_photo_workspace_bytes(a.B * a.V * a.T, a.Ho, a.Wo))
     return fail(VFS_ERR_ARG, who, "workspace smaller than vfs_crop_resize_flip_photo_norm_workspace_bytes");
@@ -241,6 +244,7 @@ static int photo_run(const char* who, const PipelineArgs& a, const int* photo, v
   pa.photo = photo;
   pa.sums = (unsigned long long*)workspace;
   pa.pix = (uint32_t*)((char*)workspace + (size_t)a.B * a.V * a.T * 8);
+  pa.max_blur_radius = max_blur_radius;
   return vfs_crop_resize_flip_photo_norm_launch(pa, s);
 }
 
@@ -1239,7 +1243,15 @@ int vfs_crop_resize_flip_photo_norm(const uint8_t* src, const int* boxes, const 
                                     int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r, double std_g,
                                     double std_b, vfs_stream_t stream) {
   const PipelineArgs a = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
-  return photo_run("crop_resize_flip_photo_norm", a, photo, workspace, workspace_bytes, stream_of(stream));
+  return photo_run("crop_resize_flip_photo_norm", a, photo, workspace, workspace_bytes, 0, stream_of(stream));
+}
+
+int vfs_crop_resize_flip_photo_norm_blur(const uint8_t* src, const int* boxes, const uint8_t* flips, const int* photo, void* workspace,
+                                         long long workspace_bytes, float* imgs, vfs_bf16* x4, int B, int V, int T, int Hs, int Ws, int Ho,
+                                         int Wo, int Wp, double mean_r, double mean_g, double mean_b, double std_r, double std_g,
+                                         double std_b, int max_blur_radius, vfs_stream_t stream) {
+  const PipelineArgs a = pipeline_args(src, boxes, flips, imgs, x4, B, V, T, Hs, Ws, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g, std_b);
+  return photo_run("crop_resize_flip_photo_norm_blur", a, photo, workspace, workspace_bytes, max_blur_radius, stream_of(stream));
 }
 
 int vfs_crop_resize_flip_norm_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes, const uint8_t* flips,
@@ -1256,7 +1268,17 @@ int vfs_crop_resize_flip_photo_norm_ragged(const uint8_t* src, long long src_byt
                                            double mean_b, double std_r, double std_g, double std_b, vfs_stream_t stream) {
   const PipelineArgs a = ragged_args(pipeline_args(src, boxes, flips, imgs, x4, B, V, T, 0, 0, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g,
                                                    std_b), srcdesc, src_bytes);
-  return photo_run("crop_resize_flip_photo_norm_ragged", a, photo, workspace, workspace_bytes, stream_of(stream));
+  return photo_run("crop_resize_flip_photo_norm_ragged", a, photo, workspace, workspace_bytes, 0, stream_of(stream));
+}
+
+int vfs_crop_resize_flip_photo_norm_blur_ragged(const uint8_t* src, long long src_bytes, const int* srcdesc, const int* boxes,
+                                                const uint8_t* flips, const int* photo, void* workspace, long long workspace_bytes,
+                                                float* imgs, vfs_bf16* x4, int B, int V, int T, int Ho, int Wo, int Wp, double mean_r,
+                                                double mean_g, double mean_b, double std_r, double std_g, double std_b, int max_blur_radius,
+                                                vfs_stream_t stream) {
+  const PipelineArgs a = ragged_args(pipeline_args(src, boxes, flips, imgs, x4, B, V, T, 0, 0, Ho, Wo, Wp, mean_r, mean_g, mean_b, std_r, std_g,
+                                                   std_b), srcdesc, src_bytes);
+  return photo_run("crop_resize_flip_photo_norm_blur_ragged", a, photo, workspace, workspace_bytes, max_blur_radius, stream_of(stream));
 }
 
 }  // extern "C"

@@ -143,12 +143,24 @@ int vfs_crop_resize_flip_norm_launch(const PipelineArgs& a, hipStream_t s) {
 // RGBX into the workspace, plus the frame's sum of PIL luma when contrast follows (contrast blends towards the mean of
 // the frame AS IT STANDS then); B = one 64x16 tile + 3-pixel halo in LDS: contrast, the remaining jitter ops, grey,
 // the six box-blur passes, normalise, store.  Integer sums: bit-identical whatever the order of the atomics.
+// A launch whose rows may carry a box radius of 1..3 (vfs_crop_resize_flip_photo_norm_blur) runs launch B as
+// photo_finish_wide_kernel: the same tile with a halo of 3 * (r + 1) pixels.
 
 #define PHOTO_TW 64
 #define PHOTO_TH 16
 #define PHOTO_HALO 3
 #define PHOTO_LW (PHOTO_TW + 2 * PHOTO_HALO)
 #define PHOTO_LH (PHOTO_TH + 2 * PHOTO_HALO)
+// photo_finish_wide_kernel<R>: every pass needs its input valid r + 1 pixels further out, six passes, three per axis: a halo of
+// 3 * (R + 1) for the launch-wide bound R; a frame of radius r < R fills and sweeps only its own 3 * (r + 1) of it.
+// LDS per block = 2 buffers * 4 bytes * (64 + 2 halo) * (16 + 2 halo):
+//   R = 1: halo  6, 76 x 28 -> 17,024 bytes     R = 2: halo  9, 82 x 34 -> 22,304 bytes     R = 3: halo 12, 88 x 40 -> 28,160 bytes
+// (the radius-0 kernel: 70 x 22 -> 12,320 bytes); the 160 KiB of a CU hold 9 / 7 / 5 such blocks of 4 waves: LDS does not limit
+// R = 1 (8 blocks fill the CU's 32 wave slots) and leaves 28 / 20 of the 32 waves for R = 2 / 3.
+#define PHOTO_MAX_RADIUS 3
+#define PHOTO_WIDE_HALO(R) (3 * ((R) + 1))
+#define PHOTO_WIDE_LW(R) (PHOTO_TW + 2 * PHOTO_WIDE_HALO(R))
+#define PHOTO_WIDE_LH(R) (PHOTO_TH + 2 * PHOTO_WIDE_HALO(R))
 
 enum { PH_BRIGHT = 1, PH_CONTRAST = 2, PH_SAT = 3, PH_HUE = 4 };
 
@@ -158,9 +170,11 @@ struct PhotoFrame {
   float fac[4];        // blend factors by op code - 1 (brightness, contrast, saturation)
   int hue, gray;
   uint32_t ww, fw;     // box-blur weights, ww == 0: no blur
+  int rad;             // integer box radius, at most the launch's bound
 };
 
-__device__ __forceinline__ PhotoFrame load_photo(const int* p) {
+// max_radius: the largest box radius the launch runs (0 for the entry points that know none: they ignore bits 8.. of word [4])
+__device__ __forceinline__ PhotoFrame load_photo(const int* p, int max_radius) {
   PhotoFrame r;
   const uint32_t code = (uint32_t)p[0];
   r.split = 4;
@@ -172,9 +186,12 @@ __device__ __forceinline__ PhotoFrame load_photo(const int* p) {
   r.fac[0] = __builtin_bit_cast(float, p[1]); r.fac[1] = __builtin_bit_cast(float, p[2]); r.fac[2] = __builtin_bit_cast(float, p[3]); r.fac[3] = 0.f;
   r.hue = p[4] & 255;
   r.gray = p[5] != 0;
-  // host weights are clamped so that x*ww + 2*255*fw + 2^23 stays below 2^32 (ww + 2*fw <= 2^24)
-  r.ww = min((uint32_t)p[6], 1u << 24);
-  r.fw = min((uint32_t)p[7], ((1u << 24) - r.ww) / 2);
+  // host values are clamped so that no row reaches outside the tile (rad <= max_radius) and the window sum
+  // 255 * ((2 rad + 1) ww + 2 fw) + 2^23 stays below 2^32 ((2 rad + 1) ww + 2 fw <= 2^24)
+  r.rad = min((int)(((uint32_t)p[4] >> 8) & 255u), max_radius);
+  const uint32_t taps = 2u * (uint32_t)r.rad + 1u;
+  r.ww = min((uint32_t)p[6], (1u << 24) / taps);
+  r.fw = min((uint32_t)p[7], ((1u << 24) - taps * r.ww) / 2);
   return r;
 }
 
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(256) void photo_resize_kernel(PhotoArgs pa) {
   const int f = blockIdx.y;
   const FrameSrc fs = frame_src<RAGGED>(a, f);
   if (RAGGED && !fs.img) return;     // block-uniform: a bad descriptor row, launch B writes the frame's zeros
-  const PhotoFrame ph = load_photo(pa.photo + 8 * f);
+  const PhotoFrame ph = load_photo(pa.photo + 8 * f, 0);      // the blur words are launch B's
   const long long hw = (long long)a.Ho * a.Wo;
   uint32_t* out = pa.pix + (size_t)f * hw;
   uint32_t lsum = 0;
@@ -313,7 +330,7 @@ __global__ __launch_bounds__(256) void photo_finish_kernel(PhotoArgs pa) {
     }
     return;
   }
-  const PhotoFrame ph = load_photo(pa.photo + 8 * f);
+  const PhotoFrame ph = load_photo(pa.photo + 8 * f, 0);
   const uint32_t* in = pa.pix + (size_t)f * a.Ho * a.Wo;
   int cmean = 0;
   if (ph.split < 4) cmean = (int)((double)pa.sums[f] / ((double)a.Ho * (double)a.Wo) + 0.5);     // ImageStat mean, int(m + 0.5)
@@ -365,6 +382,96 @@ __global__ __launch_bounds__(256) void photo_finish_kernel(PhotoArgs pa) {
   }
 }
 
+// one pass of PIL's extended box blur at integer radius rad on one pixel: s = the line (row: stride 1, column: stride LW) in LDS,
+// g = the pixel's frame coordinate on that axis, n = the frame's extent, g0 = the frame coordinate of s[0].  Neighbours are taken
+// at clamped frame coordinates (ImagingLineBoxBlur8's three edge regimes in one form).  R+B and G are summed in 16-bit lanes:
+// 7 taps of 255 fit 11 bits.
+__device__ __forceinline__ uint32_t box_pass_wide(const uint32_t* s, int stride, int g, int g0, int n, int rad, uint32_t ww, uint32_t fw) {
+  uint32_t rb = 0, gg = 0;
+  for (int d = -rad; d <= rad; ++d) {
+    const uint32_t p = s[(min(max(g + d, 0), n - 1) - g0) * stride];
+    rb += p & 0x00FF00FFu;
+    gg += (p >> 8) & 255u;
+  }
+  const uint32_t lo = s[(max(g - rad - 1, 0) - g0) * stride], hi = s[(min(g + rad + 1, n - 1) - g0) * stride];
+  const uint32_t erb = (lo & 0x00FF00FFu) + (hi & 0x00FF00FFu), eg = ((lo >> 8) & 255u) + ((hi >> 8) & 255u);
+  const uint32_t r = ((rb & 0xFFFFu) * ww + (erb & 0xFFFFu) * fw + (1u << 23)) >> 24;
+  const uint32_t gr = (gg * ww + eg * fw + (1u << 23)) >> 24;
+  const uint32_t b = ((rb >> 16) * ww + (erb >> 16) * fw + (1u << 23)) >> 24;
+  return r | (gr << 8) | (b << 16);
+}
+
+// launch B for rows of box radius up to R (1..3): grid (column tiles, row tiles, frames).  The frame's radius is uniform in the
+// block, so every loop bound and barrier below is.
+template <int R, bool RAGGED>
+__global__ __launch_bounds__(256) void photo_finish_wide_kernel(PhotoArgs pa) {
+  constexpr int LW = PHOTO_WIDE_LW(R), LH = PHOTO_WIDE_LH(R);
+  const PipelineArgs& a = pa.p;
+  const int f = blockIdx.z, x0 = blockIdx.x * PHOTO_TW, y0 = blockIdx.y * PHOTO_TH;
+  if (RAGGED && !frame_src<RAGGED>(a, f).img) {     // block-uniform: a bad descriptor row, launch A wrote nothing for the frame
+    const float zero[3] = {0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+      const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+      if (x < a.Wo && y < a.Ho) store_pixel(a, f, x, y, zero);
+    }
+    return;
+  }
+  const PhotoFrame ph = load_photo(pa.photo + 8 * f, R);
+  const uint32_t* in = pa.pix + (size_t)f * a.Ho * a.Wo;
+  int cmean = 0;
+  if (ph.split < 4) cmean = (int)((double)pa.sums[f] / ((double)a.Ho * (double)a.Wo) + 0.5);     // ImageStat mean, int(m + 0.5)
+  if (ph.ww == 0) {     // no blur: pixel by pixel
+    for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+      const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+      if (x < a.Wo && y < a.Ho) store_normalized(a, f, x, y, photo_post(in[(size_t)y * a.Wo + x], ph, cmean));
+    }
+    return;
+  }
+  __shared__ uint32_t buf[2][LH * LW];
+  const int step = ph.rad + 1, halo = 3 * step;      // <= PHOTO_WIDE_HALO(R): load_photo clamped rad to R
+  const int lw = PHOTO_TW + 2 * halo, lh = PHOTO_TH + 2 * halo;      // the part of the LW x LH tile this frame uses
+  const int gx0 = x0 - halo, gy0 = y0 - halo;
+  for (int i = threadIdx.x; i < lh * lw; i += 256) {
+    const int lx = i % lw, ly = i / lw;
+    const int gx = gx0 + lx, gy = gy0 + ly;
+    if (gx >= 0 && gx < a.Wo && gy >= 0 && gy < a.Ho) buf[0][ly * LW + lx] = photo_post(in[(size_t)gy * a.Wo + gx], ph, cmean);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int k = 1; k <= 3; ++k) {       // pass k is valid on local columns [k step, lw - k step): pass k-1 was valid step further out
+    const int w = lw - 2 * k * step;
+    for (int i = threadIdx.x; i < lh * w; i += 256) {
+      const int lx = k * step + i % w, ly = i / w;
+      const int gx = gx0 + lx, gy = gy0 + ly;
+      if (gx < 0 || gx >= a.Wo || gy < 0 || gy >= a.Ho) continue;
+      buf[cur ^ 1][ly * LW + lx] = box_pass_wide(buf[cur] + ly * LW, 1, gx, gx0, a.Wo, ph.rad, ph.ww, ph.fw);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  for (int k = 1; k <= 3; ++k) {       // rows [k step, lh - k step) of the columns [halo, halo + TW) the tile keeps
+    const int h = lh - 2 * k * step;
+    for (int i = threadIdx.x; i < h * PHOTO_TW; i += 256) {
+      const int lx = halo + i % PHOTO_TW, ly = k * step + i / PHOTO_TW;
+      const int gx = gx0 + lx, gy = gy0 + ly;
+      if (gx >= a.Wo || gy < 0 || gy >= a.Ho) continue;
+      buf[cur ^ 1][ly * LW + lx] = box_pass_wide(buf[cur] + lx, LW, gy, gy0, a.Ho, ph.rad, ph.ww, ph.fw);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  for (int i = threadIdx.x; i < PHOTO_TW * PHOTO_TH; i += 256) {
+    const int x = x0 + i % PHOTO_TW, y = y0 + i / PHOTO_TW;
+    if (x < a.Wo && y < a.Ho) store_normalized(a, f, x, y, buf[cur][(i / PHOTO_TW + halo) * LW + i % PHOTO_TW + halo]);
+  }
+}
+
+template <int R>
+static void photo_finish_wide_launch(const PhotoArgs& pa, dim3 grid, hipStream_t s) {
+  if (pa.p.ragged) hipLaunchKernelGGL((photo_finish_wide_kernel<R, true>), grid, dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL((photo_finish_wide_kernel<R, false>), grid, dim3(256), 0, s, pa);
+}
+
 long long vfs_photo_workspace_bytes(int F, int Ho, int Wo) {
   return (long long)F * 8 + (long long)F * Ho * Wo * 4;
 }
@@ -374,6 +481,7 @@ int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& pa, hipStream_t s) {
   if (a.B <= 0 || a.V <= 0 || a.T <= 0 || a.Ho <= 0 || a.Wo <= 0) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: empty batch");
   const long long F = (long long)a.B * a.V * a.T;
   if (F > 65535) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: at most 65535 frames per launch");
+  if (pa.max_blur_radius < 0 || pa.max_blur_radius > PHOTO_MAX_RADIUS) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: max_blur_radius outside 0..3");
   if (hipMemsetAsync(pa.sums, 0, (size_t)F * 8, s) != hipSuccess) return vfs_set_error(VFS_ERR_LAUNCH, "photo pipeline: memset");
   const long long hw = (long long)a.Ho * a.Wo;
   long long bx = (hw + 255) / 256;
@@ -384,7 +492,11 @@ int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& pa, hipStream_t s) {
   if (rc != VFS_OK) return rc;
   const int tx = (a.Wo + PHOTO_TW - 1) / PHOTO_TW, ty = (a.Ho + PHOTO_TH - 1) / PHOTO_TH;
   if (ty > 65535) return vfs_set_error(VFS_ERR_SHAPE, "photo pipeline: output too tall");
-  if (a.ragged) hipLaunchKernelGGL(photo_finish_kernel<true>, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
-  else hipLaunchKernelGGL(photo_finish_kernel<false>, dim3(tx, ty, (int)F), dim3(256), 0, s, pa);
+  const dim3 grid(tx, ty, (int)F);
+  if (pa.max_blur_radius == 1) photo_finish_wide_launch<1>(pa, grid, s);
+  else if (pa.max_blur_radius == 2) photo_finish_wide_launch<2>(pa, grid, s);
+  else if (pa.max_blur_radius == 3) photo_finish_wide_launch<3>(pa, grid, s);
+  else if (a.ragged) hipLaunchKernelGGL(photo_finish_kernel<true>, grid, dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL(photo_finish_kernel<false>, grid, dim3(256), 0, s, pa);
   return vfs_check_launch("photo_finish");
 }

@@ -581,6 +581,7 @@ struct PhotoArgs {
   const int* photo;      // [F][8] photometric parameters (vfs_hip.h vfs_crop_resize_flip_photo_norm)
   unsigned long long* sums;   // workspace: [F] luma sums of the frames whose contrast follows launch A's ops
   uint32_t* pix;         // workspace: [F][Ho][Wo] uint8 RGB(X) after launch A
+  int max_blur_radius;   // 0: rows carry box radii below 1 (bits 8.. of word [4] ignored); 1..3: the largest integer box radius a row may carry
 };
 long long vfs_photo_workspace_bytes(int F, int Ho, int Wo);
 int vfs_crop_resize_flip_photo_norm_launch(const PhotoArgs& a, hipStream_t s);

@@ -7,7 +7,8 @@ are already on the device, by ONE kernel (`vfs_crop_resize_flip_norm`, csrc/pipe
 The object-level configs (r18_sgd_cos_100e_r2_1xNx8_k400.py, r50_sgd_cos_100e_r5_1xNx2_k400.py) add ColorJitter,
 RandomGrayScale and RandomGaussianBlur between Flip and Normalize (augmentations.py:1224-1320); with any of
 them present the chain runs as two launches (`vfs_crop_resize_flip_photo_norm`) that apply them to the uint8
-resized frame, where the reference's PIL / cv2 calls act.
+resized frame, where the reference's PIL / cv2 calls act.  A blur whose box radius reaches 1 (sigma above ~0.9) needs a
+wider tile in the second launch: `GpuTrainPipeline(..., max_blur_radius=R)` and `vfs_crop_resize_flip_photo_norm_blur`.
 
 DecordDecode returns every video at its own size (Kinetics-400: 340x256, 454x256, 256x340, ...) and the reference crops
 and resizes sample by sample; a batch of such samples is packed into one byte buffer (`pack_frames`) and goes through
@@ -102,25 +103,47 @@ def _jitter_params(ranges):
     return factors, ops
 
 
-def blur_weights(sigma):
-    """PIL GaussianBlur(radius=sigma): _gaussian_blur_radius (3 passes, fp32 as Pillow computes it) -> the box weights
-    (ww, fw) of ImagingHorizontalBoxBlur.  The kernel runs box radii below 1 only (sigma_range (0.1, 0.2) gives ~0.1)."""
+MAX_BLUR_RADIUS = 3      # the largest max_blur_radius the _blur entry points take (csrc/pipeline.hip PHOTO_MAX_RADIUS)
+
+
+def _box_radius(sigma):
+    """PIL GaussianBlur(radius=sigma): _gaussian_blur_radius (3 passes, fp32 as Pillow computes it)"""
     f32 = np.float32
     s2 = f32(f32(f32(sigma) * f32(sigma)) / f32(3))
     L = f32(math.sqrt(12.0 * float(s2) + 1.0))
     l = f32(math.floor((float(L) - 1.0) / 2.0))
     a = f32(f32(f32(2) * l + f32(1)) * f32(f32(l * f32(l + f32(1))) - f32(f32(3) * s2)))
     a = f32(a / f32(f32(6) * f32(s2 - f32(f32(l + f32(1)) * f32(l + f32(1))))))
-    rad = f32(l + a)
-    if not 0 <= rad < 1:
-        raise NotImplementedError(f'RandomGaussianBlur: sigma {sigma} gives a box radius of {float(rad)} (only < 1 runs on the GPU)')
+    return f32(l + a)
+
+
+def blur_weights_wide(sigma):
+    """PIL GaussianBlur(radius=sigma) at any box radius -> (r, ww, fw) of ImagingLineBoxBlur8: r the integer part of the
+    fp32 box radius, ww the weight of the 2r + 1 inner taps, fw of the two outer ones (row words [4] bits 8..15, [6], [7])"""
+    f32 = np.float32
+    rad = _box_radius(sigma)
+    if not rad >= 0:
+        raise ValueError(f'RandomGaussianBlur: sigma {sigma} gives a box radius of {float(rad)}')
+    r = int(rad)
     ww = int(f32(f32(1 << 24) / f32(rad * f32(2) + f32(1))))
-    return ww, ((1 << 24) - ww) // 2
+    return r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2
 
 
-def pack_photometric(photo):
+def blur_weights(sigma):
+    """the box weights (ww, fw) of a box radius below 1 (sigma_range (0.1, 0.2) gives ~0.1), all that runs without
+    max_blur_radius; blur_weights_wide takes any radius"""
+    rad = _box_radius(sigma)
+    if not 0 <= rad < 1:
+        hint = f'; GpuTrainPipeline(..., max_blur_radius={int(rad)}) admits it' if 1 <= rad < MAX_BLUR_RADIUS + 1 else ''
+        raise NotImplementedError(f'RandomGaussianBlur: sigma {sigma} gives a box radius of {float(rad)} '
+                                  f'(only < 1 runs on the GPU by default{hint})')
+    return blur_weights_wide(sigma)[1:]
+
+
+def pack_photometric(photo, max_blur_radius=0):
     """per-frame photometric decisions (GpuTrainPipeline.sample) -> int32 [F][8] parameter rows of
-    vfs_crop_resize_flip_photo_norm (layout in include/vfs_hip.h)"""
+    vfs_crop_resize_flip_photo_norm (layout in include/vfs_hip.h).  max_blur_radius: the largest integer box radius a row
+    may carry (0: blurs of box radius >= 1 are refused, as blur_weights does)"""
     F = len(photo['jitter'])
     rows = np.zeros((F, 8), np.int32)
     for i in range(F):
@@ -133,7 +156,14 @@ def pack_photometric(photo):
                 rows[i, 4] = int(math.trunc(photo['factors'][i][3] * 255)) % 256    # np.uint8(h * 255) of numpy 1.x: wraps
         rows[i, 5] = int(photo['gray'][i])
         if photo['blur'][i]:
-            rows[i, 6], rows[i, 7] = blur_weights(float(photo['sigma'][i]))
+            sigma = float(photo['sigma'][i])
+            if max_blur_radius == 0:
+                rows[i, 6], rows[i, 7] = blur_weights(sigma)
+            else:
+                r, rows[i, 6], rows[i, 7] = blur_weights_wide(sigma)
+                if r > max_blur_radius:
+                    raise NotImplementedError(f'frame {i}: sigma {sigma} gives a box radius of {r}, above max_blur_radius={max_blur_radius}')
+                rows[i, 4] |= r << 8
     return rows
 
 
@@ -191,9 +221,18 @@ class GpuTrainPipeline:
     [B][num_clips*clip_len][Hs][Ws][3] on the GPU returns dict(imgs=fp32 [B][num_clips][3][clip_len][H][W])
     (and x4, the bf16 NHWC4 frames, when asked).  A batch of samples decoded at different sizes (DecordDecode on
     Kinetics: 340x256, 454x256, 256x340, ...) goes in as a list of per-sample [num_clips*clip_len][Hs_i][Ws_i][3]
-    arrays / tensors or as a PackedFrames, through the same number of launches (`vfs_crop_resize_flip_norm_ragged`)."""
+    arrays / tensors or as a PackedFrames, through the same number of launches (`vfs_crop_resize_flip_norm_ragged`).
 
-    def __init__(self, pipeline_cfg, num_clips=None, clip_len=None):
+    max_blur_radius (0..3): the largest integer box radius a RandomGaussianBlur of this pipeline may reach.  With the
+    default 0 only sigma ranges whose box radius stays below 1 are taken (the reference's default (0.1, 0.2)); with R >= 1
+    a sigma_range whose ends give int(radius) <= R is admitted ((0.1, 2.0) of the SimSiam / BYOL recipes needs 1) and every
+    call runs `vfs_crop_resize_flip_photo_norm_blur` with that R: the bound belongs to the pipeline, so its launches do
+    not depend on the sigmas a batch drew."""
+
+    def __init__(self, pipeline_cfg, num_clips=None, clip_len=None, max_blur_radius=0):
+        if not (isinstance(max_blur_radius, int) and 0 <= max_blur_radius <= MAX_BLUR_RADIUS):
+            raise ValueError(f'max_blur_radius {max_blur_radius!r}: an integer in 0..{MAX_BLUR_RADIUS}')
+        self.max_blur_radius = max_blur_radius
         if num_clips is None or clip_len is None:
             num_clips, clip_len = clips_from_pipeline(pipeline_cfg)
         self.num_clips, self.clip_len = int(num_clips), int(clip_len)
@@ -245,8 +284,12 @@ class GpuTrainPipeline:
                                  same_across_clip=step.get('same_across_clip', True))
             elif t == 'RandomGaussianBlur':   # augmentations.py:1224-1255
                 sr = tuple(float(v) for v in step.get('sigma_range', (0.1, 0.2)))
-                for sg in sr:
-                    blur_weights(sg)      # NotImplementedError for a box radius >= 1
+                for sg in sr:      # the box radius grows with sigma: the ends bound every draw
+                    if max_blur_radius == 0:
+                        blur_weights(sg)      # NotImplementedError for a box radius >= 1
+                    elif blur_weights_wide(sg)[0] > max_blur_radius:
+                        raise NotImplementedError(f'RandomGaussianBlur: sigma {sg} gives a box radius of {blur_weights_wide(sg)[0]}, '
+                                                  f'above max_blur_radius={max_blur_radius} (at most {MAX_BLUR_RADIUS} runs on the GPU)')
                 self.blur = dict(sigma_range=sr, p=float(step.get('p', 0.5)), same_on_clip=step.get('same_on_clip', True),
                                  same_across_clip=step.get('same_across_clip', True))
         if self.out_hw is None or self.mean is None:
@@ -400,15 +443,24 @@ class GpuTrainPipeline:
             if photo is None:
                 rows = np.zeros((B * F, 8), np.int32)
             elif isinstance(photo, dict):
-                rows = pack_photometric(photo)
+                rows = pack_photometric(photo, self.max_blur_radius)
                 out['photo'] = photo
             else:
                 rows = np.ascontiguousarray(photo, dtype=np.int32)
             assert rows.shape == (B * F, 8), rows.shape
+            R = self.max_blur_radius
+            if R:      # the kernel clamps a radius above the bound; the host names the frame
+                over = np.flatnonzero(((rows[:, 4] >> 8) & 255) > R)
+                if over.size:
+                    raise ValueError(f'frame {int(over[0])}: photo row carries a box radius of {int((rows[over[0], 4] >> 8) & 255)}, '
+                                     f'above max_blur_radius={R}')
             out['photo_rows'] = rows
             pt = torch.as_tensor(rows).to(dev)
             ws = self._workspace(B * F, H, W, dev)
-            getattr(get_lib(), 'crop_resize_flip_photo_norm' + entry)(*src, bt, ft, pt, ws, ws.numel(), *tail)
+            if R:
+                getattr(get_lib(), 'crop_resize_flip_photo_norm_blur' + entry)(*src, bt, ft, pt, ws, ws.numel(), *tail[:-1], R, stream)
+            else:
+                getattr(get_lib(), 'crop_resize_flip_photo_norm' + entry)(*src, bt, ft, pt, ws, ws.numel(), *tail)
         else:
             getattr(get_lib(), 'crop_resize_flip_norm' + entry)(*src, bt, ft, *tail)
         if want_imgs:
