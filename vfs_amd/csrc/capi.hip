@@ -27,11 +27,12 @@ int vfs_check_launch(const char* what) {
 
 static hipStream_t stream_of(vfs_stream_t s) { return (hipStream_t)s; }
 // "<who>: <what>" as the error text: checks shared by several entry points name the one that was called
-static int fail(int code, const char* who, const char* what) {
+int vfs_fail(int code, const char* who, const char* what) {      // (vfs_common.h: the launchers' shared checks use it too)
   char buf[256];
   snprintf(buf, sizeof(buf), "%s: %s", who, what);
   return vfs_set_error(code, buf);
 }
+static int fail(int code, const char* who, const char* what) { return vfs_fail(code, who, what); }
 
 // the A/B knobs (vfs_options.h): their definitions and the name table of vfs_set_option
 #define VFS_OPTION_DEFINE(name, dflt) int vfs_option_##name = dflt;

@@ -7,7 +7,7 @@
 //   nn.MaxPool2d(3,2,1), resnet.py:435                                                           -> maxpool_f32_kernel
 //   F.normalize(dim=1), local_attention.py:277-279                                               -> l2norm_rows_f32_kernel
 //   masked_attention_efficient + spatial_neighbor('circle'), local_attention.py:237-348          -> labelprop_f32_kernel (+merge)
-//   F.interpolate(bilinear) / min-max / argmax, vanilla_tracker.py:162-181                       -> seg_*_exact_kernel
+//   F.interpolate(bilinear) / min-max / argmax, vanilla_tracker.py:162-181                       -> seg_*_exact_kernel (text: vfs_segpost.h)
 //
 // Arithmetic contract (identical in the oracle):
 //   * every dot product is ONE ascending fp32 chain acc = fma(a_k, b_k, acc) from +0: that is what
@@ -757,22 +757,25 @@ static void lpx_targets(int C, int nactive, int* target, int* wgs) {
   }
 }
 
+// the checks of both launchers below; who: the entry point in the error text, nkeys: the most key frames a video of the launch has
+static int lpx_check(const char* who, int C, int nkeys, int topk, int H, int W, float temperature) {
+  if (C % 4) return vfs_fail(VFS_ERR_SHAPE, who, "C % 4");
+  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= nkeys <= 64");
+  if (topk < 1 || topk > LPX_TOPK) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= topk <= 10");
+  if (H >= 32768 || W >= 65536 || (long long)nkeys * H * W >= 0x7fffffffLL)
+    return vfs_fail(VFS_ERR_SHAPE, who, "map too large for the packed candidate ids");
+  if (!(temperature > 0.f)) return vfs_fail(VFS_ERR_ARG, who, "temperature > 0");
+  return VFS_OK;
+}
+
 int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
-  if (a.C % 4) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: C % 4");
-  if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: 1 <= nkeys <= 64");
-  if (a.topk < 1 || a.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: 1 <= topk <= 10");
-  if (a.H >= 32768 || a.W >= 65536 || (long long)a.nkeys * a.H * a.W >= 0x7fffffffLL)
-    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32: map too large for the packed candidate ids");
-  if (!(a.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: temperature > 0");
+  if (int rc = lpx_check("labelprop_f32", a.C, a.nkeys, a.topk, a.H, a.W, a.temperature)) return rc;
   if (a.pval == nullptr || a.pidx == nullptr) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32: partial workspace missing");
   const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
   int target, wgs, nsub;
   lpx_targets(a.C, 1, &target, &wgs);
   const int nsplit = lpx_splits_for(a.nkeys, tiles, target, wgs, vfs_option_lpx_minb, a.H, a.W, a.radius, &nsub);
-  if (a.C % 32)
-    hipLaunchKernelGGL(labelprop_f32_kernel<true>, dim3(tiles, nsplit), dim3(256), 0, s, a, nsub);
-  else
-    hipLaunchKernelGGL(labelprop_f32_kernel<false>, dim3(tiles, nsplit), dim3(256), 0, s, a, nsub);
+  hipLaunchKernelGGL(a.C % 32 ? labelprop_f32_kernel<true> : labelprop_f32_kernel<false>, dim3(tiles, nsplit), dim3(256), 0, s, a, nsub);
   int rc = vfs_check_launch("labelprop_f32");
   if (rc) return rc;
   hipLaunchKernelGGL(labelprop_f32_merge_kernel, dim3((a.H * a.W + 255) / 256), dim3(256), 0, s, a, nsplit);
@@ -781,21 +784,13 @@ int vfs_labelprop_f32_launch(const LabelPropF32Args& a, hipStream_t s) {
 
 // every slot of one lock-step: the two launches of one video.  b.flags given: the fallback of the two-pass path, per slot
 int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
-  if (b.C % 4) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: C % 4");
-  if (b.topk < 1 || b.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: 1 <= topk <= 10");
-  if (b.H >= 32768 || b.W >= 65536 || (long long)b.max_nkeys * b.H * b.W >= 0x7fffffffLL)
-    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_batch: map too large for the packed candidate ids");
-  if (!(b.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_batch: temperature > 0");
+  if (int rc = lpx_check("labelprop_f32_batch", b.C, b.max_nkeys, b.topk, b.H, b.W, b.temperature)) return rc;
   const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8);
   lpx_targets(b.C, nactive, &b.target, &b.wgs);
   b.minb = vfs_option_lpx_minb;
   int most = 1, nsub;
   for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lpx_splits_for(nk, tiles, b.target, b.wgs, b.minb, b.H, b.W, b.radius, &nsub));
-  const dim3 grid(tiles, most, b.nslots);
-  if (b.C % 32)
-    hipLaunchKernelGGL(labelprop_f32_batch_kernel<true>, grid, dim3(256), 0, s, b);
-  else
-    hipLaunchKernelGGL(labelprop_f32_batch_kernel<false>, grid, dim3(256), 0, s, b);
+  hipLaunchKernelGGL(b.C % 32 ? labelprop_f32_batch_kernel<true> : labelprop_f32_batch_kernel<false>, dim3(tiles, most, b.nslots), dim3(256), 0, s, b);
   int rc = vfs_check_launch("labelprop_f32_batch");
   if (rc) return rc;
   hipLaunchKernelGGL(labelprop_f32_merge_batch_kernel, dim3((b.H * b.W + 255) / 256, 1, b.nslots), dim3(256), 0, s, b);
@@ -803,124 +798,34 @@ int vfs_labelprop_f32_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// post-processing (vanilla_tracker.py:162-181), every step a single fp32 operation (oracle: xo_bilerp / xo_seg_postprocess)
-__device__ __forceinline__ float bilerp_exact(const float* __restrict__ seg, int H, int W, int CO, int c, int oy, int ox, float sy,
-                                              float sx) {
-  float fy = sy * ((float)oy + 0.5f) - 0.5f, fx = sx * ((float)ox + 0.5f) - 0.5f;
-  fy = fy < 0.f ? 0.f : fy; fx = fx < 0.f ? 0.f : fx;
-  const int y0 = (int)fy, x0 = (int)fx;
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const float v00 = seg[((size_t)y0 * W + x0) * CO + c], v01 = seg[((size_t)y0 * W + x1) * CO + c];
-  const float v10 = seg[((size_t)y1 * W + x0) * CO + c], v11 = seg[((size_t)y1 * W + x1) * CO + c];
-  const float top = hx * v00 + lx * v01, bot = hx * v10 + lx * v11;
-  return hy * top + ly * bot;
-}
-
-// grid (LP_POST_BLOCKS, CO): one class per workgroup (round 6: the 64 workgroups of the first version walked the classes one after
-// the other - a quarter of the CUs, 37 us per 480 x 854 frame with four classes).  min / max do not depend on the order: same bits.
-__device__ __forceinline__ void seg_minmax_exact_body(const float* __restrict__ seg, float* __restrict__ partial, int H, int W, int CO, int Ho,
-                                                      int Wo) {
-  __shared__ float smn[256], smx[256];
-  const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  const int total = Ho * Wo, c = blockIdx.y;
-  const int stride = gridDim.x * 256, dy = stride / Wo, dx = stride - dy * Wo;
-  float mn = INFINITY, mx = -INFINITY;
-  int p = blockIdx.x * 256 + threadIdx.x, oy = p / Wo, ox = p - oy * Wo;
-  for (; p < total; p += stride) {
-    const float v = bilerp_exact(seg, H, W, CO, c, oy, ox, sy, sx);
-    mn = v < mn ? v : mn; mx = v > mx ? v : mx;
-    oy += dy; ox += dx;
-    if (ox >= Wo) { ox -= Wo; ++oy; }
-  }
-  smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const float o1 = smn[threadIdx.x + s], o2 = smx[threadIdx.x + s];
-      smn[threadIdx.x] = o1 < smn[threadIdx.x] ? o1 : smn[threadIdx.x];
-      smx[threadIdx.x] = o2 > smx[threadIdx.x] ? o2 : smx[threadIdx.x];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[((size_t)blockIdx.x * CO + c) * 2] = smn[0];
-    partial[((size_t)blockIdx.x * CO + c) * 2 + 1] = smx[0];
-  }
-}
-
-__device__ __forceinline__ void seg_argmax_exact_body(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
-                                                      uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
-  __shared__ float smn[LP_MAX_CLASSES], smx[LP_MAX_CLASSES];
-  if ((int)threadIdx.x < CO) {
-    float mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < nblk; ++b) {
-      const float p0 = partial[((size_t)b * CO + threadIdx.x) * 2], p1 = partial[((size_t)b * CO + threadIdx.x) * 2 + 1];
-      mn = p0 < mn ? p0 : mn; mx = p1 > mx ? p1 : mx;
-    }
-    smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-  }
-  __syncthreads();
-  const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  const int total = Ho * Wo;
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < total; p += gridDim.x * 256) {
-    const int oy = p / Wo, ox = p % Wo;
-    float best = -INFINITY;
-    int bc = 0;
-    for (int c = 0; c < CO; ++c) {
-      float v = bilerp_exact(seg, H, W, CO, c, oy, ox, sy, sx);
-      if (smx[c] > 0.f) v = (v - smn[c]) / (smx[c] - smn[c] + 1e-12f);
-      if (v > best) { best = v; bc = c; }
-    }
-    label[p] = (uint8_t)bc;
-  }
-}
-
+// post-processing (vanilla_tracker.py:162-181): the bodies and the launcher are vfs_segpost.h's.  Included HERE, below this file's
+// contract(off), its text is compiled with every step a single fp32 operation (oracle: xo_bilerp / xo_seg_postprocess)
+#ifdef VFS_SEGPOST_H
+#error "vfs_segpost.h came in above `#pragma clang fp contract(off)`: the exact post-processing would be compiled with contraction"
+#endif
+#include "vfs_segpost.h"
 __global__ __launch_bounds__(256) void seg_minmax_exact_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
                                                                int CO, int Ho, int Wo) {
-  seg_minmax_exact_body(seg, partial, H, W, CO, Ho, Wo);
+  seg_minmax_body(seg, partial, H, W, CO, Ho, Wo);
 }
 __global__ __launch_bounds__(256) void seg_argmax_exact_kernel(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
                                                                uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
-  seg_argmax_exact_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
+  seg_argmax_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
 }
-// lock-step batch: slot blockIdx.z post-processes ITS propagated frame (frame qframe of its label rows [frame][H*W][CO_n]) with its own
-// class count into the row's map position of its label maps (seg_post_slot: vfs_lpb.h); the class dimension of the min / max grid is sized for COcap
-__global__ __launch_bounds__(256) void seg_minmax_exact_batch_kernel(SegPostBatchArgs b) {
-  const float* seg; float* partial; uint8_t* label; int CO;
-  if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;
-  seg_minmax_exact_body(seg, partial, b.H, b.W, CO, b.Ho, b.Wo);
-}
-__global__ __launch_bounds__(256) void seg_argmax_exact_batch_kernel(SegPostBatchArgs b) {
-  const float* seg; float* partial; uint8_t* label; int CO;
-  if (!seg_post_slot(b, seg, partial, label, CO)) return;
-  seg_argmax_exact_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
-}
+__global__ __launch_bounds__(256) void seg_minmax_exact_batch_kernel(SegPostBatchArgs b) { seg_minmax_batch_body(b); }
+__global__ __launch_bounds__(256) void seg_argmax_exact_batch_kernel(SegPostBatchArgs b) { seg_argmax_batch_body(b); }
 int vfs_seg_postprocess_exact_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
                                            int W, int COcap, int Ho, int Wo, hipStream_t s) {
-  if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact_batch: 1 <= classes <= 256");
-  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
-  hipLaunchKernelGGL(seg_minmax_exact_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
-  int rc = vfs_check_launch("seg_minmax_exact_batch");
-  if (rc) return rc;
-  int blocks = (Ho * Wo + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(seg_argmax_exact_batch_kernel, dim3(blocks, 1, nslots), dim3(256), 0, s, b);
-  return vfs_check_launch("seg_argmax_exact_batch");
+  const SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
+  return seg_post_launch("seg_postprocess_exact_batch", "seg_minmax_exact_batch", "seg_argmax_exact_batch", COcap, nslots, Ho, Wo,
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_minmax_exact_batch_kernel, g, dim3(256), 0, s, b); },
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_argmax_exact_batch_kernel, g, dim3(256), 0, s, b); });
 }
-
 int vfs_seg_postprocess_exact_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                                      hipStream_t s) {
-  if (CO < 1 || CO > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_exact: 1 <= classes <= 256");
-  const int nblk = LP_POST_BLOCKS;
-  hipLaunchKernelGGL(seg_minmax_exact_kernel, dim3(nblk, CO), dim3(256), 0, s, seg, partial, H, W, CO, Ho, Wo);
-  int rc = vfs_check_launch("seg_minmax_exact");
-  if (rc) return rc;
-  int blocks = (Ho * Wo + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(seg_argmax_exact_kernel, dim3(blocks), dim3(256), 0, s, seg, partial, nblk, label, H, W, CO, Ho, Wo);
-  return vfs_check_launch("seg_argmax_exact");
+  return seg_post_launch("seg_postprocess_exact", "seg_minmax_exact", "seg_argmax_exact", CO, 1, Ho, Wo,
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_minmax_exact_kernel, g, dim3(256), 0, s, seg, partial, H, W, CO, Ho, Wo); },
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_argmax_exact_kernel, g, dim3(256), 0, s, seg, partial, LP_POST_BLOCKS, label, H, W, CO, Ho, Wo); });
 }
 
 // F.interpolate(mode='bilinear', align_corners=False) between arbitrary layouts (element (c, y, x) of a map at
@@ -935,18 +840,10 @@ __device__ __forceinline__ void bilinear_resize_f32_body(const float* __restrict
   const int c = (int)(i % C);
   const long long p = i / C;
   const int ox = (int)(p % Wo), oy = (int)(p / Wo);
-  const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  float fy = sy * ((float)oy + 0.5f) - 0.5f, fx = sx * ((float)ox + 0.5f) - 0.5f;
-  fy = fy < 0.f ? 0.f : fy; fx = fx < 0.f ? 0.f : fx;
-  const int y0 = (int)fy, x0 = (int)fx;
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
+  const SegTaps t = seg_taps(H, W, oy, ox, (float)H / (float)Ho, (float)W / (float)Wo);
   const float* s = src + (size_t)c * ssc;
-  const float v00 = s[y0 * ssy + x0 * ssx], v01 = s[y0 * ssy + x1 * ssx];
-  const float v10 = s[y1 * ssy + x0 * ssx], v11 = s[y1 * ssy + x1 * ssx];
-  const float top = hx * v00 + lx * v01, bot = hx * v10 + lx * v11;
-  dst[(size_t)c * dsc + (size_t)oy * dsy + (size_t)ox * dsx] = hy * top + ly * bot;
+  dst[(size_t)c * dsc + (size_t)oy * dsy + (size_t)ox * dsx] =
+      seg_blend(t, s[t.y0 * ssy + t.x0 * ssx], s[t.y0 * ssy + t.x1 * ssx], s[t.y1 * ssy + t.x0 * ssx], s[t.y1 * ssy + t.x1 * ssx]);
 }
 __global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int H, int W,
                                                                   int Ho, int Wo, long long ssc, long long ssy, long long ssx, long long dsc,

@@ -1,5 +1,5 @@
 // DAVIS label propagation for gfx950: local-window affinity on MFMA + streaming top-k + softmax
-// + value gather in ONE kernel, and the bilinear-upsample / min-max / argmax post-processing.
+// + value gather in ONE kernel, and the kernels of the bilinear-upsample / min-max / argmax post-processing (their text: vfs_segpost.h).
 //
 // Replaces masked_attention_efficient (mmaction/models/common/local_attention.py:237-348) with
 // the circular spatial_neighbor mask (common/affinity_utils.py:144-156), as called per frame by
@@ -18,6 +18,7 @@
 #include "vfs_lpb.h"
 #include "vfs_ops.h"
 #include "vfs_rows.h"
+#include "vfs_segpost.h"
 
 #define LP_TOPK 10
 
@@ -282,11 +283,17 @@ __global__ __launch_bounds__(256) void labelprop_merge_batch_kernel(LpBatchArgs 
   if (lp_slot_args(b, a, nsplit)) labelprop_merge_body(a, nsplit);
 }
 
+// the checks of both launchers below; who: the entry point in the error text, nkeys: the most key frames a video of the launch has
+static int labelprop_check(const char* who, int C, int nkeys, int topk, int H, int W) {
+  if (C % 64) return vfs_fail(VFS_ERR_SHAPE, who, "C%64");
+  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= nkeys <= 64");
+  if (topk < 1 || topk > LP_TOPK) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= topk <= 10");
+  if (H >= 65536 || W >= 65536) return vfs_fail(VFS_ERR_SHAPE, who, "H,W < 65536");
+  return VFS_OK;
+}
+
 int vfs_labelprop_launch(const LabelPropArgs& a, hipStream_t s) {
-  if (a.C % 64) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: C%64");
-  if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: 1 <= nkeys <= 64");
-  if (a.topk < 1 || a.topk > LP_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: 1 <= topk <= 10");
-  if (a.H >= 65536 || a.W >= 65536) return vfs_set_error(VFS_ERR_SHAPE, "labelprop: H,W < 65536");
+  if (int rc = labelprop_check("labelprop", a.C, a.nkeys, a.topk, a.H, a.W)) return rc;
   const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
   if (a.pval == nullptr || a.pidx == nullptr) return vfs_set_error(VFS_ERR_ARG, "labelprop: partial workspace missing");
   const int nsplit = lp_splits_for(a.nkeys, tiles);
@@ -299,10 +306,7 @@ int vfs_labelprop_launch(const LabelPropArgs& a, hipStream_t s) {
 
 // every slot of one lock-step: the two launches of one video, each slot with the key-frame split of its own nkeys
 int vfs_labelprop_batch_launch(const LpBatchArgs& b, hipStream_t s) {
-  if (b.C % 64) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: C%64");
-  if (b.max_nkeys < 1 || b.max_nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: 1 <= max_nkeys <= 64");
-  if (b.topk < 1 || b.topk > LP_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: 1 <= topk <= 10");
-  if (b.H >= 65536 || b.W >= 65536) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_batch: H,W < 65536");
+  if (int rc = labelprop_check("labelprop_batch", b.C, b.max_nkeys, b.topk, b.H, b.W)) return rc;
   const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8);
   int most = 1;
   for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lp_splits_for(nk, tiles));
@@ -314,81 +318,8 @@ int vfs_labelprop_batch_launch(const LpBatchArgs& b, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// post-processing of one propagated frame (vanilla_tracker.py:162-181):
-//   up = F.interpolate(seg[HW][CO] -> [Ho][Wo], bilinear, align_corners=False)
-//   per channel: (up - min)/(max - min + 1e-12) where max > 0
-//   label = argmax over channels (first maximum) -> uint8
-// pass 1: per-channel min / max of the upsampled map (one partial per workgroup, fixed order)
-__device__ __forceinline__ float bilerp(const float* __restrict__ seg, int H, int W, int CO, int c, int oy, int ox,
-                                        float sy, float sx) {
-  float fy = sy * ((float)oy + 0.5f) - 0.5f, fx = sx * ((float)ox + 0.5f) - 0.5f;
-  fy = fy < 0.f ? 0.f : fy; fx = fx < 0.f ? 0.f : fx;
-  const int y0 = (int)fy, x0 = (int)fx;
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const float v00 = seg[((size_t)y0 * W + x0) * CO + c], v01 = seg[((size_t)y0 * W + x1) * CO + c];
-  const float v10 = seg[((size_t)y1 * W + x0) * CO + c], v11 = seg[((size_t)y1 * W + x1) * CO + c];
-  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
-}
-
-// grid (LP_POST_BLOCKS, CO): one class per workgroup (as seg_minmax_exact_kernel, csrc/exact_f32.hip)
-__device__ __forceinline__ void seg_minmax_body(const float* __restrict__ seg, float* __restrict__ partial, int H, int W, int CO, int Ho,
-                                                int Wo) {
-  __shared__ float smn[256], smx[256];
-  const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  const int total = Ho * Wo, c = blockIdx.y;
-  const int stride = gridDim.x * 256, dy = stride / Wo, dx = stride - dy * Wo;
-  float mn = INFINITY, mx = -INFINITY;
-  int p = blockIdx.x * 256 + threadIdx.x, oy = p / Wo, ox = p - oy * Wo;
-  for (; p < total; p += stride) {
-    const float v = bilerp(seg, H, W, CO, c, oy, ox, sy, sx);
-    mn = fminf(mn, v); mx = fmaxf(mx, v);
-    oy += dy; ox += dx;
-    if (ox >= Wo) { ox -= Wo; ++oy; }
-  }
-  smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + s]);
-      smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[((size_t)blockIdx.x * CO + c) * 2] = smn[0];
-    partial[((size_t)blockIdx.x * CO + c) * 2 + 1] = smx[0];
-  }
-}
-
-__device__ __forceinline__ void seg_argmax_body(const float* __restrict__ seg, const float* __restrict__ partial, int nblk,
-                                                uint8_t* __restrict__ label, int H, int W, int CO, int Ho, int Wo) {
-  __shared__ float smn[LP_MAX_CLASSES], smx[LP_MAX_CLASSES];
-  if ((int)threadIdx.x < CO) {
-    float mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < nblk; ++b) {
-      mn = fminf(mn, partial[((size_t)b * CO + threadIdx.x) * 2]);
-      mx = fmaxf(mx, partial[((size_t)b * CO + threadIdx.x) * 2 + 1]);
-    }
-    smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-  }
-  __syncthreads();
-  const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  const int total = Ho * Wo;
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < total; p += gridDim.x * 256) {
-    const int oy = p / Wo, ox = p % Wo;
-    float best = -INFINITY;
-    int bc = 0;
-    for (int c = 0; c < CO; ++c) {
-      float v = bilerp(seg, H, W, CO, c, oy, ox, sy, sx);
-      if (smx[c] > 0.f) v = (v - smn[c]) / (smx[c] - smn[c] + 1e-12f);
-      if (v > best) { best = v; bc = c; }
-    }
-    label[p] = (uint8_t)bc;
-  }
-}
-
+// post-processing of one propagated frame (vanilla_tracker.py:162-181): the bodies and the launcher are vfs_segpost.h's, compiled here
+// with the compiler's default contraction (exact_f32.hip compiles the same text without)
 __global__ __launch_bounds__(256) void seg_minmax_kernel(const float* __restrict__ seg, float* __restrict__ partial, int H, int W,
                                                          int CO, int Ho, int Wo) {
   seg_minmax_body(seg, partial, H, W, CO, Ho, Wo);
@@ -398,42 +329,20 @@ __global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict
                                                          int Wo) {
   seg_argmax_body(seg, partial, nblk, label, H, W, CO, Ho, Wo);
 }
-// lock-step batch: slot blockIdx.z post-processes its propagated frame with its own class count (seg_post_slot: vfs_lpb.h); the class
-// dimension of the min / max grid is sized for COcap
-__global__ __launch_bounds__(256) void seg_minmax_batch_kernel(SegPostBatchArgs b) {
-  const float* seg; float* partial; uint8_t* label; int CO;
-  if (!seg_post_slot(b, seg, partial, label, CO) || (int)blockIdx.y >= CO) return;
-  seg_minmax_body(seg, partial, b.H, b.W, CO, b.Ho, b.Wo);
-}
-__global__ __launch_bounds__(256) void seg_argmax_batch_kernel(SegPostBatchArgs b) {
-  const float* seg; float* partial; uint8_t* label; int CO;
-  if (!seg_post_slot(b, seg, partial, label, CO)) return;
-  seg_argmax_body(seg, partial, LP_POST_BLOCKS, label, b.H, b.W, CO, b.Ho, b.Wo);
-}
+__global__ __launch_bounds__(256) void seg_minmax_batch_kernel(SegPostBatchArgs b) { seg_minmax_batch_body(b); }
+__global__ __launch_bounds__(256) void seg_argmax_batch_kernel(SegPostBatchArgs b) { seg_argmax_batch_body(b); }
 int vfs_seg_postprocess_batch_launch(const float* sbank, float* partial, uint8_t* preds, const int* desc, int nslots, int Tcap, int Tmaps, int H,
                                      int W, int COcap, int Ho, int Wo, hipStream_t s) {
-  if (COcap < 1 || COcap > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess_batch: 1 <= classes <= 256");
-  SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
-  hipLaunchKernelGGL(seg_minmax_batch_kernel, dim3(LP_POST_BLOCKS, COcap, nslots), dim3(256), 0, s, b);
-  int rc = vfs_check_launch("seg_minmax_batch");
-  if (rc) return rc;
-  int blocks = (Ho * Wo + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(seg_argmax_batch_kernel, dim3(blocks, 1, nslots), dim3(256), 0, s, b);
-  return vfs_check_launch("seg_argmax_batch");
+  const SegPostBatchArgs b{sbank, partial, preds, desc, Tcap, Tmaps, COcap, H, W, Ho, Wo};
+  return seg_post_launch("seg_postprocess_batch", "seg_minmax_batch", "seg_argmax_batch", COcap, nslots, Ho, Wo,
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_minmax_batch_kernel, g, dim3(256), 0, s, b); },
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_argmax_batch_kernel, g, dim3(256), 0, s, b); });
 }
-
 int vfs_seg_postprocess_launch(const float* seg, float* partial, uint8_t* label, int H, int W, int CO, int Ho, int Wo,
                                hipStream_t s) {
-  if (CO < 1 || CO > LP_MAX_CLASSES) return vfs_set_error(VFS_ERR_SHAPE, "seg_postprocess: 1 <= classes <= 256");
-  const int nblk = LP_POST_BLOCKS;
-  hipLaunchKernelGGL(seg_minmax_kernel, dim3(nblk, CO), dim3(256), 0, s, seg, partial, H, W, CO, Ho, Wo);
-  int rc = vfs_check_launch("seg_minmax");
-  if (rc) return rc;
-  int blocks = (Ho * Wo + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(seg_argmax_kernel, dim3(blocks), dim3(256), 0, s, seg, partial, nblk, label, H, W, CO, Ho, Wo);
-  return vfs_check_launch("seg_argmax");
+  return seg_post_launch("seg_postprocess", "seg_minmax", "seg_argmax", CO, 1, Ho, Wo,
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_minmax_kernel, g, dim3(256), 0, s, seg, partial, H, W, CO, Ho, Wo); },
+                         [&](dim3 g) { hipLaunchKernelGGL(seg_argmax_kernel, g, dim3(256), 0, s, seg, partial, LP_POST_BLOCKS, label, H, W, CO, Ho, Wo); });
 }
 
 // one-hot of a uint8 label map into the fp32 seg bank (vanilla_tracker.py:96-100)

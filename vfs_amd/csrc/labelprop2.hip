@@ -1004,7 +1004,7 @@ __device__ __forceinline__ bool lp2_slot_args(const LpBatchArgs& b, Lp2SlotArgs&
   a.H = b.H; a.W = b.W; a.C = b.C; a.CO = r.CO; a.radius = b.radius; a.topk = b.topk; a.non_mask_len = r.non_mask_len;
   a.temperature = b.temperature; a.margin = b.margin;
   a.nsplit = lp2_splits_for(b.want_splits, r.nkeys, b.fpb_opt);
-  a.cap = min(b.cap_opt > 0 ? b.cap_opt : LP2_LIST_MAX, min(LP2_LIST_MAX, b.entries / a.nsplit));      // >= 1: checked by the launcher for the most splits a slot can have
+  a.cap = lp2_cap(b.cap_opt, b.entries, a.nsplit);      // >= 1: checked by the launcher for the most splits a slot can have
   a.xcd_order = 0;      // (the XCD-aware order is defined on a one-video grid)
   a.dbg = b.dbg; a.trim = b.trim; a.entries = b.entries;
   return true;
@@ -1058,8 +1058,31 @@ int vfs_lp2_wanted_splits(int H, int W, int nactive) {
 }
 int vfs_lp2_splits(int H, int W, int nkeys, int nactive) { return lp2_splits_for(vfs_lp2_wanted_splits(H, W, nactive), nkeys, vfs_option_lp2_fpb); }
 
-// C = 64, 128: the narrow pass 1 (lp2_score_narrow_body); C = 2048 stays on the dense kernel (the query tile does not fit in registers)
-bool vfs_lp2_eligible(int C) { return vfs_option_lp2 && (C == 64 || C == 128 || C == 256 || C == 512 || C == 1024); }
+// The supported channel widths, ONE line each: X(C, pass-1 kernel family, its NG, NP of pass 2).  C = 64, 128: the narrow pass 1
+// (lp2_score_narrow_body); C = 2048 stays on the dense kernel (the query tile does not fit in registers)
+#define LP2_WIDTHS(X) \
+  X(64, lp2_score_narrow, 4, 2) \
+  X(128, lp2_score_narrow, 8, 4) \
+  X(256, lp2_score, 4, 8) \
+  X(512, lp2_score, 8, 8) \
+  X(1024, lp2_score, 16, 8)
+#define LP2_NAME(c, fam, ng, np) " " #c
+static const char lp2_widths_text[] = "C must be one of" LP2_WIDTHS(LP2_NAME);
+#undef LP2_NAME
+bool vfs_lp2_eligible(int C) {
+#define LP2_IS(c, fam, ng, np) || C == c
+  return vfs_option_lp2 && (false LP2_WIDTHS(LP2_IS));
+#undef LP2_IS
+}
+// the kernels of a launch form, named by its argument struct: Lp2Args = one video, LpBatchArgs = every slot of a lock-step
+inline auto lp2_seed_for(const Lp2Args&) { return lp2_seed_kernel; }
+inline auto lp2_seed_for(const LpBatchArgs&) { return lp2_seed_batch_kernel; }
+template <int NG> auto lp2_score_for(const Lp2Args&) { return lp2_score_kernel<NG>; }
+template <int NG> auto lp2_score_for(const LpBatchArgs&) { return lp2_score_batch_kernel<NG>; }
+template <int NG> auto lp2_score_narrow_for(const Lp2Args&) { return lp2_score_narrow_kernel<NG>; }
+template <int NG> auto lp2_score_narrow_for(const LpBatchArgs&) { return lp2_score_narrow_batch_kernel<NG>; }
+template <int NP> auto lp2_refine_for(const Lp2Args&) { return lp2_refine_kernel<NP>; }
+template <int NP> auto lp2_refine_for(const LpBatchArgs&) { return lp2_refine_batch_kernel<NP>; }
 
 static float lp2_margin(int C) {
   // |s~ - s| <= EPS for unit rows: 3 * 2^-16 (the dropped lo.lo product and the two representation remainders, Cauchy-Schwarz) +
@@ -1072,47 +1095,62 @@ static float lp2_margin(int C) {
   return 2.0f * (3.0f / 65536.0f + 4.0f * (float)C / 16777216.0f) + 1.0f / 2097152.0f;
 }
 
+// the checks of both launchers below; who: the entry point in the error text, nkeys: the most key frames a video of the launch has
+static int lp2_check(const char* who, int C, int nkeys, int topk, int H, int W, float temperature) {
+  if (!vfs_lp2_eligible(C)) return vfs_fail(VFS_ERR_SHAPE, who, lp2_widths_text);
+  if (nkeys < 1 || nkeys > LP_MAX_KEYS) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= nkeys <= 64");
+  if (topk < 1 || topk > LPX_TOPK) return vfs_fail(VFS_ERR_SHAPE, who, "1 <= topk <= 10");
+  if (H >= 32768 || W >= 65536 || (long long)nkeys * H * W >= 0x7fffffffLL || (long long)H * W * C * 4 >= 0xFFFFFFF0LL)
+    return vfs_fail(VFS_ERR_SHAPE, who, "map too large");
+  if (!(temperature > 0.f)) return vfs_fail(VFS_ERR_ARG, who, "temperature > 0");
+  return VFS_OK;
+}
+static const char lp2_no_room[] = "the workspace holds less than one list entry per (key-frame split, query)";
+
+// memset of the overflow words, seed, score, refine: the launches of one video (A = Lp2Args, nslots = 1) or of every slot of a
+// lock-step (A = LpBatchArgs).  nsplit: the most key-frame splits a video of the launch has; names: the kernels in the error texts
+template <class A>
+static int lp2_launch(const char* who, const char* const (&names)[3], const A& a, int nslots, int nsplit, hipStream_t s) {
+  const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
+  const dim3 per_query((a.H * a.W + 3) / 4, 1, nslots), per_tile(tiles * nsplit, 1, nslots);
+  if (hipMemsetAsync(a.flags, 0, sizeof(int) * nslots, s) != hipSuccess) return vfs_fail(VFS_ERR_LAUNCH, who, "hipMemsetAsync");
+  hipLaunchKernelGGL(lp2_seed_for(a), per_query, dim3(256), 0, s, a);
+  if (int rc = vfs_check_launch(names[0])) return rc;
+  switch (a.C) {
+#define LP2_SCORE(c, fam, ng, np) case c: hipLaunchKernelGGL(fam##_for<ng>(a), per_tile, dim3(256), 0, s, a); break;
+    LP2_WIDTHS(LP2_SCORE)
+#undef LP2_SCORE
+    default: return vfs_fail(VFS_ERR_SHAPE, who, lp2_widths_text);
+  }
+  if (int rc = vfs_check_launch(names[1])) return rc;
+  switch (a.C) {
+#define LP2_REFINE(c, fam, ng, np) case c: hipLaunchKernelGGL(lp2_refine_for<np>(a), per_query, dim3(256), 0, s, a); break;
+    LP2_WIDTHS(LP2_REFINE)
+#undef LP2_REFINE
+    default: return vfs_fail(VFS_ERR_SHAPE, who, lp2_widths_text);
+  }
+  return vfs_check_launch(names[2]);
+}
+
 int vfs_labelprop_f32_2pass_launch(Lp2Args a, hipStream_t s) {
-  if (!vfs_lp2_eligible(a.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: C must be 64, 128, 256, 512 or 1024");
-  if (a.nkeys < 1 || a.nkeys > LP_MAX_KEYS) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: 1 <= nkeys <= 64");
-  if (a.topk < 1 || a.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: 1 <= topk <= 10");
-  if (a.H >= 32768 || a.W >= 65536 || (long long)a.nkeys * a.H * a.W >= 0x7fffffffLL || (long long)a.H * a.W * a.C * 4 >= 0xFFFFFFF0LL)
-    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass: map too large");
-  if (!(a.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass: temperature > 0");
+  static const char who[] = "labelprop_f32_2pass";
+  if (int rc = lp2_check(who, a.C, a.nkeys, a.topk, a.H, a.W, a.temperature)) return rc;
   a.margin = lp2_margin(a.C);
   a.nsplit = vfs_lp2_splits(a.H, a.W, a.nkeys);
   // the list workspace (LP2_MAX_SPLIT x LP2_MAX_CAP entries per query) is shared out among the splits in use: the first steps of a
   // clip have few key frames (few splits) and cold thresholds (long lists)
-  a.cap = min(vfs_option_lp2_cap > 0 ? vfs_option_lp2_cap : LP2_LIST_MAX, min(LP2_LIST_MAX, a.entries / a.nsplit));
-  if (a.cap < 1) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass: the workspace holds less than one list entry per (key-frame split, query)");
-  const int tiles = ((a.H + 7) / 8) * ((a.W + 7) / 8);
-  if (hipMemsetAsync(a.flags, 0, sizeof(int), s) != hipSuccess) return vfs_set_error(VFS_ERR_LAUNCH, "labelprop_f32_2pass: hipMemsetAsync");
-  hipLaunchKernelGGL(lp2_seed_kernel, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
-  int rcs = vfs_check_launch("lp2_seed");
-  if (rcs) return rcs;
+  a.cap = lp2_cap(vfs_option_lp2_cap, a.entries, a.nsplit);
+  if (a.cap < 1) return vfs_fail(VFS_ERR_ARG, who, lp2_no_room);
   a.xcd_order = vfs_option_lp2_xcd >= 0 ? vfs_option_lp2_xcd : (a.C >= 1024 ? 1 : 0);
   a.trim = vfs_option_lp2_trim;
   a.dbg = vfs_option_lp2_dbg;
-  if (a.C == 64) hipLaunchKernelGGL(lp2_score_narrow_kernel<4>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
-  else if (a.C == 128) hipLaunchKernelGGL(lp2_score_narrow_kernel<8>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
-  else if (a.C == 256) hipLaunchKernelGGL(lp2_score_kernel<4>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
-  else if (a.C == 512) hipLaunchKernelGGL(lp2_score_kernel<8>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(lp2_score_kernel<16>, dim3(tiles * a.nsplit), dim3(256), 0, s, a);
-  int rc = vfs_check_launch("lp2_score");
-  if (rc) return rc;
-  if (a.C == 64) hipLaunchKernelGGL(lp2_refine_kernel<2>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
-  else if (a.C == 128) hipLaunchKernelGGL(lp2_refine_kernel<4>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(lp2_refine_kernel<8>, dim3((a.H * a.W + 3) / 4), dim3(256), 0, s, a);
-  return vfs_check_launch("lp2_refine");
+  return lp2_launch(who, {"lp2_seed", "lp2_score", "lp2_refine"}, a, 1, a.nsplit, s);
 }
 
-// every slot of one lock-step: memset of the slots' overflow words, seed, score, refine - the launches of one video
+// every slot of one lock-step: the launches of one video
 int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t s) {
-  if (!vfs_lp2_eligible(b.C)) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: C must be 64, 128, 256, 512 or 1024");
-  if (b.topk < 1 || b.topk > LPX_TOPK) return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: 1 <= topk <= 10");
-  if (b.H >= 32768 || b.W >= 65536 || (long long)b.max_nkeys * b.H * b.W >= 0x7fffffffLL || (long long)b.H * b.W * b.C * 4 >= 0xFFFFFFF0LL)
-    return vfs_set_error(VFS_ERR_SHAPE, "labelprop_f32_2pass_batch: map too large");
-  if (!(b.temperature > 0.f)) return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch: temperature > 0");
+  static const char who[] = "labelprop_f32_2pass_batch";
+  if (int rc = lp2_check(who, b.C, b.max_nkeys, b.topk, b.H, b.W, b.temperature)) return rc;
   b.margin = lp2_margin(b.C);
   b.want_splits = vfs_lp2_wanted_splits(b.H, b.W, nactive);
   b.fpb_opt = vfs_option_lp2_fpb;
@@ -1121,24 +1159,6 @@ int vfs_labelprop_f32_2pass_batch_launch(LpBatchArgs b, int nactive, hipStream_t
   b.dbg = vfs_option_lp2_dbg;
   int most = 1;      // the most key-frame splits a slot of this step can have: the grid, and the least list capacity
   for (int nk = 1; nk <= b.max_nkeys; ++nk) most = max(most, lp2_splits_for(b.want_splits, nk, b.fpb_opt));
-  if (b.entries / most < 1)
-    return vfs_set_error(VFS_ERR_ARG, "labelprop_f32_2pass_batch: the workspace holds less than one list entry per (key-frame split, query)");
-  const int tiles = ((b.H + 7) / 8) * ((b.W + 7) / 8), HW = b.H * b.W;
-  if (hipMemsetAsync(b.flags, 0, sizeof(int) * b.nslots, s) != hipSuccess) return vfs_set_error(VFS_ERR_LAUNCH, "labelprop_f32_2pass_batch: hipMemsetAsync");
-  hipLaunchKernelGGL(lp2_seed_batch_kernel, dim3((HW + 3) / 4, 1, b.nslots), dim3(256), 0, s, b);
-  int rc = vfs_check_launch("lp2_seed_batch");
-  if (rc) return rc;
-  const dim3 grid(tiles * most, 1, b.nslots);
-  if (b.C == 64) hipLaunchKernelGGL(lp2_score_narrow_batch_kernel<4>, grid, dim3(256), 0, s, b);
-  else if (b.C == 128) hipLaunchKernelGGL(lp2_score_narrow_batch_kernel<8>, grid, dim3(256), 0, s, b);
-  else if (b.C == 256) hipLaunchKernelGGL(lp2_score_batch_kernel<4>, grid, dim3(256), 0, s, b);
-  else if (b.C == 512) hipLaunchKernelGGL(lp2_score_batch_kernel<8>, grid, dim3(256), 0, s, b);
-  else hipLaunchKernelGGL(lp2_score_batch_kernel<16>, grid, dim3(256), 0, s, b);
-  rc = vfs_check_launch("lp2_score_batch");
-  if (rc) return rc;
-  const dim3 rgrid((HW + 3) / 4, 1, b.nslots);
-  if (b.C == 64) hipLaunchKernelGGL(lp2_refine_batch_kernel<2>, rgrid, dim3(256), 0, s, b);
-  else if (b.C == 128) hipLaunchKernelGGL(lp2_refine_batch_kernel<4>, rgrid, dim3(256), 0, s, b);
-  else hipLaunchKernelGGL(lp2_refine_batch_kernel<8>, rgrid, dim3(256), 0, s, b);
-  return vfs_check_launch("lp2_refine_batch");
+  if (lp2_cap(b.cap_opt, b.entries, most) < 1) return vfs_fail(VFS_ERR_ARG, who, lp2_no_room);
+  return lp2_launch(who, {"lp2_seed_batch", "lp2_score_batch", "lp2_refine_batch"}, b, b.nslots, most, s);
 }

@@ -218,5 +218,6 @@ __device__ __forceinline__ unsigned mask8_load(const void* bits, long long m, in
 
 int vfs_set_error(int code, const char* msg);  // capi.hip
 int vfs_check_launch(const char* what);        // capi.hip
+int vfs_fail(int code, const char* who, const char* what);   // capi.hip: vfs_set_error with "<who>: <what>", for checks that several entry points share
 
 #include "vfs_options.h"      // the A/B knobs the dispatchers read (extern int vfs_option_*)

@@ -474,6 +474,11 @@ __host__ __device__ inline int lp2_splits_for(int want, int nkeys, int fpb_opt) 
   }
   return (nkeys + fpb - 1) / fpb;
 }
+// list entries per (split, query) when a video's `entries` per query are shared out among nsplit key-frame splits (cap_opt > 0: the
+// lp2_cap option bounds it); < 1: the workspace is too small
+__host__ __device__ inline int lp2_cap(int cap_opt, int entries, int nsplit) {
+  return min(cap_opt > 0 ? cap_opt : LP2_LIST_MAX, min(LP2_LIST_MAX, entries / nsplit));
+}
 // dense kernel: key-frame splits x window sub-splits (blockIdx.y) for nkeys key frames; returns the product, *nsub_out the sub-splits
 __host__ __device__ inline int lpx_splits_for(int nkeys, int tiles, int target, int wgs, int minb, int H, int W, int radius, int* nsub_out) {
   int nsplit = (target + tiles - 1) / tiles;
