@@ -334,6 +334,22 @@ int vfs_stem_pool_bn_bwd_apply(const vfs_bf16* gp, const vfs_bf16* yp, const uin
 int vfs_avgpool_fwd(const vfs_bf16* x, vfs_bf16* y, int N, int HW, int C, vfs_stream_t stream);
 int vfs_avgpool_bwd(const vfs_bf16* g, vfs_bf16* gx, int N, int HW, int C, vfs_stream_t stream);
 
+/* ---- fp32 NCHW <-> bf16 NHWC: the boundary of the module-level autograd entry points (ResNet.forward, SimSiamHead.forward,
+ * DenseSimSiamHead.forward in train mode) and the gradient joins of ResNet.backward_nhwc / SimSiamHead.backward_nhwc.
+ * LDS-tiled transposes over [N][HW][C] <-> [N][C][HW]; HW is free, C a multiple of 64.  VFS_ERR_SHAPE for a null buffer, a
+ * non-positive size, C % 64 != 0, or 2^31 and more 64 x 64 tiles; the NHWC buffers are 16-byte aligned (VFS_ERR_ARG).
+ * vfs_nhwc_bf16_to_nchw_f32: dst = src.float().permute(0, 3, 1, 2).contiguous() of a stage output [N, h, w, C] (exact).
+ * vfs_nchw_f32_to_nhwc_bf16: dst = g.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16) of a cotangent [N, C, h, w]: round to
+ *   nearest even; Inf stays Inf, NaN stays NaN.
+ * vfs_nchw_f32_add_nhwc_bf16: the join, dst = bf16_rne(acc.float() + src.permute(0, 2, 3, 1)) - ONE rounding of the fp32 sum, not
+ *   the two of (acc + src.to(bf16)).  dst may be acc.
+ * vfs_bf16_add: dst = (a.float() + b.float()).to(torch.bfloat16) over n elements (n % 8 == 0, n <= 2^40): the join of two bf16
+ *   gradients in one launch.  dst may be a or b. */
+int vfs_nhwc_bf16_to_nchw_f32(const vfs_bf16* src, float* dst, int N, int HW, int C, vfs_stream_t stream);
+int vfs_nchw_f32_to_nhwc_bf16(const float* src, vfs_bf16* dst, int N, int HW, int C, vfs_stream_t stream);
+int vfs_nchw_f32_add_nhwc_bf16(const float* src, const vfs_bf16* acc, vfs_bf16* dst, int N, int HW, int C, vfs_stream_t stream);
+int vfs_bf16_add(const vfs_bf16* a, const vfs_bf16* b, vfs_bf16* dst, long long n, vfs_stream_t stream);
+
 /* ---- CosineSimLoss over all temporal rolls (sim_loss.py:42-63, sim_siam_head.py:165-174,
  * sim_siam_base_tracker.py:31-56).  loss/gloss: float[K][N]; K = T (intra_video) or 1 */
 int vfs_cosine_loss_fwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2,

@@ -671,6 +671,19 @@ int vfs_avgpool_bwd(const vfs_bf16* g, vfs_bf16* gx, int N, int HW, int C, vfs_s
   return vfs_avgpool_bwd_launch(g, gx, N, HW, C, stream_of(stream));
 }
 
+int vfs_nhwc_bf16_to_nchw_f32(const vfs_bf16* src, float* dst, int N, int HW, int C, vfs_stream_t stream) {
+  return vfs_nhwc_bf16_to_nchw_f32_launch(src, dst, N, HW, C, stream_of(stream));
+}
+int vfs_nchw_f32_to_nhwc_bf16(const float* src, vfs_bf16* dst, int N, int HW, int C, vfs_stream_t stream) {
+  return vfs_nchw_f32_to_nhwc_bf16_launch(src, dst, N, HW, C, stream_of(stream));
+}
+int vfs_nchw_f32_add_nhwc_bf16(const float* src, const vfs_bf16* acc, vfs_bf16* dst, int N, int HW, int C, vfs_stream_t stream) {
+  return vfs_nchw_f32_add_nhwc_bf16_launch(src, acc, dst, N, HW, C, stream_of(stream));
+}
+int vfs_bf16_add(const vfs_bf16* a, const vfs_bf16* b, vfs_bf16* dst, long long n, vfs_stream_t stream) {
+  return vfs_bf16_add_launch(a, b, dst, n, stream_of(stream));
+}
+
 int vfs_cosine_loss_fwd(const vfs_bf16* p1, const vfs_bf16* z1, const vfs_bf16* p2, const vfs_bf16* z2, float* loss, int N,
                         int C, int T, int K, int negative, float weight, vfs_stream_t stream) {
   if (N % T) return vfs_set_error(VFS_ERR_SHAPE, "cosine_loss: N % T");

@@ -166,6 +166,13 @@ int vfs_avgpool_fwd_launch(const bf16_t* x, bf16_t* y, int N, int HW, int C, hip
 int vfs_avgpool_bwd_launch(const bf16_t* g, bf16_t* gx, int N, int HW, int C, hipStream_t s);
 int vfs_bias_grad_launch(const bf16_t* dy, float* db, int M, int C, hipStream_t s);
 
+// ---- layout.hip -------------------------------------------------------------------------------------------
+// fp32 NCHW <-> bf16 NHWC at the module-level autograd boundary, and the gradient joins (maps and checks: layout_host.h)
+int vfs_nhwc_bf16_to_nchw_f32_launch(const bf16_t* src, float* dst, int N, int HW, int C, hipStream_t s);
+int vfs_nchw_f32_to_nhwc_bf16_launch(const float* src, bf16_t* dst, int N, int HW, int C, hipStream_t s);
+int vfs_nchw_f32_add_nhwc_bf16_launch(const float* src, const bf16_t* acc, bf16_t* dst, int N, int HW, int C, hipStream_t s);
+int vfs_bf16_add_launch(const bf16_t* a, const bf16_t* b, bf16_t* dst, long long n, hipStream_t s);
+
 // SimSiam cosine loss, all T temporal rolls at once (sim_siam_base_tracker.py:31-56,
 // sim_siam_head.py:165-174, sim_loss.py:42-63)
 struct LossArgs {

@@ -66,6 +66,12 @@ class BwdRows(NamedTuple):
     nrows: int                        # rows of all groups together
 
 
+class NCHWGrad(NamedTuple):
+    """a gradient as the caller's autograd holds it - fp32 [N, C, h, w] (or [N, C]) - where backward_nhwc takes bf16 NHWC: it is
+    converted (vfs_nchw_f32_to_nhwc_bf16) or joined (vfs_nchw_f32_add_nhwc_bf16) by Engine.grad_join"""
+    t: torch.Tensor
+
+
 class Engine:
     def __init__(self, lib=None):
         self.lib = lib if lib is not None else get_lib()
@@ -332,7 +338,7 @@ class Engine:
         if lin_fused:
             bn = u.bn
             u.sums = self.buf(f'{u.name}.sums', (G, 2, u.cout), torch.float64, dev)
-            u.bnp = self.buf(f'{u.name}.bnp', (G, 4, u.cout), torch.float32, dev)
+            u.bnp = self.buf(f'{u.name}{tag}.bnp', (G, 4, u.cout), torch.float32, dev)
             act = self.buf(f'{u.name}{tag}.act', (N, u.cout), BF16, dev)      # (the shape bn_act gives the head: raw.view(N, cout))
             flops, nbytes = work(N)
             self.timed('conv_igemm', (flops, nbytes + 2.0 * M * u.cout), dev, lib.linear_bn_act,      # (raw AND the activation go out)
@@ -358,7 +364,7 @@ class Engine:
             else:
                 self.timed(self.conv_kind(u, nn_, H, W), work(nn_), dev, lib.conv_fwd, x[n0:n0 + nn_], u.wf, y[n0:n0 + nn_], bias, part,
                            nn_, H, W, u.cin, Ho, Wo, u.cout, u.k, u.k, u.stride, u.pad, s)
-        fin = None if u.bn is None else self._finish_stats(u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer_fin and u.kind != 'stem')
+        fin = None if u.bn is None else self._finish_stats(u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer_fin and u.kind != 'stem', tag)
         return y, Ho, Wo, fin
 
     @staticmethod
@@ -368,21 +374,22 @@ class Engine:
         return (knobs.flag('VFS_FIN_FUSE') and nrows <= knobs.integer('VFS_FIN_MAX_ROWS')
                 and (not xchg or (knobs.flag('VFS_FIN_XCHG') and G * 2 * min(C, 64) <= 256 and C <= 4096)))
 
-    def _finish_stats(self, u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer):
+    def _finish_stats(self, u, y, partial, G, nblk_g, mpg, train, raw_stats, fused, defer, tag=''):
         """where the BatchNorm statistics of u's fresh output y get finished: eval parameters, from the stored output (raw_stats),
         in the prologue of the bn_act that follows (defer: there is one; fused: ONE conv launch wrote the rows in `partial`), or by
-        the launches issued here (SyncBN: with the sums over the ranks in between).  Returns the FinRows for that bn_act, or None"""
+        the launches issued here (SyncBN: with the sums over the ranks in between).  Returns the FinRows for that bn_act, or None.
+        tag: the batch's scale / shift / mean / invstd (u.bnp) belong to the pass - its backward reads them (vfs_amd/autograd.py)"""
         dev = y.device
         s = self.stream(dev)
         lib = self.lib
         bn = u.bn
         C = u.cout
         if not train:
-            u.bnp = self.buf(f'{u.name}.bnp_eval', (1, 4, C), torch.float32, dev)
+            u.bnp = self.buf(f'{u.name}{tag}.bnp_eval', (1, 4, C), torch.float32, dev)      # (per pass: another module under the same name may be alive)
             lib.bn_eval_params(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, u.bnp, C, float(bn.eps), s)
             return None
         u.sums = self.buf(f'{u.name}.sums', (G, 2, C), torch.float64, dev)
-        u.bnp = self.buf(f'{u.name}.bnp', (G, 4, C), torch.float32, dev)
+        u.bnp = self.buf(f'{u.name}{tag}.bnp', (G, 4, C), torch.float32, dev)
         u.nbt_pending += G   # num_batches_tracked, flushed lazily
         params = (bn.weight.data, bn.bias.data, u.bnp, bn.running_mean, bn.running_var)
         if raw_stats:
@@ -460,6 +467,29 @@ class Engine:
         return y
 
     # ------------------------------------------------------------------ backward primitives
+    def grad_join(self, g, new, key, N, HW, C):
+        """the gradient wrt a [N, HW, C] activation: `new` - bf16 NHWC or NCHWGrad - alone (g is None) or joined with the bf16 NHWC
+        gradient g already in flight: bf16_rne(float(g) + new), one launch, one rounding.  A bf16 `new` alone is returned as it is;
+        everything else lands in the engine buffer `key`."""
+        if g is None and not isinstance(new, NCHWGrad):
+            return new
+        dev = new.t.device if isinstance(new, NCHWGrad) else new.device
+        s = self.stream(dev)
+        dst = self.buf(key, (N, HW, C), BF16, dev)
+        if isinstance(new, NCHWGrad):
+            t = new.t.contiguous().float()
+            if t.numel() != N * HW * C:
+                raise ValueError(f'{key}: a gradient of {tuple(t.shape)} for an activation of [{N}, {C}, {HW}]')
+            if g is None:
+                self.timed('layout', (0.0, 6.0 * t.numel()), dev, self.lib.nchw_f32_to_nhwc_bf16, t, dst, N, HW, C, s)
+            else:
+                self.timed('layout', (0.0, 8.0 * t.numel()), dev, self.lib.nchw_f32_add_nhwc_bf16, t, g, dst, N, HW, C, s)
+        else:
+            if new.dtype != BF16 or new.numel() != N * HW * C:
+                raise ValueError(f'{key}: a {new.dtype} gradient of {tuple(new.shape)} for a bf16 activation of [{N}, {HW}, {C}]')
+            self.timed('layout', (0.0, 6.0 * new.numel()), dev, self.lib.bf16_add, g, new.contiguous(), dst, N * HW * C, s)
+        return dst
+
     @staticmethod
     def bwd_row_pixels(mpg, cap):
         """pixels per BatchNorm-backward statistics row: a divisor of the group size mpg (rows never straddle groups), at most cap;

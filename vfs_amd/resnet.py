@@ -331,8 +331,9 @@ class ResNet(nn.Module):
         return a, ah, aw, bctx
 
     def backward_nhwc(self, eng, ctx, grads, on_stage_done=None):
-        """grads: {stage: gradient wrt that stage's output (bf16 NHWC)}; accumulates parameter
-        gradients (the stem needs no input gradient).  on_stage_done(module) is called as soon as
+        """grads: {stage: gradient wrt that stage's output - bf16 NHWC, or engine.NCHWGrad(fp32 NCHW)}; accumulates parameter
+        gradients (the stem needs no input gradient).  Gradients at several stages are joined where the walk reaches the stage's
+        last block (Engine.grad_join).  on_stage_done(module) is called as soon as
         all parameter gradients of a stage / the stem are final (gradient all-reduce overlap)."""
         N, G = ctx['N'], ctx['G']
         blocks = ctx['blocks']
@@ -360,11 +361,15 @@ class ResNet(nn.Module):
                 break
             si = stage_end.get(i)
             if si is not None and si in grads:
-                gs = grads[si]
-                if g is None:
-                    g = gs
-                else:
-                    raise NotImplementedError('gradients at several stages')  # not on the VFS path
+                # the stage's own cotangent, alone or joined with the gradient arriving from the later stages (one launch, one
+                # rounding).  A lone bf16 NHWC gradient is taken as it is (the fused step, the SiamFC probe).
+                joined = g is not None
+                out = blocks[i]['out']
+                g = eng.grad_join(g, grads[si], f'backbone.gstage{si}{ctx.get("tag", "")}', N, out.shape[1] * out.shape[2], out.shape[3])
+                if g.shape != out.shape:
+                    g = g.view(out.shape)
+                if joined:
+                    rows = None      # statistics rows a dgrad emitted describe the gradient before the join
             if g is None:
                 continue
             # the BatchNorm unit that consumes this block's INPUT gradient: the join unit of the block before
@@ -447,11 +452,15 @@ class ResNet(nn.Module):
 
     # ------------------------------------------------------------------ module-level forward
     def forward(self, x):
-        """x [N,3,H,W] fp32 -> stage output(s) [N,C,h,w] fp32 (resnet.py:555-575).  Inference /
-        feature extraction entry point; training goes through the tracker's fused step."""
+        """x [N,3,H,W] fp32 -> stage output(s) [N,C,h,w] fp32 (resnet.py:555-575).  In train mode with gradients enabled and
+        something to train the outputs carry a grad_fn (vfs_amd/autograd.py: backward() accumulates into .grad through the HIP
+        backward); eval mode, no_grad and a fully frozen net are the inference / feature extraction path."""
         from .engine import shared_engine
         if x.requires_grad:
             raise RuntimeError('ResNet.forward is the inference entry point; use SimSiamBaseTracker.forward_train')
+        from . import autograd
+        if autograd.grad_mode(self):
+            return autograd.resnet_forward(self, x)
         eng = shared_engine(x.device)
         N, _, H, W = x.shape
         precision = eval_precision(getattr(self, 'eval_precision', None))

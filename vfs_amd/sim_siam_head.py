@@ -83,23 +83,24 @@ class SimSiamHead(nn.Module):
         self._engine = engine
 
     # ------------------------------------------------------------------ HIP execution
-    def forward_nhwc(self, eng, feat, N, h, w, C, G, train):
-        """feat bf16 [N,h,w,C] (G views stacked) -> z, p bf16 [N,Cout] + ctx."""
+    def forward_nhwc(self, eng, feat, N, h, w, C, G, train, tag=''):
+        """feat bf16 [N,h,w,C] (G views stacked) -> z, p bf16 [N,Cout] + ctx.  tag: buffer namespace of the pass (a second
+        context alive at the same time keeps its own activations, ResNet.forward_nhwc)."""
         dev = feat.device
         s = eng.stream(dev)
-        x = eng.buf('img_head.pooled', (N, C), BF16, dev)
+        x = eng.buf(f'img_head.pooled{tag}', (N, C), BF16, dev)
         eng.lib.avgpool_fwd(feat, x, N, h * w, C, s)
-        ctx = dict(N=N, G=G, h=h, w=w, C=C, ins=[], raws=[], acts=[])
+        ctx = dict(N=N, G=G, h=h, w=w, C=C, ins=[], raws=[], acts=[], tag=tag)
         a = x
         z = None
         for ui, u in enumerate(self.units):
             tr = train and (u.bn.training if u.bn is not None else True)
             ctx['ins'].append(a)
-            raw, _, _, fin = eng.conv_fwd(u, a.view(N, 1, 1, u.cin), N, 1, 1, G, tr, defer_fin=u.bn is not None)
+            raw, _, _, fin = eng.conv_fwd(u, a.view(N, 1, 1, u.cin), N, 1, 1, G, tr, tag=tag, defer_fin=u.bn is not None)
             raw = raw.view(N, u.cout)
             ctx['raws'].append(raw)
             if u.bn is not None:
-                a = eng.bn_act(u, raw, N, G, tr, u.relu, fin)
+                a = eng.bn_act(u, raw, N, G, tr, u.relu, fin, tag=tag)
             else:
                 a = raw
             ctx['acts'].append(a)
@@ -108,21 +109,27 @@ class SimSiamHead(nn.Module):
         return z, a, ctx
 
     def backward_nhwc(self, eng, ctx, dp, dz=None):
-        """dp: gradient wrt p (bf16 [N,C]); z only feeds the predictor (it is detached in the loss)."""
-        N, G = ctx['N'], ctx['G']
-        dev = dp.device
-        g = dp
+        """dp / dz: gradients wrt p / z - bf16 [N,C] or engine.NCHWGrad(fp32 [N,C]), either may be None.  In the SimSiam loss z is
+        detached and only feeds the predictor (dz=None); a dz joins the predictor's gradient at the projector's output
+        (Engine.grad_join: one launch, one rounding)."""
+        N, G, tag = ctx['N'], ctx['G'], ctx.get('tag', '')
+        dev = ctx['raws'][0].device
+        g = None
         for ui in range(len(self.units) - 1, -1, -1):
             u = self.units[ui]
+            if ui == len(self.units) - 1 and dp is not None:
+                g = eng.grad_join(None, dp, f'img_head.dp_in{tag}', N, 1, u.cout).view(N, u.cout)
             if ui == self._n_proj - 1 and dz is not None:
-                raise NotImplementedError('explicit z gradient')
+                g = eng.grad_join(g, dz, f'img_head.dz_join{tag}', N, 1, u.cout).view(N, u.cout)
+            if g is None:
+                continue      # no gradient wrt p: the predictor's layers get none
             if u.bn is not None:
-                dx, _ = eng.bn_bwd(u, g, None, ctx['raws'][ui], N, G, relu=u.relu)
+                dx, _ = eng.bn_bwd(u, g, None, ctx['raws'][ui], N, G, relu=u.relu, tag=tag)
             else:
                 dx = g
-            g, _ = eng.conv_bwd(u, dx, ctx['ins'][ui], N, 1, 1, 1, 1, need_dgrad=True)
+            g, _ = eng.conv_bwd(u, dx, ctx['ins'][ui], N, 1, 1, 1, 1, need_dgrad=True, tag=tag)
             g = g.view(N, u.cin)
-        gfeat = eng.buf('img_head.gfeat', (N, ctx['h'], ctx['w'], ctx['C']), BF16, dev)
+        gfeat = eng.buf(f'img_head.gfeat{tag}', (N, ctx['h'], ctx['w'], ctx['C']), BF16, dev)
         eng.lib.avgpool_bwd(g, gfeat, N, ctx['h'] * ctx['w'], ctx['C'], eng.stream(dev))
         return gfeat
 
@@ -137,8 +144,12 @@ class SimSiamHead(nn.Module):
 
     # ------------------------------------------------------------------ reference-compatible API
     def forward(self, x):
-        """x [N,C,h,w] fp32 -> (z, p) fp32 (sim_siam_head.py:143-163); inference entry point."""
+        """x [N,C,h,w] fp32 -> (z, p) fp32 (sim_siam_head.py:143-163).  Train mode with gradients enabled: z and p carry a grad_fn
+        and x may require grad (vfs_amd/autograd.py); otherwise the inference entry point."""
+        from . import autograd
         from .engine import shared_engine
+        if autograd.grad_mode(self):
+            return autograd.head_forward(self, x)
         if x.requires_grad:
             raise RuntimeError('SimSiamHead.forward is the inference entry point; training runs in the tracker')
         eng = shared_engine()
@@ -256,35 +267,45 @@ class DenseSimSiamHead(nn.Module):
         self._engine = engine
 
     # ------------------------------------------------------------------ HIP execution
-    def forward_nhwc(self, eng, feat, N, h, w, C, G, train):
-        """feat bf16 [N,h,w,C] (G views stacked, each its own BatchNorm batch) -> z, p bf16 [N,h,w,Cout] + ctx."""
+    def forward_nhwc(self, eng, feat, N, h, w, C, G, train, tag=''):
+        """feat bf16 [N,h,w,C] (G views stacked, each its own BatchNorm batch) -> z, p bf16 [N,h,w,Cout] + ctx.  tag: buffer
+        namespace of the pass (SimSiamHead.forward_nhwc)."""
         M = N * h * w
-        ctx = dict(N=N, G=G, h=h, w=w, C=C, ins=[], raws=[], acts=[])
+        ctx = dict(N=N, G=G, h=h, w=w, C=C, ins=[], raws=[], acts=[], tag=tag)
         a, z = feat, None
         for ui, u in enumerate(self.units):
             tr = train and (u.bn.training if u.bn is not None else True)
             ctx['ins'].append(a)
-            raw, _, _, fin = eng.conv_fwd(u, a, N, h, w, G, tr, defer_fin=u.bn is not None)
+            raw, _, _, fin = eng.conv_fwd(u, a, N, h, w, G, tr, tag=tag, defer_fin=u.bn is not None)
             ctx['raws'].append(raw)
-            a = eng.bn_act(u, raw, M, G, tr, u.relu, fin) if u.bn is not None else raw
+            a = eng.bn_act(u, raw, M, G, tr, u.relu, fin, tag=tag) if u.bn is not None else raw
             ctx['acts'].append(a)
             if ui == self._n_proj - 1:
                 z = a
         return z, a, ctx
 
-    def backward_nhwc(self, eng, ctx, dp):
-        """dp: gradient wrt p (bf16 [N,h,w,C]; z is detached in the loss) -> gradient wrt the feature map [N,h,w,C]."""
-        N, G, h, w = ctx['N'], ctx['G'], ctx['h'], ctx['w']
+    def backward_nhwc(self, eng, ctx, dp, dz=None):
+        """dp / dz: gradients wrt p / z - bf16 [N,h,w,C] or engine.NCHWGrad(fp32 [N,C,h,w]), either may be None (z is detached in
+        the loss: dz=None; a dz joins the predictor's gradient at the projector's output, Engine.grad_join) -> gradient wrt the
+        feature map [N,h,w,C]."""
+        N, G, h, w, tag = ctx['N'], ctx['G'], ctx['h'], ctx['w'], ctx.get('tag', '')
         M = N * h * w
-        g, rows = dp, None
+        g, rows = None, None
         for ui in range(len(self.units) - 1, -1, -1):
             u = self.units[ui]
+            if ui == len(self.units) - 1 and dp is not None:
+                g = eng.grad_join(None, dp, f'img_head.dp_in{tag}', N, h * w, u.cout).view(N, h, w, u.cout)
+            if ui == self._n_proj - 1 and dz is not None:
+                g = eng.grad_join(g, dz, f'img_head.dz_join{tag}', N, h * w, u.cout).view(N, h, w, u.cout)
+                rows = None      # statistics rows the dgrad emitted describe the gradient before the join
+            if g is None:
+                continue      # no gradient wrt p: the predictor's layers get none
             if u.bn is not None:
-                g, _ = eng.bn_bwd(u, g, None, ctx['raws'][ui], M, G, relu=u.relu, rows=rows)
+                g, _ = eng.bn_bwd(u, g, None, ctx['raws'][ui], M, G, relu=u.relu, rows=rows, tag=tag)
             # the dgrad also emits the BatchNorm-backward statistics of the layer in front (Engine.conv_bwd)
             prev = self.units[ui - 1] if ui > 0 else None
             bn_next = (prev, ctx['raws'][ui - 1], None, prev.relu, G if prev.bn.training else 1) if prev is not None and prev.bn is not None else None
-            g, rows = eng.conv_bwd(u, g, ctx['ins'][ui], N, h, w, h, w, need_dgrad=True, bn_next=bn_next)
+            g, rows = eng.conv_bwd(u, g, ctx['ins'][ui], N, h, w, h, w, need_dgrad=True, bn_next=bn_next, tag=tag)
         return g
 
     def _check_fused_loss(self):
@@ -316,8 +337,12 @@ class DenseSimSiamHead(nn.Module):
 
     # ------------------------------------------------------------------ reference-compatible API
     def forward(self, x):
-        """x [N,C,h,w] fp32 -> (z, p) [N,Cout,h,w] fp32 (sim_siam_head.py:262-275); inference entry point."""
+        """x [N,C,h,w] fp32 -> (z, p) [N,Cout,h,w] fp32 (sim_siam_head.py:262-275).  Train mode with gradients enabled: z and p
+        carry a grad_fn and x may require grad (vfs_amd/autograd.py); otherwise the inference entry point."""
+        from . import autograd
         from .engine import shared_engine
+        if autograd.grad_mode(self):
+            return autograd.head_forward(self, x)
         if x.requires_grad:
             raise RuntimeError('DenseSimSiamHead.forward is the inference entry point; training runs in the tracker')
         eng = shared_engine()
