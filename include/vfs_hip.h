@@ -399,6 +399,34 @@ int vfs_simloss_bwd(const float* other, const float* invo, const float* mask, in
 int vfs_simloss_norm_bwd(const float* x, const float* inv, const float* d, float* dx, int B, int C, int S,
                          vfs_stream_t stream);
 
+/* ---- Differentiable masked_attention (mmaction/models/common/local_attention.py:161-234 with the circular window of
+ * spatial_neighbor, affinity_utils.py:144-156): forward, and backward wrt query, key and value ------------------------------
+ * fp32 NCHW operands: query [N][C][H*W], key [N][C][T*H*W], value [N][CO][T*H*W], out / dout [N][CO][H*W].
+ * score(i, j) = <k^_i, q^_j> / temperature over the keys i = (t, y', x') with (y - y')^2 + (x - x')^2 < (neighbor_range / 2)^2
+ * of query j = (y, x) (the same window in every key frame; neighbor_range = 0: every key); k^, q^ = F.normalize(dim=1,
+ * eps 1e-12) when normalize, the rows themselves otherwise (:194-196).  The topk largest (equal scores: the lower flat key
+ * index first) are softmaxed and weight the value columns (:212-226).  The window is a test in the kernel: no mask, no
+ * [T*H*W][H*W] affinity.
+ *   fwd: writes out and what the backward needs: idx int32 [N][topk][H*W] (flat key index over T*H*W; -1 = the weight-0 fill
+ *        of a query with fewer than topk in-window keys), weights fp32 [N][topk][H*W] (the softmax; 0 at a fill), and with
+ *        normalize invq [N][H*W], invk [N][T*H*W] = 1 / max(||row||_2, 1e-12) (NULL allowed otherwise).
+ *   bwd: ds_a = w_a (<v_a, dout_j> - sum_b w_b <v_b, dout_j>) / temperature;  dq^_j = sum_a ds_a k^_a;  dk^_i = sum over
+ *        the (j, a) that selected i of ds_a q^_j;  dv_i = sum over the same of w_a dout_j;  dq, dk go through the
+ *        normalisation (d x = inv (g - x^ <x^, g>), as vfs_simloss_norm_bwd).  dq / dk / dv = NULL: that gradient is not
+ *        computed.  No atomics: each key scans the queries that can reach it in ascending index, equal inputs give equal bits.
+ *        workspace: at least vfs_masked_attention_workspace_bytes(...) bytes (host-only query; the size for all three
+ *        gradients); a smaller buffer is REFUSED (VFS_ERR_ARG).
+ * VFS_ERR_SHAPE: topk outside 1..10, neighbor_range 1 or negative, C % 64 != 0 or C > 2048, T outside 1..64, CO outside
+ * 1..256, T*H*W >= 2^31, N outside 1..65535.  VFS_ERR_ARG: a null operand, temperature not positive and finite. */
+int vfs_masked_attention_workspace_bytes(int N, int C, int T, int H, int W, int CO, int topk, int normalize, long long* bytes);
+int vfs_masked_attention_fwd(const float* query, const float* key, const float* value, float* out, int* idx, float* weights,
+                             float* invq, float* invk, int N, int C, int T, int H, int W, int CO, int neighbor_range, int topk,
+                             float temperature, int normalize, vfs_stream_t stream);
+int vfs_masked_attention_bwd(const float* query, const float* key, const float* value, const float* dout, const int* idx,
+                             const float* weights, const float* invq, const float* invk, float* dq, float* dk, float* dv,
+                             void* workspace, long long workspace_bytes, int N, int C, int T, int H, int W, int CO,
+                             int neighbor_range, int topk, float temperature, int normalize, vfs_stream_t stream);
+
 /* ---- SyncBN statistic exchange over xGMI (configs/r*_*.py:9,15 SyncBN under MMDistributedDataParallel, apis/train.py:58-66):
  * a latency-bound all-reduce of <= 8192 doubles among the <= 8 ranks of one node as ONE small kernel - peer stores into
  * IPC-mapped windows + epoch flags (csrc/p2p.hip) - instead of a collective-library call per BatchNorm layer and direction.

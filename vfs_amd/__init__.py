@@ -9,6 +9,7 @@ from .config import Config, ConfigDict  # noqa: F401
 from .registry import BACKBONES, HEADS, LOSSES, TRACKERS, Registry, build_from_cfg  # noqa: F401
 from .resnet import ResNet  # noqa: F401
 from .sim_loss import CosineSimLoss  # noqa: F401
+from .attention import masked_attention  # noqa: F401
 from .sim_siam_head import DenseSimSiamHead, SimSiamHead  # noqa: F401
 from .trackers import BaseTracker, SimSiamBaseTracker, VanillaTracker  # noqa: F401
 from .optim import SGD, Adam, AdamW, LrUpdater, build_lr_updater, build_optimizer, clip_grad_norm_  # noqa: F401

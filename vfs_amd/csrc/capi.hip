@@ -857,6 +857,54 @@ int vfs_simloss_norm_bwd(const float* x, const float* inv, const float* d, float
   return vfs_simloss_norm_bwd_launch(x, inv, d, dx, B, C, S, stream_of(stream));
 }
 
+// masked_attention (attn_train.hip): the limits of the kernels, shared by the three entry points
+static int attn_shape(const char* who, AttnShape& s, int N, int C, int T, int H, int W, int CO, int neighbor_range, int topk, float temperature,
+                      int normalize) {
+  if (N < 1 || N > 65535 || H < 1 || W < 1) return fail(VFS_ERR_SHAPE, who, "1 <= N <= 65535, H >= 1, W >= 1");
+  if (topk < 1 || topk > VFS_ATTN_MAX_TOPK) return fail(VFS_ERR_SHAPE, who, "1 <= topk <= 10");
+  if (neighbor_range != 0 && neighbor_range < 2) return fail(VFS_ERR_SHAPE, who, "neighbor_range >= 2, or 0 for no window");
+  if (C < 64 || C % 64 || C > VFS_ATTN_MAX_C) return fail(VFS_ERR_SHAPE, who, "C % 64 == 0 and C <= 2048");
+  if (T < 1 || T > VFS_ATTN_MAX_T) return fail(VFS_ERR_SHAPE, who, "1 <= T <= 64");
+  if (CO < 1 || CO > VFS_ATTN_MAX_CO) return fail(VFS_ERR_SHAPE, who, "1 <= CO <= 256");
+  if ((long long)T * H * W >= (1ll << 31)) return fail(VFS_ERR_SHAPE, who, "T * H * W < 2^31");
+  if (!(temperature > 0.0f) || !(temperature < INFINITY)) return fail(VFS_ERR_ARG, who, "temperature must be positive and finite");
+  s.N = N; s.C = C; s.T = T; s.H = H; s.W = W; s.CO = CO; s.neighbor_range = neighbor_range; s.topk = topk; s.temperature = temperature;
+  s.normalize = normalize != 0;
+  return VFS_OK;
+}
+int vfs_masked_attention_workspace_bytes(int N, int C, int T, int H, int W, int CO, int topk, int normalize, long long* bytes) {
+  AttnShape s;
+  if (!bytes) return vfs_set_error(VFS_ERR_ARG, "masked_attention_workspace_bytes: null out-pointer");
+  const int rc = attn_shape("masked_attention_workspace_bytes", s, N, C, T, H, W, CO, 0, topk, 1.0f, normalize);
+  if (rc) return rc;
+  *bytes = 4 * vfs_attn_bwd_workspace_floats(s, true, true);
+  return VFS_OK;
+}
+int vfs_masked_attention_fwd(const float* query, const float* key, const float* value, float* out, int* idx, float* weights, float* invq,
+                             float* invk, int N, int C, int T, int H, int W, int CO, int neighbor_range, int topk, float temperature,
+                             int normalize, vfs_stream_t stream) {
+  AttnShape s;
+  const int rc = attn_shape("masked_attention_fwd", s, N, C, T, H, W, CO, neighbor_range, topk, temperature, normalize);
+  if (rc) return rc;
+  if (!query || !key || !value || !out || !idx || !weights || (normalize && (!invq || !invk)))
+    return vfs_set_error(VFS_ERR_ARG, "masked_attention_fwd: null buffer");
+  return vfs_attn_fwd_launch(s, query, key, value, out, idx, weights, invq, invk, stream_of(stream));
+}
+int vfs_masked_attention_bwd(const float* query, const float* key, const float* value, const float* dout, const int* idx, const float* weights,
+                             const float* invq, const float* invk, float* dq, float* dk, float* dv, void* workspace,
+                             long long workspace_bytes, int N, int C, int T, int H, int W, int CO, int neighbor_range, int topk,
+                             float temperature, int normalize, vfs_stream_t stream) {
+  AttnShape s;
+  const int rc = attn_shape("masked_attention_bwd", s, N, C, T, H, W, CO, neighbor_range, topk, temperature, normalize);
+  if (rc) return rc;
+  if (!query || !key || !value || !dout || !idx || !weights || (normalize && (!invq || !invk)))
+    return vfs_set_error(VFS_ERR_ARG, "masked_attention_bwd: null buffer");
+  if (!dq && !dk && !dv) return VFS_OK;
+  if (!workspace || workspace_bytes < 4 * vfs_attn_bwd_workspace_floats(s, dq != nullptr, dk != nullptr))
+    return vfs_set_error(VFS_ERR_ARG, "masked_attention_bwd: workspace smaller than vfs_masked_attention_workspace_bytes");
+  return vfs_attn_bwd_launch(s, query, key, value, dout, idx, weights, invq, invk, dq, dk, dv, static_cast<float*>(workspace), stream_of(stream));
+}
+
 int vfs_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float lr, float momentum,
                  float weight_decay, const void* skip_flag, vfs_stream_t stream) {
   return vfs_sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, nullptr, static_cast<const unsigned long long*>(skip_flag), stream_of(stream));

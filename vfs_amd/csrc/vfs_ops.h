@@ -239,6 +239,21 @@ int vfs_simloss_bwd_launch(const float* other, const float* invo, const float* m
                            int B, int C, int Sself, int Sother, int pairwise, int negative, float weight, hipStream_t s);
 int vfs_simloss_norm_bwd_launch(const float* x, const float* inv, const float* d, float* dx, int B, int C, int S, hipStream_t s);
 
+// ---- attn_train.hip: differentiable masked_attention (local_attention.py:161-234), forward and backward on fp32 NCHW ----
+#define VFS_ATTN_MAX_TOPK 10
+#define VFS_ATTN_MAX_C 2048
+#define VFS_ATTN_MAX_T 64
+#define VFS_ATTN_MAX_CO 256
+struct AttnShape {
+  int N, C, T, H, W, CO, neighbor_range, topk, normalize;      // neighbor_range 0: no window
+  float temperature;
+};
+long long vfs_attn_bwd_workspace_floats(const AttnShape& s, bool need_q, bool need_k);
+int vfs_attn_fwd_launch(const AttnShape& s, const float* q, const float* k, const float* v, float* out, int* idx, float* w, float* invq,
+                        float* invk, hipStream_t st);
+int vfs_attn_bwd_launch(const AttnShape& s, const float* q, const float* k, const float* v, const float* dout, const int* idx, const float* w,
+                        const float* invq, const float* invk, float* dq, float* dk, float* dv, float* ws, hipStream_t st);
+
 // ---- simloss_dense.hip: the same loss per spatial position of bf16 NHWC maps (DenseSimSiamHead, sim_siam_head.py:277-284) ----
 #define DSL_MAX_CHUNKS 4                          // 16-byte chunks a lane of the backward keeps in registers (a, b, gradient)
 #define VFS_DENSE_LOSS_MAX_C (64 * DSL_MAX_CHUNKS * 8)      // = 2048
